@@ -9,15 +9,22 @@ One "step" = one pass of the pose hot path over one batch that is already reside
 NCHW fp32 crops -> NHWC pack -> ResNet-50 + 3x deconv + heatmap conv (HIP graph) -> per-map arg-max /
 sub-pixel nudge (ft_heatmap_max_preds) [-> RCCL all-gather of the keypoint rows when N > 1].
 Workload = BASELINE.json configs[1]: ResNet-50 pose head, fp16, batch 64 x 256x192 per GPU (weak scaling).
-BASELINE.json's metric is "pose crops/sec + flow frame-pairs/sec ...; mAP@OKS vs CPU ref": the headline `value` is the
-pose half; the default run adds, in the SAME JSON line, the sub-records
-  "flow"             FlowNet2S fp16 on configs[3]'s 16 x 512x384 pairs per GPU, timed with the same protocol (its own
-                     roofline, cpu_baseline and `roofline_ops` = the correlation / warp / channelnorm kernels at C4 shapes);
+The timed region is ONE block of exactly K steps after the W warm-up steps (and a short untimed spin-up), bracketed by
+barrier + synchronize; `ms_per_step` = that block's time / K.  A plain run measures the headline and nothing else.
+`--dump-outputs DIR` writes what the last timed step computed (pose: `keypoint_rows` [B,17,3] and `heatmaps`
+[B,17,H/4,W/4]; flow: `flow` [B,2,384,512] and, when sampled, `flow_samples`) as DIR/<name>.npy in float32, <= 64 MB.
+The timed block always starts at resident batch 0, so with the same arguments the last step's inputs are the same.
+`--full` adds, in the SAME JSON line, the rest of BASELINE.json's metric ("pose crops/sec + flow frame-pairs/sec ...;
+mAP@OKS vs CPU ref") and the evidence around it, each timed as the median of blocks of >= 1 s in all:
+  "roofline", "cpu_baseline", "same_batch_replay" of the headline;
+  "flow"             FlowNet2S fp16 on configs[3]'s 16 x 512x384 pairs per GPU (its own roofline, cpu_baseline and
+                     `roofline_ops` = the correlation / warp / channelnorm kernels at C4 shapes);
   "fp32_parity_mode" the pose step in the arithmetic whose arg-max is bit-exact vs the CPU reference;
   "parity"           heat-map error / identical-arg-max fraction / mAP@OKS of both modes on the benchmarked batch vs the
-                     CPU oracle (N = 1 only, outside every timed region).
-`--workload flow` makes FlowNet2S the headline instead; `--no-extras` prints the headline alone.
-Rank 0 prints ONE JSON line.
+                     CPU oracle (N = 1 only, outside every timed region);
+  "c3_per_gpu", "fp16_exact_argmax", "clip" and (N > 1) the "rccl" check of the exchange.
+`--no-extras` / `--no-roofline` / `--no-cpu-baseline` drop parts of a `--full` run.  `--workload flow` makes FlowNet2S
+the headline instead.  Rank 0 prints ONE JSON line.
 """
 from __future__ import annotations
 
@@ -613,6 +620,7 @@ def make_pose_runner(args, device, dtype, rank, world, backbone, H, W, B, force_
     def step():
         plan = plans[state["i"] % len(plans)]
         state["i"] = (state["i"] + 1) % len(plans)
+        state["last"] = plan
         rows = model.replay(plan).kp_rows                    # [B,17,3] (x, y, score) rows written by the plan's last launch
         if gather is None:
             kp_host.copy_(rows, non_blocking=True)
@@ -628,6 +636,8 @@ def make_pose_runner(args, device, dtype, rank, world, backbone, H, W, B, force_
             consume(state["pending"])
             state["pending"] = None
     step.drain = drain
+    step.restart = lambda: state.update(i=0)
+    step.outputs = lambda: {"keypoint_rows": state["last"].kp_rows, "heatmaps": state["last"].heatmaps}
     step.gather = gather
     step.plans = plans
     return model, x, step
@@ -656,6 +666,7 @@ def make_flow_runner(args, device, dtype, rank, world, name, B, gather_mode="sam
     def step():
         plan = plans[state["i"] % len(plans)]
         state["i"] = (state["i"] + 1) % len(plans)
+        state["last"] = plan
         flow = model.replay(plan).out
         if not full:
             torch.index_select(flow.flatten(2), 2, idx, out=samples)
@@ -670,7 +681,15 @@ def make_flow_runner(args, device, dtype, rank, world, name, B, gather_mode="sam
         if state["pending"] is not None:
             gather.finish(state["pending"])
             state["pending"] = None
+
+    def outputs():
+        out = {"flow": state["last"].out}
+        if not full:
+            out["flow_samples"] = samples
+        return out
     step.drain = drain
+    step.restart = lambda: state.update(i=0)
+    step.outputs = outputs
     step.gather = gather
     step.plans = plans
     return model, x, step
@@ -681,19 +700,43 @@ def measure(step, steps, warmup, device, fixed_warmup=False, min_total_s=1.0, ma
     (timed_region).  One block is what the contract asks for; with a small `steps` it is a few tens of milliseconds, one
     preempted step away from a 5 % error, so the block is repeated until >= min_total_s has been timed and the MEDIAN block
     is reported.  The repeat count follows from the first block's (max-over-ranks) time, so every rank runs the same number
-    of blocks.  Returns (median block seconds, repeats, total timed seconds)."""
+    of blocks (max_repeats=1: exactly one block of `steps` steps).  Returns (median block seconds, repeats, total timed seconds).
+    The first block starts at resident batch 0 (step.restart), whatever number of steps the time-based spin-up took."""
     for _ in range(max(warmup, 2)):   # >= 2: first run is eager (+ tile benchmark) + graph capture, second replays the graph
         step()
     if fixed_warmup:                  # profiling runs that count launches: exactly one block
+        getattr(step, "restart", lambda: None)()
         t = timed_region(step, steps, device)
         return t, 1, t
     spin_up(step, device)
+    getattr(step, "restart", lambda: None)()
     blocks = [timed_region(step, steps, device)]
     repeats = min(max_repeats, max(1, int(min_total_s / max(blocks[0], 1e-6)) + 1))
     for _ in range(repeats - 1):
         blocks.append(timed_region(step, steps, device))
     blocks.sort()
     return blocks[len(blocks) // 2], len(blocks), sum(blocks)
+
+
+DUMP_BUDGET_BYTES = 60_000_000   # data of all dumped arrays; headers included, the files stay under 64 MB
+
+
+def dump_outputs(arrays, out_dir, budget=DUMP_BUDGET_BYTES):
+    """Writes every tensor of `arrays` (name -> tensor) as out_dir/<name>.npy in float32.  An array larger than what is left of
+    `budget` is replaced by an evenly strided sample of its flattened elements (the same elements on every run).
+    Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    left, written = budget, {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > left:
+            stride = -(-a.size // max(left // a.itemsize, 1))
+            a = np.ascontiguousarray(a.reshape(-1)[::stride])
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        written[name] = list(a.shape)
+    return written
 
 
 def main():
@@ -712,10 +755,15 @@ def main():
     ap.add_argument("--gather", choices=["sampled", "full", "none"], default="sampled",
                     help="flow, N > 1: all-gather the field sampled at 8 x 17 key points per pair (what the tracker reads), the full fields, or nothing")
     ap.add_argument("--fixed-warmup", action="store_true", help="exactly max(W,2) untimed steps (profiling runs that count launches)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline only: no flow / fp32_parity_mode / parity sub-records")
-    ap.add_argument("--layers", action="store_true", help="also print the per-layer table to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline, cpu_baseline, same_batch_replay, the "
+                         "flow / fp32_parity_mode / parity / c3_per_gpu / fp16_exact_argmax / clip sub-records, the N > 1 rccl check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32, <= 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without roofline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the flow / fp32_parity_mode / parity / ... sub-records")
+    ap.add_argument("--layers", action="store_true", help="with --full: also print the per-layer table to stderr")
     ap.add_argument("--rotate", type=int, default=4, help="resident batches the timed steps go round (1 = replay one batch)")
     ap.add_argument("--config", choices=["c2", "c3", "c5"], default="c2",
                     help="c2 (default) = BASELINE configs[1] per GPU, weak; c3 = configs[2]: ResNet-101 384x288, 128 crops sharded over the "
@@ -736,6 +784,8 @@ def main():
     dtype = torch.float16 if args.dtype == "fp16" else torch.float32
 
     if args.config == "c5":
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: pose and flow workloads only (not --config c5)")
         return main_clips(args, device, rank, world)
     scaling = "weak"
     if args.workload == "pose":
@@ -759,13 +809,14 @@ def main():
         workload = (f"{args.flow_model} {args.dtype}, batch {B} x 512x384 synthetic frame pairs per GPU "
                     f"(BASELINE.json configs[3]{'' if default_cfg else ' shape, other stack'})")
 
-    rccl = parallel.verify_gather(step.gather, rank) if (world > 1 and step.gather is not None) else None
-    elapsed, repeats, total_s = measure(step, args.steps, args.warmup, device, args.fixed_warmup)
+    rccl = parallel.verify_gather(step.gather, rank) if (args.full and world > 1 and step.gather is not None) else None
+    elapsed, repeats, total_s = measure(step, args.steps, args.warmup, device, args.fixed_warmup, max_repeats=1)
+    dumped = dump_outputs(step.outputs(), args.dump_outputs) if (args.dump_outputs and rank == 0) else None
     value = B * world * args.steps / elapsed
     out = {
         "metric": metric, "value": round(value, 2), "unit": unit, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(1e3 * elapsed / args.steps, 4), "repeats": repeats, "timed_region_s": round(total_s, 4),
-        "timing": f"median of {repeats} blocks of exactly {args.steps} steps, barrier + synchronize around each, max over ranks",
+        "timing": f"one block of exactly {args.steps} steps, barrier + synchronize around it, max over ranks",
         "higher_is_better": True, "scaling": scaling, "vs_baseline": None,
         "hip_force_dev_kernarg": __import__("flowtrack.pytorch_amd", fromlist=["KERNARG_STATE"]).KERNARG_STATE,
         "dtype": args.dtype, "data": f"synthetic crops / frame pairs and random weights; {max(1, args.rotate)} different HBM-resident "
@@ -774,9 +825,11 @@ def main():
                    "parallelism": f"dp{world}: batch sharded, one process per GPU" +
                                   (", RCCL all-gather of the output rows on a comm stream, one step behind" if world > 1 else "")},
     }
+    if dumped is not None:
+        out["outputs_dumped"] = dumped
     if rccl is not None:
         out["rccl"] = rccl
-    if args.rotate > 1 and not args.fixed_warmup:
+    if args.full and args.rotate > 1 and not args.fixed_warmup:
         # the same step replaying ONE resident batch (what rounds 1-4 reported): the A/B for the cache effect of rotation
         keep = list(step.plans)
         step.plans[:] = keep[:1]
@@ -787,7 +840,7 @@ def main():
         plan = next(iter(model._plans.values()))
         out["gflop_per_unit"] = round(plan.prog.flops / B / 1e9, 3)
         out["achieved_tflops_end_to_end"] = round(value / world * plan.prog.flops / B / 1e12, 2)
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             roof, per_layer = conv_roofline(plan.prog, args.dtype)
             if args.dtype == "fp16" and not args.batch and default_cfg:   # the committed PMC run is this exact default workload
                 roof["traffic"], roof["traffic_source"] = pmc_traffic(args.workload)
@@ -797,11 +850,11 @@ def main():
                 for label, fl, ms in per_layer:
                     print(f"  {label:28s} {fl / 1e9:9.2f} GFLOP {ms * 1e3:9.1f} us {fl / (ms * 1e-3) / 1e12 if ms > 0 else 0:8.1f} TF/s",
                           file=sys.stderr)
-        if not args.no_cpu_baseline and world == 1 and default_cfg:
+        if args.full and not args.no_cpu_baseline and world == 1 and default_cfg:
             out["cpu_baseline"] = cpu_baseline_pose() if args.workload == "pose" else cpu_baseline_flow()
 
-    # ---- the rest of BASELINE.json's metric, in the same line (default pose run only) -----------------------------------
-    extras = (not args.no_extras and args.workload == "pose" and args.dtype == "fp16" and default_cfg and not args.batch
+    # ---- the rest of BASELINE.json's metric, in the same line (--full, default pose workload only) -----------------------
+    extras = (args.full and not args.no_extras and args.workload == "pose" and args.dtype == "fp16" and default_cfg and not args.batch
               and not args.fixed_warmup)
     if extras:
         # (1) FlowNet2S fp16 on configs[3]'s pairs, every rank, same protocol; sized for >= ~1 s like the headline

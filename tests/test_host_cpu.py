@@ -505,6 +505,23 @@ def test_bench_line_summary_is_flat_and_last():
     assert line.rstrip("}").rsplit('"summary":', 1)[1].startswith("{") and len(line) < 4000
 
 
+def test_bench_dump_outputs_float32_within_budget(tmp_path):
+    """bench.py --dump-outputs: every array lands as <name>.npy in float32, whole while it fits; an array beyond the rest of the
+    byte budget becomes an evenly strided sample of its flat elements, the same on every run, and the budget holds."""
+    import bench
+    rows = torch.arange(4 * 17 * 3, dtype=torch.float16).reshape(4, 17, 3)
+    big = torch.arange(1000, dtype=torch.float32)
+    written = bench.dump_outputs({"keypoint_rows": rows, "heatmaps": big}, str(tmp_path / "a"), budget=rows.numel() * 4 + 400)
+    assert written == {"keypoint_rows": [4, 17, 3], "heatmaps": [100]}
+    got = np.load(tmp_path / "a" / "keypoint_rows.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, rows.float().numpy())
+    sample = np.load(tmp_path / "a" / "heatmaps.npy")
+    assert sample.dtype == np.float32 and np.array_equal(sample, np.arange(0, 1000, 10, dtype=np.float32))
+    bench.dump_outputs({"keypoint_rows": rows, "heatmaps": big}, str(tmp_path / "b"), budget=rows.numel() * 4 + 400)
+    assert np.array_equal(np.load(tmp_path / "b" / "heatmaps.npy"), sample)
+    assert bench.DUMP_BUDGET_BYTES + 2 * 4096 <= 64_000_000
+
+
 def test_folded_bottleneck_operands_reproduce_batchnorm():
     """hip_ops._folded_kmajor / shift_pairs (round 6: the operands of ft_bottleneck_stream_fwd with d.folded = 1), host side only: the
     fp16 weights carry conv * scale with ONE rounding from the fp32 weights, in the K-major order the pack kernel expects

@@ -298,6 +298,28 @@ def test_bench_runners_take_the_comm_stream_path_on_one_gpu(hip_lib):
     assert tuple(flow.shape) == (2, 2, 384, 512) and torch.isfinite(flow).all()
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(hip_lib, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` in a fresh process: the headline alone (nothing that
+    --full adds), ONE timed block of exactly K steps behind ms_per_step, and the last step's key-point rows and heat maps as
+    float32 .npy files, the rows' scores being the maps' maxima."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)]
+    p = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    assert line["unit"] == "crops/s" and line["dtype"] == "fp16" and line["higher_is_better"] is True
+    assert line["steps"] == 3 and line["repeats"] == 1 and abs(3 * line["ms_per_step"] / 1e3 - line["timed_region_s"]) < 2e-4
+    assert abs(line["value"] - 64 * 1e3 / line["ms_per_step"]) <= 1e-3 * line["value"]
+    assert not {"roofline", "cpu_baseline", "same_batch_replay", "flow", "fp32_parity_mode", "parity", "c3_per_gpu", "clip"} & set(line)
+    assert line["outputs_dumped"] == {"keypoint_rows": [64, 17, 3], "heatmaps": [64, 17, 64, 48]}
+    rows, hm = np.load(tmp_path / "keypoint_rows.npy"), np.load(tmp_path / "heatmaps.npy")
+    assert rows.dtype == np.float32 and hm.dtype == np.float32 and np.isfinite(hm).all()
+    assert np.array_equal(rows[..., 2], hm.reshape(64, 17, -1).max(-1))
+
+
 @pytest.mark.parametrize("pair", [(64, 128), (8, 256)], ids=["b64_then_b128", "b8_then_b256"])
 def test_two_batch_sizes_of_one_model_get_their_own_conv_direct_streams(hip_lib, monkeypatch, pair):
     """ft_conv_direct_fwd's kernel form follows the pixel count (K split 1 / 4, weight-stationary), every form orders the

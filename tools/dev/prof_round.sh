@@ -1,6 +1,7 @@
 #!/bin/bash
 # usage: prof_round.sh <round tag, e.g. r01>   -- regenerates every file under profiles/ for pose and flow:
-#   1. one plain bench run per workload that benchmarks the tiles and persists the picks (FT_TILE_CACHE)
+#   1. one bench run per workload (--full: with its roofline) that benchmarks the tiles and persists the picks (FT_TILE_CACHE);
+#      its line goes to $OUT/<tag>_<workload>_bench.json (default ./artifacts)
 #   2. rocprofv3 --kernel-trace --stats of the same command (kernels = the bench's kernels, no tuning launches)
 #   3. separate --pmc FETCH_SIZE / WRITE_SIZE passes of a short fixed-length run -> HBM bytes per conv launch
 tag=${1:-r01}
@@ -8,8 +9,10 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 export FT_TILE_CACHE=$R/gpurun_out/tile_cache_$tag.json
 rm -f $FT_TILE_CACHE
+OUT=${OUT:-artifacts}
+mkdir -p $OUT
 for w in pose flow; do
-  timeout 300 python bench.py --workload $w --no-cpu-baseline --no-extras --steps 200 > gpurun_out/${tag}_${w}_bench.json 2> gpurun_out/${tag}_${w}_bench.err
+  timeout 300 python bench.py --full --workload $w --no-cpu-baseline --no-extras --steps 200 > $OUT/${tag}_${w}_bench.json 2> $OUT/${tag}_${w}_bench.err
   # kernel-level passes run the launch list in order (FT_NO_BRANCHES=1): inside parallel graph branches two kernels share
   # the GPU and each one's traced duration stretches, which is not what roofline.avg_launch_us (per-kernel, in order) means
   export FT_NO_BRANCHES=1
@@ -29,4 +32,4 @@ timeout 300 tools/dev/prof_trace.sh ${tag}_flow_ops python tools/dev/flow_ops_pr
 timeout 600 tools/dev/prof_traffic.sh ${tag}_flow_ops python tools/dev/flow_ops_prof.py
 python tools/dev/pmc_traffic.py gpurun_out/traffic_${tag}_flow_ops 22 gpurun_out/${tag}_flow_ops_hbm_traffic_pmc.json
 python tools/dev/flow_ops_prof.py --json > gpurun_out/${tag}_flow_ops_rooflines.json 2>/dev/null
-tail -c 600 gpurun_out/${tag}_pose_bench.json
+tail -c 600 $OUT/${tag}_pose_bench.json
