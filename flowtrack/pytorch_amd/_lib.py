@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FT_LIB_PATH") or os.path.join(HERE, "libflowtrack_hip.so")  # FT_LIB_PATH: developer A/B builds
 
 FT_OK = 0
+FT_ERR_INVALID_ARG = 1  # ft_status: bad size / alignment / enum / NULL pointer
 FT_ERR_UNSUPPORTED = 2   # ft_status: valid but not implemented for this combination
 FT_F16, FT_F32 = 0, 1
 FT_ACT_NONE, FT_ACT_RELU, FT_ACT_LEAKY = 0, 1, 2
@@ -128,6 +129,9 @@ _PROTOTYPES = {
     "ft_correlation_nhwc_fwd": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 10 + [c_float, c_int, c_void_p]),
     "ft_resample2d_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ft_channelnorm_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "ft_correlation_bwd": (c_int, [c_void_p] * 5 + [c_int] * 10 + [c_void_p]),
+    "ft_resample2d_bwd": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
+    "ft_channelnorm_bwd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
     "ft_upsample_nearest4x": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "ft_flow_fusion_concat": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 8 + [c_void_p]),
     "ft_crop_affine_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float,

@@ -1,4 +1,4 @@
-// FlowNet2's three custom operators, forward only (the reference ships them as CUDA-only cffi
+// FlowNet2's three custom operators, forward and backward (the reference ships them as CUDA-only cffi
 // extensions; its CPU entry points are empty stubs, correlation_package/src/correlation.c:3-33):
 //   Correlation   correlation_package/src/correlation_cuda_kernel.cu:10-106
 //   Resample2d    resample2d_package/src/Resample2d_kernel.cu:20-66
@@ -1273,6 +1273,348 @@ __global__ __launch_bounds__(256) void upsample_nearest4x_kernel(const float* __
   }
 }
 
+// ==== backward (training) ===========================================================================================
+// ---- Correlation backward, any parameters: one thread per input element gathers every output element it fed ----------
+// The exact adjoint of correlation_nchw_kernel: in the forward, in1[ya, xa] meets in2[ya + tj*s2, xa + ti*s2] in output
+// (tc, y, x) for every kernel offset (j, i) with ya = y*s1 + max_disp + krad - pad + j (same for x).  Correctness path only.
+template <bool GRAD2>
+__global__ __launch_bounds__(256) void correlation_bwd_gather_kernel(const float* __restrict__ feat, const float* __restrict__ g,
+                                                                     float* __restrict__ grad, int C, int H, int W, int oh, int ow,
+                                                                     int pad, int ksize, int max_disp, int s1, int s2, size_t total) {
+  const int krad = (ksize - 1) / 2;
+  const int drad = max_disp / s2;
+  const int D = 2 * drad + 1;
+  const float nelems = (float)(ksize * ksize * C);
+  const size_t HW = (size_t)H * W, OHW = (size_t)oh * ow;
+  const int base = max_disp + krad - pad;
+  for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+    const int xq = (int)(idx % W);
+    size_t t = idx / W;
+    const int yq = (int)(t % H);
+    t /= H;
+    const int c = (int)(t % C);
+    const size_t n = t / C;
+    const float* pf = feat + (n * C + c) * HW;          // grad_in1: in2, grad_in2: in1
+    const float* pg = g + n * (size_t)D * D * OHW;
+    float acc = 0.f;
+    for (int tc = 0; tc < D * D; ++tc) {
+      const int ddy = (tc / D - drad) * s2, ddx = (tc % D - drad) * s2;
+      const int ya = GRAD2 ? yq - ddy : yq, xa = GRAD2 ? xq - ddx : xq;   // in1 position
+      const int yo = GRAD2 ? ya : yq + ddy, xo = GRAD2 ? xa : xq + ddx;   // the other operand
+      if ((unsigned)yo >= (unsigned)H || (unsigned)xo >= (unsigned)W) continue;   // zero padding
+      if (GRAD2 && ((unsigned)ya >= (unsigned)H || (unsigned)xa >= (unsigned)W)) continue;
+      const float v = pf[(size_t)yo * W + xo];
+      for (int j = -krad; j <= krad; ++j) {
+        const int yy = ya - j - base;
+        if (yy < 0 || yy % s1) continue;
+        const int y = yy / s1;
+        if (y >= oh) continue;
+        for (int i = -krad; i <= krad; ++i) {
+          const int xx = xa - i - base;
+          if (xx < 0 || xx % s1) continue;
+          const int x = xx / s1;
+          if (x >= ow) continue;
+          acc += pg[(size_t)tc * OHW + (size_t)y * ow + x] * v;
+        }
+      }
+    }
+    grad[idx] = acc / nelems;
+  }
+}
+
+// ---- Correlation backward, kernel_size 1 / stride1 1 (every FlowNet in the reference) ----------------------------------
+// With off = max_disp - pad and displacements d_t = s2 * (dy - drad, dx - drad):
+//   grad_in1[c, p] = 1/C sum_t g[t, p - off] * in2[c, p + d_t]        grad_in2[c, q] = 1/C sum_t g[t, q - d_t - off] * in1[c, q - d_t]
+// Workgroup = (image, row, 32*s2 pixels, 128/s2 channels), 128 threads.  Pixels are split by their residue mod s2: a thread owns
+// four consecutive pixels of one residue class (stride s2 in x) and 8 channels, so for one displaced row dy the D horizontal
+// displacements slide ONE class position at a time over the feature window: the D + 3 window values of a channel are read once
+// from LDS and each feeds up to four FMAs with g values held in registers (D x 4 per thread and dy, reused by all 8 channels).
+// Per dy the feature row window (TX + 2*drad*s2 pixels of every channel of the chunk) and the g slab of the D displacements of
+// that dy are staged in LDS.  Fixed summation order (dy, channel chunk, class position): bit-reproducible.
+constexpr int kCbwCh = 8;                                   // channels per thread: LDS <= 45 KiB per block for every stride2 (4 blocks per CU at stride2 2)
+template <int DRAD, bool GRAD2>
+__global__ __launch_bounds__(128, 2) void correlation_bwd_k1_kernel(const float* __restrict__ feat, const float* __restrict__ g,
+                                                                 float* __restrict__ grad, int C, int H, int W, int oh, int ow,
+                                                                 int off, int s2, int tiles_x, int cchunks, float inv_c) {
+  constexpr int D = 2 * DRAD + 1;
+  extern __shared__ float cb_smem[];
+  const int TX = 32 * s2, R = DRAD * s2;
+  const int PR = 32 + 2 * DRAD + 1;                         // class row pitch (odd: lanes of other residues / channels hit other banks)
+  const int WWp = s2 * PR;                                  // channel pitch of the window
+  const int WW = TX + 2 * R;                                // window pixels
+  const int npg = 8 * s2, ncg = 128 / npg;
+  const int CB = kCbwCh * ncg;
+  float* win = cb_smem;                                     // [CB][s2][PR]
+  float* gs = cb_smem + CB * WWp;                           // [D][s2][PR]
+  int bid = blockIdx.x;
+  const int tx = bid % tiles_x; bid /= tiles_x;
+  const int cc = bid % cchunks; bid /= cchunks;
+  const int row = bid % H;
+  const size_t n = (size_t)(bid / H);
+  const int x0 = tx * TX, c0 = cc * CB;
+  const int tid = threadIdx.x;
+  const int pg = tid % npg, cg = tid / npg;
+  const int rr = pg % s2, u0 = (pg / s2) * 4;
+  const size_t HW = (size_t)H * W, OHW = (size_t)oh * ow;
+  const float* fb = feat + n * C * HW;
+  const float* gb = g + n * (size_t)D * D * OHW;
+  float acc[kCbwCh][4];
+#pragma unroll
+  for (int cl = 0; cl < kCbwCh; ++cl)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[cl][k] = 0.f;
+  const int gw = GRAD2 ? WW : TX, gx0 = (GRAD2 ? x0 - R : x0) - off;
+#pragma unroll 1
+  for (int dy = 0; dy < D; ++dy) {
+    const int ddy = (dy - DRAD) * s2;
+    const int frow = GRAD2 ? row - ddy : row + ddy;
+    const int grow = (GRAD2 ? row - ddy : row) - off;
+    __syncthreads();                                        // the previous step's readers are done
+    // staging: a thread keeps its window column(s) i = tid + 128 * r for every row (no per-element division)
+    const bool frow_ok = (unsigned)frow < (unsigned)H;
+    const bool grow_ok = (unsigned)grow < (unsigned)oh;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int i = tid + 128 * r;
+      const int lo = (i % s2) * PR + i / s2;
+      const int x = x0 - R + i, gx = gx0 + i;
+      // all loads of a 32-row chunk are issued before the first LDS store (one memory round trip per chunk, not per row)
+      if (i < WW) {
+        const bool xok = frow_ok && (unsigned)x < (unsigned)W;
+        const float* src = fb + (size_t)c0 * HW + (size_t)frow * W + x;
+        for (int cl0 = 0; cl0 < CB; cl0 += 32) {
+          float t[32];
+#pragma unroll
+          for (int j = 0; j < 32; ++j) t[j] = (xok && c0 + cl0 + j < C) ? src[(size_t)(cl0 + j) * HW] : 0.f;
+#pragma unroll
+          for (int j = 0; j < 32; ++j) win[(cl0 + j) * WWp + lo] = t[j];
+        }
+      }
+      if (i < gw) {
+        const bool gok = grow_ok && (unsigned)gx < (unsigned)ow;
+        const float* src = gb + (size_t)dy * D * OHW + (size_t)grow * ow + gx;
+        float t[D];
+#pragma unroll
+        for (int dxi = 0; dxi < D; ++dxi) t[dxi] = gok ? src[(size_t)dxi * OHW] : 0.f;
+#pragma unroll
+        for (int dxi = 0; dxi < D; ++dxi) gs[dxi * WWp + lo] = t[dxi];
+      }
+    }
+    __syncthreads();
+    // gr[e][k]: the g value that meets window class position u0 + k + e (grad_in1: e = dx; grad_in2: e = D - 1 - dx)
+    float gr[D][4];
+#pragma unroll
+    for (int e = 0; e < D; ++e)
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        gr[e][k] = GRAD2 ? gs[(D - 1 - e) * WWp + rr * PR + u0 + k + e] : gs[e * WWp + rr * PR + u0 + k];
+#pragma unroll
+    for (int cl = 0; cl < kCbwCh; ++cl) {
+      const float* wp = win + (cl * ncg + cg) * WWp + rr * PR + u0;
+#pragma unroll
+      for (int j = 0; j < D + 3; ++j) {
+        const float v = wp[j];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int e = j - k;
+          if (e >= 0 && e < D) acc[cl][k] = fmaf(gr[e][k], v, acc[cl][k]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int cl = 0; cl < kCbwCh; ++cl) {
+    const int c = c0 + cl * ncg + cg;
+    if (c >= C) continue;
+    float* o = grad + (n * C + c) * HW + (size_t)row * W;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int x = x0 + rr + s2 * (u0 + k);
+      if (x < W) o[x] = acc[cl][k] * inv_c;
+    }
+  }
+}
+
+// ---- Resample2d backward: grad_flow (a gather, Resample2d_kernel.cu:118-186, same operation order) ------------------------
+__global__ __launch_bounds__(256) void resample2d_bwd_flow_kernel(const float* __restrict__ in1, const float* __restrict__ flow,
+                                                                  const float* __restrict__ gout, float* __restrict__ gflow,
+                                                                  int C, int H, int W, size_t total) {
+  const size_t HW = (size_t)H * W;
+  for (size_t i = xcd_contiguous_block() * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / HW, pix = i - b * HW;
+    const int y = (int)(pix / W), x = (int)(pix - (size_t)y * W);
+    const float xf = (float)x + flow[(b * 2 + 0) * HW + pix], yf = (float)y + flow[(b * 2 + 1) * HW + pix];
+    const float fx = floorf(xf), fy = floorf(yf);
+    const int xL = (int)fminf(fmaxf(fx, 0.f), (float)(W - 1));
+    const int xR = (int)fminf(fmaxf(fx + 1.f, 0.f), (float)(W - 1));
+    const int yT = (int)fminf(fmaxf(fy, 0.f), (float)(H - 1));
+    const int yB = (int)fminf(fmaxf(fy + 1.f, 0.f), (float)(H - 1));
+    const float gx = 1.f - (yf - fy), gy = 1.f - (xf - fx);   // the reference's gamma of channel 0 (x) / 1 (y)
+    float ox = 0.f, oy = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float* p = in1 + (b * C + c) * HW;
+      const float go = gout[(b * C + c) * HW + pix];
+      const float tL = p[(size_t)yT * W + xL], tR = p[(size_t)yT * W + xR];
+      const float bL = p[(size_t)yB * W + xL], bR = p[(size_t)yB * W + xR];
+      ox += gx * go * tR;
+      ox -= gx * go * tL;
+      ox += (1.f - gx) * go * bR;
+      ox -= (1.f - gx) * go * bL;
+      oy += gy * go * bL;
+      oy -= gy * go * tL;
+      oy += (1.f - gy) * go * bR;
+      oy -= (1.f - gy) * go * tR;
+    }
+    gflow[(b * 2 + 0) * HW + pix] = ox;
+    gflow[(b * 2 + 1) * HW + pix] = oy;
+  }
+}
+
+// ---- Resample2d backward: grad_in1 (a scatter) through an LDS window -------------------------------------------------------
+// The forward's tiling (16 x 64 output pixels, 4 per thread) and bounding box of the taps.  The window is the box, or, when the
+// box exceeds the budget, a kRsbClipPitch-wide region centred on the tile (as resample2d_window_kernel).  Per channel: zero the
+// window, every pixel whose four taps lie inside adds them with ds_add_f32, the others with global float atomics; then the
+// window's nonzero entries leave as global atomics, 64 lanes along a row (256 contiguous bytes per wave instruction).  Windows
+// of neighbouring tiles overlap: the flush must add, and the sum's order (hence its last bits) is not fixed.  grad_in1 is
+// zero-filled by the host entry point before this kernel.
+constexpr int kRsbBudget = 3072, kRsbClipPitch = 96;        // window floats (one plane at a time: 12 KiB of LDS)
+__global__ __launch_bounds__(256) void resample2d_bwd_in1_kernel(const float* __restrict__ flow, const float* __restrict__ gout,
+                                                                 float* __restrict__ gin, int C, int H, int W, int tiles_x,
+                                                                 int tiles_y) {
+  __shared__ float win[kRsbBudget];
+  __shared__ int s_box[4][4];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tiles = tiles_x * tiles_y;
+  const int b = blockIdx.x / tiles, trem = blockIdx.x - b * tiles;
+  const int ty0 = (trem / tiles_x) * kRsTH, tx0 = (trem % tiles_x) * kRsTW;
+  const size_t HW = (size_t)H * W;
+  const int x = tx0 + lane;
+  float w00[kRsPPT], w01[kRsPPT], w10[kRsPPT], w11[kRsPPT];
+  int xL[kRsPPT], xR[kRsPPT], yT[kRsPPT], yB[kRsPPT];
+  int bx0 = 0x7fffffff, bx1 = -1, by0 = 0x7fffffff, by1 = -1;
+#pragma unroll
+  for (int k = 0; k < kRsPPT; ++k) {
+    const int y = ty0 + k * 4 + wave;
+    const bool live = x < W && y < H;
+    float dx = 0.f, dy = 0.f;
+    if (live) {
+      const size_t pix = (size_t)y * W + x;
+      dx = flow[((size_t)b * 2 + 0) * HW + pix];
+      dy = flow[((size_t)b * 2 + 1) * HW + pix];
+    }
+    const float xf = (float)x + dx, yf = (float)y + dy;
+    const float fx = floorf(xf), fy = floorf(yf);
+    const float alpha = xf - fx, beta = yf - fy;
+    xL[k] = (int)fminf(fmaxf(fx, 0.f), (float)(W - 1));
+    xR[k] = (int)fminf(fmaxf(fx + 1.f, 0.f), (float)(W - 1));
+    yT[k] = (int)fminf(fmaxf(fy, 0.f), (float)(H - 1));
+    yB[k] = (int)fminf(fmaxf(fy + 1.f, 0.f), (float)(H - 1));
+    w00[k] = (1.f - alpha) * (1.f - beta); w01[k] = alpha * (1.f - beta);
+    w10[k] = (1.f - alpha) * beta;         w11[k] = alpha * beta;
+    if (live) {
+      bx0 = min(bx0, xL[k]); bx1 = max(bx1, xR[k]);
+      by0 = min(by0, yT[k]); by1 = max(by1, yB[k]);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    bx0 = min(bx0, __shfl_xor(bx0, o)); bx1 = max(bx1, __shfl_xor(bx1, o));
+    by0 = min(by0, __shfl_xor(by0, o)); by1 = max(by1, __shfl_xor(by1, o));
+  }
+  if (lane == 0) { s_box[wave][0] = bx0; s_box[wave][1] = bx1; s_box[wave][2] = by0; s_box[wave][3] = by1; }
+  __syncthreads();
+  bx0 = min(min(s_box[0][0], s_box[1][0]), min(s_box[2][0], s_box[3][0]));
+  bx1 = max(max(s_box[0][1], s_box[1][1]), max(s_box[2][1], s_box[3][1]));
+  by0 = min(min(s_box[0][2], s_box[1][2]), min(s_box[2][2], s_box[3][2]));
+  by1 = max(max(s_box[0][3], s_box[1][3]), max(s_box[2][3], s_box[3][3]));
+  if (bx1 < 0) return;                                     // (no live pixel: cannot happen for ceil-divided grids)
+  int wx0 = bx0, wx1 = bx1, wy0 = by0, wy1 = by1;
+  int ww = wx1 - wx0 + 1, wh = wy1 - wy0 + 1;
+  if (ww * wh > kRsbBudget) {                              // clip around the tile
+    const int cp = ww < kRsbClipPitch ? ww : kRsbClipPitch;
+    const int rows = kRsbBudget / cp;
+    int cx0 = tx0 - ((cp - (kRsTW + 1)) >> 1), cy0 = ty0 - ((rows - (kRsTH + 1)) >> 1);
+    cx0 = max(min(cx0, wx1 - cp + 1), wx0);
+    cy0 = max(min(cy0, wy1 - rows + 1), wy0);
+    wx0 = cx0; wx1 = min(wx1, cx0 + cp - 1);
+    wy0 = cy0; wy1 = min(wy1, cy0 + rows - 1);
+    ww = wx1 - wx0 + 1; wh = wy1 - wy0 + 1;
+  }
+  bool inw[kRsPPT];
+#pragma unroll
+  for (int k = 0; k < kRsPPT; ++k) inw[k] = xL[k] >= wx0 && xR[k] <= wx1 && yT[k] >= wy0 && yB[k] <= wy1;
+  const int wn = ww * wh;
+#pragma unroll 1
+  for (int c = 0; c < C; ++c) {
+    for (int i = tid; i < wn; i += 256) win[i] = 0.f;
+    __syncthreads();
+    const size_t plane = ((size_t)b * C + c) * HW;
+#pragma unroll
+    for (int k = 0; k < kRsPPT; ++k) {
+      const int y = ty0 + k * 4 + wave;
+      if (x < W && y < H) {
+        const float go = gout[plane + (size_t)y * W + x];
+        if (inw[k]) {
+          const int oT = (yT[k] - wy0) * ww, oB = (yB[k] - wy0) * ww, oL = xL[k] - wx0, oR = xR[k] - wx0;
+          atomicAdd(&win[oT + oL], w00[k] * go);
+          atomicAdd(&win[oT + oR], w01[k] * go);
+          atomicAdd(&win[oB + oL], w10[k] * go);
+          atomicAdd(&win[oB + oR], w11[k] * go);
+        } else {
+          float* p = gin + plane;
+          unsafeAtomicAdd(p + (size_t)yT[k] * W + xL[k], w00[k] * go);
+          unsafeAtomicAdd(p + (size_t)yT[k] * W + xR[k], w01[k] * go);
+          unsafeAtomicAdd(p + (size_t)yB[k] * W + xL[k], w10[k] * go);
+          unsafeAtomicAdd(p + (size_t)yB[k] * W + xR[k], w11[k] * go);
+        }
+      }
+    }
+    __syncthreads();
+    for (int r = wave; r < wh; r += 4) {
+      float* dst = gin + plane + (size_t)(wy0 + r) * W + wx0;
+      for (int q = lane; q < ww; q += 64) {
+        const float v = win[r * ww + q];
+        if (v != 0.f) unsafeAtomicAdd(dst + q, v);
+      }
+    }
+    __syncthreads();                                       // the flush has read the window before the next channel zeroes it
+  }
+}
+
+// ---- ChannelNorm backward: grad_in1 = grad_out * in1 / (out + 1e-9), ChannelNorm_kernel.cu:54-81 ----------------------------
+// The reference's 1e-9 is a double literal: the quotient is taken in double and rounded once, as there.
+__device__ __forceinline__ float cn_bwd(float go, float x, float o) { return (float)((double)(go * x) / ((double)o + 1e-9)); }
+__global__ __launch_bounds__(256) void channelnorm_bwd_kernel(const float* __restrict__ in, const float* __restrict__ out,
+                                                              const float* __restrict__ gout, float* __restrict__ gin, int C,
+                                                              size_t HW, size_t total) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / HW, pix = i - b * HW;
+    const float go = gout[i], o = out[i];
+    for (int c = 0; c < C; ++c) {
+      const size_t e = (b * C + c) * HW + pix;
+      gin[e] = cn_bwd(go, in[e], o);
+    }
+  }
+}
+// four pixels per thread, 16-byte loads and stores: HW % 4 == 0 and 16-byte aligned planes
+__global__ __launch_bounds__(256) void channelnorm_bwd_vec4_kernel(const float4_t* __restrict__ in, const float4_t* __restrict__ out,
+                                                                   const float4_t* __restrict__ gout, float4_t* __restrict__ gin,
+                                                                   int C, size_t HW4, size_t total4) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total4) return;
+  const size_t b = i / HW4, pix = i - b * HW4;
+  const float4_t go = gout[i], o = out[i];
+  for (int c = 0; c < C; ++c) {
+    const size_t e = (b * C + c) * HW4 + pix;
+    const float4_t x = in[e];
+    float4_t r;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] = cn_bwd(go[k], x[k], o[k]);
+    gin[e] = r;
+  }
+}
+
 static inline int grid_for(size_t total) {
   size_t g = (total + 255) / 256;
   return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
@@ -1535,5 +1877,106 @@ extern "C" int ft_upsample_nearest4x(const float* x, float* y, int N, int C, int
   const size_t total = (size_t)N * C * 16 * h * w;
   hipLaunchKernelGGL(upsample_nearest4x_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), x, y, h, w, total, mul);
   FT_LAUNCH_CHECK("upsample_nearest4x_kernel");
+  return FT_OK;
+}
+
+// ==== backward entry points ===========================================================================================
+template <int DRAD>
+static int launch_correlation_bwd_k1(const float* feat, const float* g, float* grad, bool grad2, int B, int C, int H, int W, int oh,
+                                     int ow, int off, int s2, hipStream_t stream) {
+  const int TX = 32 * s2, ncg = 128 / (8 * s2), CB = kCbwCh * ncg;
+  const int tiles_x = ceil_div(W, TX), cchunks = ceil_div(C, CB);
+  const size_t lds = (size_t)(CB + 2 * DRAD + 1) * s2 * (32 + 2 * DRAD + 1) * sizeof(float);
+  const long long nblk = (long long)B * H * cchunks * tiles_x;
+  if (nblk > 0x7fffffffLL) return FT_ERR_UNSUPPORTED;
+  auto k = grad2 ? correlation_bwd_k1_kernel<DRAD, true> : correlation_bwd_k1_kernel<DRAD, false>;
+  if (lds > 64 * 1024) return FT_ERR_UNSUPPORTED;                 // (cannot happen: <= 45 KiB for stride2 <= 4, drad <= 10)
+  hipLaunchKernelGGL(k, dim3((unsigned)nblk), dim3(128), lds, stream, feat, g, grad, C, H, W, oh, ow, off, s2, tiles_x, cchunks,
+                     1.f / (float)C);
+  FT_LAUNCH_CHECK("correlation_bwd_k1_kernel");
+  return FT_OK;
+}
+
+extern "C" int ft_correlation_bwd(const float* in1, const float* in2, const float* grad_out, float* grad_in1, float* grad_in2,
+                                  int B, int C, int H, int W, int pad_size, int kernel_size, int max_displacement, int stride1,
+                                  int stride2, int corr_type_multiply, ft_stream_t stream) {
+  if (!in1 || !in2 || !grad_out || (!grad_in1 && !grad_in2) || B <= 0) return FT_ERR_INVALID_ARG;
+  if (corr_type_multiply != 1) return FT_ERR_UNSUPPORTED;
+  int oc, oh, ow;
+  int st = ft_correlation_out_shape(C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &oc, &oh, &ow);
+  if (st != FT_OK) return st;
+  const hipStream_t s = as_stream(stream);
+  const int drad = max_displacement / stride2;
+  // fast path: kernel 1, stride1 1, 1 <= drad <= 10, stride2 in {1, 2, 4} (the tile = 32 pixels of each residue mod stride2)
+  if (kernel_size == 1 && stride1 == 1 && drad >= 1 && drad <= 10 && (stride2 == 1 || stride2 == 2 || stride2 == 4)) {
+    const int off = max_displacement - pad_size;
+    for (int which = 0; which < 2; ++which) {
+      float* grad = which ? grad_in2 : grad_in1;
+      if (!grad) continue;
+      const float* feat = which ? in1 : in2;
+#define FT_CB_CASE(R) \
+  case R: st = launch_correlation_bwd_k1<R>(feat, grad_out, grad, which == 1, B, C, H, W, oh, ow, off, stride2, s); break;
+      switch (drad) {
+        FT_CB_CASE(1) FT_CB_CASE(2) FT_CB_CASE(3) FT_CB_CASE(4) FT_CB_CASE(5)
+        FT_CB_CASE(6) FT_CB_CASE(7) FT_CB_CASE(8) FT_CB_CASE(9) FT_CB_CASE(10)
+      }
+#undef FT_CB_CASE
+      if (st != FT_OK) return st;
+    }
+    return FT_OK;
+  }
+  const size_t total = (size_t)B * C * H * W;
+  if (grad_in1) {
+    hipLaunchKernelGGL(correlation_bwd_gather_kernel<false>, dim3(grid_for(total)), dim3(256), 0, s, in2, grad_out, grad_in1, C, H,
+                       W, oh, ow, pad_size, kernel_size, max_displacement, stride1, stride2, total);
+    FT_LAUNCH_CHECK("correlation_bwd_gather_kernel");
+  }
+  if (grad_in2) {
+    hipLaunchKernelGGL(correlation_bwd_gather_kernel<true>, dim3(grid_for(total)), dim3(256), 0, s, in1, grad_out, grad_in2, C, H,
+                       W, oh, ow, pad_size, kernel_size, max_displacement, stride1, stride2, total);
+    FT_LAUNCH_CHECK("correlation_bwd_gather_kernel");
+  }
+  return FT_OK;
+}
+
+extern "C" int ft_resample2d_bwd(const float* in1, const float* flow, const float* grad_out, float* grad_in1, float* grad_flow,
+                                 int B, int C, int H, int W, ft_stream_t stream) {
+  if (!in1 || !flow || !grad_out || (!grad_in1 && !grad_flow) || B <= 0 || C <= 0 || H <= 0 || W <= 0) return FT_ERR_INVALID_ARG;
+  const hipStream_t s = as_stream(stream);
+  const size_t total = (size_t)B * H * W;
+  if (grad_flow) {
+    hipLaunchKernelGGL(resample2d_bwd_flow_kernel, dim3(grid_for(total)), dim3(256), 0, s, in1, flow, grad_out, grad_flow, C, H, W,
+                       total);
+    FT_LAUNCH_CHECK("resample2d_bwd_flow_kernel");
+  }
+  if (grad_in1) {
+    const int tiles_x = ceil_div(W, kRsTW), tiles_y = ceil_div(H, kRsTH);
+    const long long nblk = (long long)B * tiles_x * tiles_y;
+    if (nblk > 0x7fffffffLL) return FT_ERR_UNSUPPORTED;
+    FT_HIP_CHECK(hipMemsetAsync(grad_in1, 0, (size_t)B * C * H * W * sizeof(float), s));
+    hipLaunchKernelGGL(resample2d_bwd_in1_kernel, dim3((unsigned)nblk), dim3(256), 0, s, flow, grad_out, grad_in1, C, H, W, tiles_x,
+                       tiles_y);
+    FT_LAUNCH_CHECK("resample2d_bwd_in1_kernel");
+  }
+  return FT_OK;
+}
+
+extern "C" int ft_channelnorm_bwd(const float* in1, const float* out, const float* grad_out, float* grad_in1, int B, int C, int H,
+                                  int W, ft_stream_t stream) {
+  if (!in1 || !out || !grad_out || !grad_in1 || B <= 0 || C <= 0 || H <= 0 || W <= 0) return FT_ERR_INVALID_ARG;
+  const size_t HW = (size_t)H * W, total = (size_t)B * HW;
+  const bool aligned = ((reinterpret_cast<uintptr_t>(in1) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(grad_out) |
+                         reinterpret_cast<uintptr_t>(grad_in1)) & 15) == 0;
+  if (HW % 4 == 0 && aligned && total / 4 / 256 < (1u << 30)) {
+    const size_t total4 = total / 4;
+    hipLaunchKernelGGL(channelnorm_bwd_vec4_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, as_stream(stream),
+                       reinterpret_cast<const float4_t*>(in1), reinterpret_cast<const float4_t*>(out),
+                       reinterpret_cast<const float4_t*>(grad_out), reinterpret_cast<float4_t*>(grad_in1), C, HW / 4, total4);
+    FT_LAUNCH_CHECK("channelnorm_bwd_vec4_kernel");
+    return FT_OK;
+  }
+  hipLaunchKernelGGL(channelnorm_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), in1, out, grad_out, grad_in1, C,
+                     HW, total);
+  FT_LAUNCH_CHECK("channelnorm_bwd_kernel");
   return FT_OK;
 }

@@ -444,6 +444,37 @@ int ft_resample2d_fwd(const float* in1, const float* flow, float* out, int B,
 int ft_channelnorm_fwd(const float* in1, float* out, int B, int C, int H, int W,
                        ft_stream_t stream);
 
+/* ---- F4-F6 backward (training: flownet/ops.py autograd Functions) ----------
+ * Replace Correlation_backward_cuda, Resample2d_cuda_backward and
+ * ChannelNorm_cuda_backward.  Contiguous NCHW fp32, same sizes as the forward
+ * entry points (grad_out has the forward output's shape).  Either gradient
+ * pointer may be NULL (not computed), not both.  Every requested gradient is
+ * fully written: the calls zero-fill what they need themselves, so the caller
+ * passes uninitialised buffers.  No host synchronisation, no allocation: the
+ * calls can be captured into a graph.
+ *   ft_correlation_bwd: the exact adjoint of ft_correlation_fwd (equals the
+ *     reference's kernels for kernel_size 1 / stride1 1; see INTEGRATION.md §1
+ *     for kernel_size > 1 and stride1 > 1).  Bit-reproducible.  Fast path:
+ *     kernel_size 1, stride1 1, stride2 in {1, 2, 4} and
+ *     1 <= max_displacement / stride2 <= 10 (every FlowNet of the reference);
+ *     any other valid parameters take a slow gather kernel (correctness only).
+ *   ft_resample2d_bwd: grad_in1 = adjoint of the forward, summed with float
+ *     atomics (may differ in the last bits between runs, as the reference's);
+ *     grad_flow = Resample2d_kernel.cu:118-186, bit-reproducible.
+ *   ft_channelnorm_bwd: grad_in1 = grad_out * in1 / (out + 1e-9)
+ *     (ChannelNorm_kernel.cu:54-81), out = the forward's output. */
+int ft_correlation_bwd(const float* in1, const float* in2, const float* grad_out,
+                       float* grad_in1, float* grad_in2, int B, int C, int H, int W,
+                       int pad_size, int kernel_size, int max_displacement,
+                       int stride1, int stride2, int corr_type_multiply,
+                       ft_stream_t stream);
+int ft_resample2d_bwd(const float* in1, const float* flow, const float* grad_out,
+                      float* grad_in1, float* grad_flow, int B, int C, int H, int W,
+                      ft_stream_t stream);
+int ft_channelnorm_bwd(const float* in1, const float* out, const float* grad_out,
+                       float* grad_in1, int B, int C, int H, int W,
+                       ft_stream_t stream);
+
 /* ---- F5+F6 fused stage between stacked FlowNets (models.py:396-403) -------
  * From x6 = NHWC `dtype` [B,H,x_wpitch,8] (normalised img0|img1, pixel x in column x_lpad + x) and
  * flow NCHW fp32 [B,2,H,W] (already multiplied by div_flow) builds the 12-channel input of the
