@@ -70,19 +70,13 @@ __device__ __forceinline__ void unroll_for(F&& f) {
 // takes conv_direct's ring reads from 27-44 % to 0), but a third of the LDS time here is STILL conflicts.  Not tracked down;
 // candidates are the 8-byte accesses (T1 / T2 / staging epilogue writes, the residual pick-up), where the two lanes of a pixel
 // write the halves of one 16-byte chunk.  60.4 -> 57.3 us per block came from the part that is fixed.
-#ifndef FT_BNK_KEY_SHIFT
-#define FT_BNK_KEY_SHIFT 1
-#endif
-#define BNK_KEY(r) (((r) >> FT_BNK_KEY_SHIFT) & 7)
+#define BNK_KEY(r) (((r) >> 1) & 7)
 // T1 (the 18- or 10-pixel-wide halo patch conv2's taps read at a row / column shift): ds_read_b128 serves lanes {0-3, 12-15,
 // 20-27} together = with 16-pixel tile rows: columns 0-3 and 12-15 of one patch row and 4-11 of the next.  Keyed by the linear
 // index (r >> 1 = 9 * row + column / 2) columns 12-13 of a row and 10-11 of the next share key AND 128-byte half: a 2-way
 // conflict in every such read (+1 LDS cycle on 4: the 30-33 % conflict cycles the PMC kept showing).  Keyed by the COLUMN pair
 // alone the sixteen lanes cover the sixteen slots.  (8-pixel tile rows: four rows x four columns per group; the old key stays.)
-#ifndef FT_BNK_T1_COLKEY
-#define FT_BNK_T1_COLKEY 1
-#endif
-template <int TW> __device__ __forceinline__ int bnk_t1_key(int r, int pc) { return (FT_BNK_T1_COLKEY && TW == 16) ? ((pc >> 1) & 7) : BNK_KEY(r); }
+template <int TW> __device__ __forceinline__ int bnk_t1_key(int r, int pc) { return TW == 16 ? ((pc >> 1) & 7) : BNK_KEY(r); }
 
 constexpr int kC = 256, kP = 64;                 // block width / planes this kernel is written for
 // LDS map (bytes).  Phase 1: two 32-KiB stages (64-channel x chunk 24 KiB + W1 K-slice 8 KiB) at 0 .. 64 Ki.
@@ -587,7 +581,7 @@ extern "C" int ft_bottleneck_fwd(const ft_bottleneck_desc* d, const void* x, con
   p.tx = ceil_div(d->W, tw);
   p.ty = ceil_div(d->H, th);
   p.total = d->N * p.tx * p.ty;
-  static const int dbg = getenv("FT_BNK_DBG") ? atoi(getenv("FT_BNK_DBG")) : 0;
+  static const int dbg = dev_env_int("FT_BNK_DBG", 0);
   p.dbg = dbg;
   hipStream_t s = as_stream(stream);
   if (d->head_only) return tall ? launch<8, 1, false>(p, s) : launch<16, 1, false>(p, s);

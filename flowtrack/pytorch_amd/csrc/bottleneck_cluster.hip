@@ -65,9 +65,6 @@ __device__ __forceinline__ void bnc_unroll(F&& f) {
 
 #define BNC_BARRIER() asm volatile("s_barrier" ::: "memory")
 #define BNC_XKEY(hp) (((hp) >> 1) & 7)      // x-chunk rows of 128 bytes: two rows share a 256-byte bank row
-#ifndef FT_BNC_PIN
-#define FT_BNC_PIN 1    // pinned issue order in phase 1 (as bottleneck_stream_direct_kernel)
-#endif
 #ifndef FT_BNC_SLOTS1
 #define FT_BNC_SLOTS1 4   // weight-step register slots of phase 1 (8 KiB per wave and step)
 #endif
@@ -521,8 +518,6 @@ struct BncPlan {
 static int bnc_plan(const ft_bottleneck_desc* d, BncPlan* out) {
   if (!d) return FT_ERR_INVALID_ARG;
   if (d->N <= 0 || d->H <= 0 || d->W <= 0) return FT_ERR_INVALID_ARG;
-  static const bool off = getenv("FT_BNC") && atoi(getenv("FT_BNC")) == 0;
-  if (off) return FT_ERR_UNSUPPORTED;
   if (d->dtype != FT_F16 || d->projection || d->head_only || d->P != kP || d->C != 4 * kP || d->stride > 1) return FT_ERR_UNSUPPORTED;
   if (d->x_coff < 0 || d->y_coff < 0 || d->x_coff % 8 || d->y_coff % 8 || d->x_cstride % 8 || d->y_cstride % 8) return FT_ERR_UNSUPPORTED;
   if (d->x_cstride < d->x_coff + d->C || d->y_cstride < d->y_coff + d->C) return FT_ERR_INVALID_ARG;
@@ -581,7 +576,7 @@ extern "C" int ft_bottleneck_cluster_fwd(const ft_bottleneck_desc* d, const void
   p.y_bytes = (unsigned)((size_t)d->N * p.HW * d->y_cstride * 2);
   p.ws_bytes = (unsigned)((kG3 + 4 * kKC) * kWSTEP);
   p.tx_bytes = (unsigned)pl.tx_bytes;
-  static const int dbg = getenv("FT_BNC_DBG") ? atoi(getenv("FT_BNC_DBG")) : 0;
+  static const int dbg = dev_env_int("FT_BNC_DBG", 0);
   p.dbg = dbg;
   hipStream_t s = as_stream(stream);
   auto k = bottleneck_cluster_kernel;

@@ -442,7 +442,7 @@ static int bnr_plan(const ft_bottleneck_desc* d, BnrPlan* out) {
   if (!d || !out) return FT_ERR_INVALID_ARG;
   // FT_BNK_RSTAT (read per call: dev / tests): 0 = off, 1 = where the cost rule below takes it (default), 2 = wherever the shape fits;
   // FT_BNR_SR = rows per strip
-  const int mode = getenv("FT_BNK_RSTAT") ? atoi(getenv("FT_BNK_RSTAT")) : 1;
+  const int mode = dev_env_int("FT_BNK_RSTAT", 1);
   if (mode <= 0) return FT_ERR_UNSUPPORTED;
   if (d->N <= 0 || d->H <= 0 || d->W <= 0) return FT_ERR_INVALID_ARG;
   if (d->dtype != FT_F16 || d->C != 256 || d->P != 64 || d->stride > 1 || d->head_only || d->projection) return FT_ERR_UNSUPPORTED;
@@ -466,7 +466,7 @@ static int bnr_plan(const ft_bottleneck_desc* d, BnrPlan* out) {
   int S = ceil_div(ncu, d->N);
   if (S > d->H) S = d->H;
   int SR = ceil_div(d->H, S);
-  const int force_sr = getenv("FT_BNR_SR") ? atoi(getenv("FT_BNR_SR")) : 0;
+  const int force_sr = dev_env_int("FT_BNR_SR", 0);
   if (force_sr > 0) SR = force_sr < d->H ? force_sr : d->H;
   S = ceil_div(d->H, SR);
   if (mode < 2 && SR * d->W < 512) return FT_ERR_UNSUPPORTED;   // fewer than eight steps per strip: the patch kernel is the better form
@@ -501,7 +501,7 @@ extern "C" int ft_bottleneck_rstat_fwd(const ft_bottleneck_desc* d, const void* 
   p.x_bytes = (unsigned)((size_t)d->N * d->H * d->W * d->x_cstride * 2);
   p.y_bytes = (unsigned)((size_t)d->N * d->H * d->W * d->y_cstride * 2);
   p.total = d->N * pl.S;
-  static const int dbg = getenv("FT_BNR_DBG") ? atoi(getenv("FT_BNR_DBG")) : 0;
+  static const int dbg = dev_env_int("FT_BNR_DBG", 0);
   p.dbg = dbg;
   FT_RAISE_LDS(bottleneck_rstat_kernel, kLds);
   hipLaunchKernelGGL(bottleneck_rstat_kernel, dim3(p.total), dim3(512), kLds, as_stream(stream), p);

@@ -58,41 +58,10 @@ __device__ __forceinline__ void bns_unroll(F&& f) {
 
 #define BNS_BARRIER() asm volatile("s_barrier" ::: "memory")
 // XOR key of the x-chunk buffers' 128-byte rows: two rows share a 256-byte bank row (see bottleneck.hip: BNK_KEY)
-#ifndef FT_BNS_XKEY_SHIFT
-#define FT_BNS_XKEY_SHIFT 1
-#endif
-#define BNS_XKEY(hp) (((hp) >> FT_BNS_XKEY_SHIFT) & 7)
-#ifndef FT_BNS_STG
-#define FT_BNS_STG 1    // dev A/B: 0 = phase 3 of the direct kernel stores straight from the accumulator layout (no LDS staging tile)
-#endif
-#ifndef FT_BNS_TOUCH_FIRST
-#define FT_BNS_TOUCH_FIRST 0   // 1 = the L2 touch and the table / shift loads in FRONT of x chunk 0 (rounds 3-5), 0 = behind it and the first weight step
-#endif
-#ifndef FT_BNS_WSTG
-#define FT_BNS_WSTG 1   // round 6: phase 3 of the direct kernel (two channel tiles per wave) transposes a quarter's tile through a WAVE-PRIVATE
-                        // piece of the staging tile: the wave's 64 channels of a pixel are one aligned 128-byte run of y, so it writes whole
-                        // lines without meeting the other waves — no workgroup barrier per quarter (the LDS queue of a wave is in order)
-#endif
-#ifndef FT_BNS_DIRECT_AUX
-#define FT_BNS_DIRECT_AUX 0   // cache policy of those stores (plain: the L2 merges the 16-byte pieces of a line)
-#endif
-#ifndef FT_BNS_OVL
-#define FT_BNS_OVL 0    // dev A/B: phase 3 of the direct kernel hides a quarter's epilogue inside the next quarter's weight steps
-#endif
-// the ring kernel's phase-3 epilogue (table form) in packed form (ft_common.h: bn_res_relu_acc8): 0 = scalar (the packed form needs
-// aligned register pairs and pushed <128,4,3> from 506 registers / no spill to 512 / 48 spilled)
-#ifndef FT_BNS_PK_RES
-#define FT_BNS_PK_RES 0
-#endif
-#ifndef FT_BNS_L2_TOUCH
-#define FT_BNS_L2_TOUCH 1   // the direct kernel's first round of workgroups pulls the weight stream into its XCD's L2 (one touch per line)
-#endif
+#define BNS_XKEY(hp) (((hp) >> 1) & 7)
 #ifndef FT_BNSD_ABL
 #define FT_BNSD_ABL 0   // dev ablations of the direct kernel (TIMING ONLY, results are wrong): 1 = no chunk barriers in phase 1, 2 = no residual
                         // pick-up, 16 / 32 = the weight loads of phase 1 / phases 2 + 3 are not issued at all (FT_BNS_DBG=64 still issues them)
-#endif
-#ifndef FT_BNS_PIN
-#define FT_BNS_PIN 3    // dev A/B: bit 0 = pinned issue order in phase 1 of the direct kernel, bit 1 = in its weight steps (dstep)
 #endif
 
 // MFMA row r of an A fragment holds output channel sigma(r) of its 32-channel tile, so that accumulator register k of
@@ -208,9 +177,8 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
   // dword per 128-byte line (see the direct kernel); the scratch corner sits between the zero row and the weight ring.
   // EXACTLY kTouch loads per thread (lines past the share: out of range, no traffic): the touch is issued BEHIND the first x
   // chunk (round 6: it used to sit in front of it in every wave's in-order load queue) and the first hand-counted wait counts it
-  constexpr int kTouch = FT_BNS_L2_TOUCH ? 6 : 0;
+  constexpr int kTouch = 6;
   auto issue_touch = [&]() {
-#if FT_BNS_L2_TOUCH
     constexpr int SCR = P == 256 ? 64000 : 102400;
     static_assert(SCR >= G::ZROW + ROWB && SCR + 1024 <= G::WBASE, "scratch of the L2 touch loads");
     const bool on = blockIdx.x < 256 && !(p.dbg & (512 | 1024));
@@ -225,7 +193,6 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
       const unsigned l = lo + tid + 256u * k;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (lds_ptr)(smem + SCR + wave * 256), 4, (on && l < hi) ? l << 7 : kOOB, 0, 0, 0);
     }
-#endif
   };
   // ---- loaders -------------------------------------------------------------------------------------------------------
   // x chunk: row = halo pixel, 128 bytes (64 channels); a 1-KiB wave load covers 8 rows, lane -> (row = lane / 8,
@@ -271,19 +238,11 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
   BNS_TS(0);
   // prologue: chunk 0 (x + W1 slice) leads every wave's load queue, then the L2 touch and table 0 / the shift pairs, chunks 1 and 2,
   // the zero row
-#if FT_BNS_TOUCH_FIRST
-  issue_touch();
-  if constexpr (FOLD) load_shp();
-  else issue_tab(0);
-  asm volatile("" ::: "memory");
-  issue_x(0, 0); issue_w(0, 0);
-#else
   issue_x(0, 0); issue_w(0, 0);
   issue_touch();
   if constexpr (FOLD) load_shp();
   else issue_tab(0);
   asm volatile("" ::: "memory");
-#endif
   issue_x(1, 1); issue_w(1, 1);
   issue_x(2, 2); issue_w(2, 2);
   if (tid < ROWB / 16) *reinterpret_cast<uint4_t*>(smem + G::ZROW + tid * 16) = uint4_t{0u, 0u, 0u, 0u};
@@ -329,7 +288,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
                                                               acc1[i][j], 0, 0, 0);
     };
     // chunk 0 has landed (this wave's share) while the touch, the table / shift loads and chunks 1 and 2 fly; after the barrier everyone's share has
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * (LX + LW) + (FT_BNS_TOUCH_FIRST ? 0 : kTouch + (FOLD ? 12 : G::LT))) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * (LX + LW) + kTouch + (FOLD ? 12 : G::LT)) : "memory");
     BNS_BARRIER();
     ld1(c0{}, 0, 0);
     bns_unroll<NC1>([&](auto cc) {
@@ -641,15 +600,12 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
               o = o8[h];
             } else {
               const half8_t rs = __builtin_bit_cast(half8_t, res[q][i][j][h]);
-#if FT_BNS_PK_RES
-              o = bn_res_relu_acc8(acc[i][j], h, sc, sh, rs);
-#else
+              // (scalar on purpose: the packed form, bn_res_relu_acc8, needs aligned register pairs and made <128,4,3> spill)
 #pragma unroll
               for (int e = 0; e < 8; ++e) {
                 const int r = h * 8 + e;
                 o[e] = (half_t)__builtin_fmaxf(acc[i][j][r] * sc[r >> 2][r & 3] + sh[r >> 2][r & 3] + (float)rs[e], 0.f);
               }
-#endif
             }
             if constexpr (STAGED) {
               const int m = m_out[j];
@@ -837,9 +793,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
   // kTouch loads per thread (lines past the share: out of range, no traffic), issued BEHIND x chunk 0 and the weights of step 0 —
   // the touch used to lead every wave's in-order load queue, so the first chunk waited for 100 KB of line fetches per CU (start-up
   // 5.4 k cycles of a 71 k-cycle workgroup, tools/dev/bns_phases.py) — and counted by the first hand-counted wait.
-  constexpr int kTouch = FT_BNS_L2_TOUCH ? 6 : 0;
+  constexpr int kTouch = 6;
   auto issue_touch = [&]() {
-#if FT_BNS_L2_TOUCH
     const bool on = blockIdx.x < 256 && !(p.dbg & 512);
     const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
     const int first = p.total < 256 ? p.total : 256;
@@ -852,7 +807,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
       const unsigned l = lo + tid + (unsigned)(NT * k);
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (lds_ptr)(smem + 77824 + wave * 256), 4, (on && l < hi) ? l << 7 : kOOB, 0, 0, 0);
     }
-#endif
   };
   // prologue: all six tables (12 KiB, 3 x 256-byte pieces per wave ... 48 pieces), x chunks 0..2, weights of steps 0 and 1, zero row
   // folded form: no tables in LDS; the shift pair of MFMA row l31 of every (epilogue, channel tile) of this wave sits in a register
@@ -901,19 +855,11 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
   };
   // order of every wave's (in-order) load queue: x chunk 0, the weights of step 0, the L2 touch, the tables / shift pairs, x chunks 1
   // and 2, the weights of steps 1 .. D-1
-#if FT_BNS_TOUCH_FIRST
-  issue_touch();
-  load_tables();
-  asm volatile("" ::: "memory");
-  issue_x(0, 0);
-  load_a(std::integral_constant<int, 0>{}, 0);
-#else
   issue_x(0, 0);
   load_a(std::integral_constant<int, 0>{}, 0);
   issue_touch();
   load_tables();
   asm volatile("" ::: "memory");
-#endif
   issue_x(1, 1);
   issue_x(2, 2);
   bns_unroll<D - 1>([&](auto sc) { load_a(std::integral_constant<int, decltype(sc)::value + 1>{}, decltype(sc)::value + 1); });
@@ -973,7 +919,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
     };
     // x chunk 0 has landed (this wave's share): behind it chunks 1, 2 and the two weight steps (8 loads each) may fly
     static_assert(2 * LX + 4 * CTW * D + kTouch + kTabLoads <= 63, "vmcnt immediate");
-    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * LX + 4 * CTW * D + (FT_BNS_TOUCH_FIRST ? 0 : kTouch + kTabLoads)) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * LX + 4 * CTW * D + kTouch + kTabLoads) : "memory");
     BNS_BARRIER();
     BNSD_TS(7);             // start-up: x chunk 0 of every wave has landed
     ldx(c0{}, 0, 0);
@@ -988,7 +934,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
       ldx(c1{}, buf, 1);
       mma1(c0{}, slot{}, std::integral_constant<int, 0>{});
       ldx(c0{}, buf, 2);
-      if constexpr ((FT_BNS_PIN & 1) && NW == 4) {
+      if constexpr (NW == 4) {
         // region: [x chunk c+2 DMA, slice-0 reads of this chunk, slice 3 of chunk c-1] (behind the last barrier) + the above
         __builtin_amdgcn_sched_group_barrier(0x020, LX, 0);
         bns_unroll<3>([&](auto) {
@@ -1022,7 +968,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
       load_a_half(std::integral_constant<int, (c + D) % NS>{}, c + D, c1{});
       ldx(c1{}, buf, 3);
       mma1(c0{}, slot{}, std::integral_constant<int, 2>{});
-      if constexpr ((FT_BNS_PIN & 1) && NW == 4) {
+      if constexpr (NW == 4) {
         bns_unroll<MT1>([&](auto) {
           __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
           __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
@@ -1150,16 +1096,13 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
                                                          __builtin_bit_cast(half8_t, fb[S][j]), A[i][j], 0, 0, 0);
   };
   // one weight step g (ring slot SL = g % 3): slice 0 of the pixel operand already sits in register set 0; `rbn` = row
-  // bases of the next step; `extra` = independent vector work that rides along (phase 3: a piece of the previous
-  // quarter's epilogue), NX = how many of its VALU instructions each of the eight issue groups takes
-  auto dstep = [&](auto slotc, int g, const int (&rb)[MT2], bool has_next, const int (&rbn)[MT2], float16_t (&A)[CTW][MT2], auto nxc,
-                   auto&& extra) {
-    constexpr int SL = decltype(slotc)::value, NX = decltype(nxc)::value;
+  // bases of the next step
+  auto dstep = [&](auto slotc, int g, const int (&rb)[MT2], bool has_next, const int (&rbn)[MT2], float16_t (&A)[CTW][MT2]) {
+    constexpr int SL = decltype(slotc)::value;
     using slot = std::integral_constant<int, SL>;
     load_a(std::integral_constant<int, (SL + D) % NS>{}, g + D);
     ldb(c1{}, 1, rb);
     mma2(c0{}, slot{}, std::integral_constant<int, 0>{}, A);
-    extra();
     ldb(c0{}, 2, rb);
     mma2(c1{}, slot{}, std::integral_constant<int, 1>{}, A);
     ldb(c1{}, 3, rb);
@@ -1169,22 +1112,15 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
     // Issue order of the step: one weight load and the pixel-operand reads after every MT2 MFMAs.  A buffer_load_b128 holds
     // the wave's issue port for ~40 cycles (tools/dev/ubench/l2_burst.hip: a step costs its compute time + 335 cycles for its
     // eight loads, whatever the prefetch depth); clustered as hipcc places them, the matrix pipe drains behind them.
-    if constexpr ((FT_BNS_PIN & 1) && NW == 4) {
+    if constexpr (NW == 4) {
       bns_unroll<8>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         __builtin_amdgcn_sched_group_barrier(0x008, MT2, 0);
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, (i & 1) ? (MT2 + 1) / 2 : MT2 / 2, 0);
-        if constexpr (NX > 0) {
-          __builtin_amdgcn_sched_group_barrier(0x002, NX, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, FOLD ? 0 : 1, 0);      // the folded-BN table reads of the piece
-          __builtin_amdgcn_sched_group_barrier(0x200, (i & 3) == 3 ? 1 : 0, 0);
-        }
       });
     }
   };
-  using nx0 = std::integral_constant<int, 0>;
-  auto no_extra = [] {};
 
   // ---- phase 2: nine taps x KC chunks, three taps per loop trip (12 steps: a multiple of the register ring period) -------
   {
@@ -1199,7 +1135,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
         constexpr int nkc = (kc + 1) % KC, nkx = kc + 1 == KC ? (kx + 1) % 3 : kx;
         const int nky = (kc + 1 == KC && kx == 2) ? ky + 1 : ky;
         row_bases(tap_off(nky, nkx), nkc, nkx == 0 ? 1 : (nkx == 2 ? 2 : 0), rbn, true);
-        dstep(std::integral_constant<int, (G2 + s) % NS>{}, G2 + 3 * KC * ky + s, rb, !(ky == 2 && s == 3 * KC - 1), rbn, acc, nx0{}, no_extra);
+        dstep(std::integral_constant<int, (G2 + s) % NS>{}, G2 + 3 * KC * ky + s, rb, !(ky == 2 && s == 3 * KC - 1), rbn, acc);
 #pragma unroll
         for (int j = 0; j < MT2; ++j) rb[j] = rbn[j];
       });
@@ -1258,7 +1194,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
     // WSTG: the wave's own [NOUT pixels][128 bytes = its 64 channels of the quarter] tile, 16-byte chunk c of pixel m at chunk
     // c ^ (m & 7): the eight lanes of a ds_write_b128 group (eight pixels, one chunk) and the sixteen of a ds_read_b128 group
     // (two pixels x eight chunks ...) cover distinct bank groups.  Read-out: lane -> pixel lane / 8 + 8 k, chunk lane % 8.
-    constexpr bool WSTG = FT_BNS_WSTG && FT_BNS_STG && CTW == 2;
+    constexpr bool WSTG = CTW == 2;
     constexpr int CPR = ROWB / 16, NSTG = WSTG ? NOUT / 8 : NOUT * CPR / NT;
     unsigned s_voff[NSTG];
     int s_off[NSTG];
@@ -1303,15 +1239,8 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
         half8_t o;
         if constexpr (FOLD) o = o8[h];
         else o = bn_res_relu_acc8(A[i][j], h, sc, sh, __builtin_bit_cast(half8_t, res[q][i][j][h]));
-#if FT_BNS_STG
         if constexpr (WSTG) *reinterpret_cast<half8_t*>(stg + wave * (NOUT * 128) + m * 128 + (((i * 4 + 2 * lhi + h) ^ (m & 7)) << 4)) = o;
         else *reinterpret_cast<half8_t*>(stg + m * ROWB + ((((CTW * wcol + i) * 4 + 2 * lhi + h) ^ (m & 15)) << 4)) = o;
-#else
-        // straight from the accumulator layout: the lane's 16 consecutive channels = two adjacent 16-byte stores
-        const int orow = m / TWc, ocol = m - orow * TWc;
-        const unsigned vo = (m < npix_out && ocol < cols_out) ? (unsigned)((((n * p.H + y0 + orow) * W + x0 + ocol) * p.y_cstride + p.y_coff + ch + 8 * h) * 2) : kOOB;
-        if (!(p.dbg & 4)) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_t, o), rsrc_y, vo + (unsigned)(q * P * 2), 0, FT_BNS_DIRECT_AUX);
-#endif
       }
     };
     // folded form: shift3 of the quarter and the residual join tile (i, j)'s accumulator as three MFMAs
@@ -1326,77 +1255,20 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
     auto readout = [&](auto qc) {
       constexpr int q = decltype(qc)::value;
       const char* stg = smem + STG + (q & 1) * STGB;
-#if !FT_BNS_STG
-      return;
-#endif
 #pragma unroll
       for (int k = 0; k < NSTG; ++k) {
         const uint4_t v = *reinterpret_cast<const uint4_t*>(stg + s_off[k]);
         if (!(p.dbg & 4)) __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_y, s_voff[k] + (unsigned)(q * P * 2), 0, FT_YSTORE_BUF_AUX);
       }
     };
-    [[maybe_unused]] auto zero_set = [&](float16_t (&A)[CTW][MT2]) {
-#pragma unroll
-      for (int i = 0; i < CTW; ++i)
-#pragma unroll
-        for (int j = 0; j < MT2; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) A[i][j][r] = 0.f;
-    };
-    constexpr bool OVL = FT_BNS_OVL && CTW * MT2 == KC;     // one epilogue tile per weight step
-    if constexpr (OVL) {
-    // Overlapped form: two accumulator sets alternate between the quarters; the epilogue of quarter q-1 (VALU + LDS writes,
-    // ~3.4 k cycles when it ran alone behind its quarter) rides inside the weight steps of quarter q, one (i, j) tile per
-    // step, pinned between the MFMAs by dstep's issue groups.  The staging tiles alternate as before: tile (q-1) & 1 is
-    // written during quarter q, read out behind quarter q's barrier; its previous readers (quarter q-3) are two barriers back.
-    float16_t acc_b[CTW][MT2];
-    zero_set(acc_b);
-    bns_unroll<4>([&](auto qc) {
-      constexpr int q = decltype(qc)::value;
-      float16_t (&A)[CTW][MT2] = (q & 1) ? acc_b : acc;
-      float16_t (&Aprev)[CTW][MT2] = (q & 1) ? acc : acc_b;
-      bns_unroll<KC>([&](auto kcc) {
-        constexpr int kc = decltype(kcc)::value;
-        constexpr int g = G3 + q * KC + kc;
-        row_bases(0, (kc + 1) % KC, 0, rbn, false);
-        if constexpr (q > 0) {
-          dstep(std::integral_constant<int, g % NS>{}, g, rb, g + 1 < GEND, rbn, A, std::integral_constant<int, FOLD ? 4 : 12>{},
-                [&] {
-                  if constexpr (FOLD) fold_tail(std::integral_constant<int, q - 1>{}, kc / MT2, kc % MT2, Aprev);
-                  epi_piece(std::integral_constant<int, q - 1>{}, kc / MT2, kc % MT2, Aprev);
-                });
-        } else {
-          dstep(std::integral_constant<int, g % NS>{}, g, rb, g + 1 < GEND, rbn, A, nx0{}, no_extra);
-        }
-#pragma unroll
-        for (int j = 0; j < MT2; ++j) rb[j] = rbn[j];
-      });
-      if constexpr (q > 0) {
-        zero_set(Aprev);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        BNS_BARRIER();
-        readout(std::integral_constant<int, q - 1>{});
-      }
-    });
-    // quarter 3 has no successor to hide behind
-#pragma unroll
-    for (int i = 0; i < CTW; ++i)
-#pragma unroll
-      for (int j = 0; j < MT2; ++j) {
-        if constexpr (FOLD) fold_tail(std::integral_constant<int, 3>{}, i, j, acc_b);
-        epi_piece(std::integral_constant<int, 3>{}, i, j, acc_b);
-      }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    BNS_BARRIER();
-    readout(std::integral_constant<int, 3>{});
-    } else {
+    // (hiding a quarter's epilogue inside the next quarter's weight steps was tried: it spills.  profiles/HISTORY.md)
     bns_unroll<4>([&](auto qc) {
       constexpr int q = decltype(qc)::value;
       bns_unroll<KC>([&](auto kcc) {
         constexpr int kc = decltype(kcc)::value;
         constexpr int g = G3 + q * KC + kc;
         row_bases(0, (kc + 1) % KC, 0, rbn, false);
-        dstep(std::integral_constant<int, g % NS>{}, g, rb, g + 1 < GEND, rbn, acc, nx0{}, no_extra);
+        dstep(std::integral_constant<int, g % NS>{}, g, rb, g + 1 < GEND, rbn, acc);
 #pragma unroll
         for (int j = 0; j < MT2; ++j) rb[j] = rbn[j];
       });
@@ -1411,7 +1283,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
 #pragma unroll
         for (int j = 0; j < MT2; ++j) epi_piece(qc, i, j, acc);
       zero_acc();
-#if FT_BNS_STG
       // the two staging tiles alternate: a tile's previous readers (quarter q-2) are two barriers behind
       // (wave-private pieces: a wave reads back only what it wrote itself, its LDS operations execute in order: no barrier)
       if constexpr (!WSTG) {
@@ -1421,9 +1292,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
         asm volatile("" ::: "memory");       // compiler fence only: the read-out must stay behind the tile's writes in program order
       }
       readout(qc);
-#endif
     });
-    }
   }
   if (p.dbg & 32) {
     ts[5] = __builtin_amdgcn_s_memtime();
@@ -1530,7 +1399,7 @@ static int bns_plan(const ft_bottleneck_desc* d, BnsPlan* out) {
     th = th < d->H ? th : d->H;
     return ceil_div(d->H, ceil_div(d->H, th));     // same strip count, balanced rows
   };
-  const int force = getenv("FT_BNS_VARIANT") ? atoi(getenv("FT_BNS_VARIANT")) : -1;   // dev / tests: 1, 2 or 3 (read per call)
+  const int force = dev_env_int("FT_BNS_VARIANT", -1);   // dev / tests: 1, 2 or 3 (read per call)
   if (d->P == 128) {
     // strips of <= 192 output pixels on <= 256 halo pixels (<128, 4, 3>), or of <= 128 on <= 192 (<128, 3, 2>, round 4) where the
     // large strips leave CUs idle: ResNet-101 at 384 x 288 with 16 crops per GPU has 160 large strips for 256 CUs (48 x 36 maps,
@@ -1538,7 +1407,7 @@ static int bns_plan(const ft_bottleneck_desc* d, BnsPlan* out) {
     // on MT1 halo tiles + (72 + 32) steps on MT2 output tiles, per pair of channel tiles.
     const int th_b = rows(192, 256), th_s = rows(128, 192);
     if (th_b < 1 && th_s < 1) return FT_ERR_UNSUPPORTED;
-    const int force128 = getenv("FT_BNS_VARIANT128") ? atoi(getenv("FT_BNS_VARIANT128")) : 0;   // dev / tests: 1 large, 2 small (read per call)
+    const int force128 = dev_env_int("FT_BNS_VARIANT128", 0);   // dev / tests: 1 large, 2 small (read per call)
     auto cost = [&](int th, int mt1, int mt2) {
       const long long wg = (long long)d->N * ceil_div(d->H, th);
       return ((wg + 255) / 256) * (long long)(32 * mt1 + 104 * mt2);
@@ -1562,8 +1431,6 @@ static int bns_plan(const ft_bottleneck_desc* d, BnsPlan* out) {
     th = th < d->H ? th : d->H;
     xs = cs; x_tw = tw; x_th = ceil_div(d->H, ceil_div(d->H, th));
   }
-  static const bool no_direct_k = getenv("FT_BNS_DIRECT") && atoi(getenv("FT_BNS_DIRECT")) == 0;
-  if (no_direct_k) xs = 0;
   if (th_big < 1 && th_small < 1 && !xs) return FT_ERR_UNSUPPORTED;
   int pick;
   if (force == 1 || force == 2 || (force == 3 && xs)) pick = force;
@@ -1619,9 +1486,6 @@ static int bns_launch(const BnsParams& p, hipStream_t s) {
 #endif
 #ifndef FT_BNS_XH_SLOTS
 #define FT_BNS_XH_SLOTS 3
-#endif
-#ifndef FT_BNS_WAVES_DEFAULT
-#define FT_BNS_WAVES_DEFAULT 4      // waves per workgroup of the direct kernels unless FT_BNS_WAVES says otherwise
 #endif
 template <int MT1, int MT2, bool XH, int HEADC = 0, int NW = 4, bool FOLD = false>
 static int bns_launch_direct(const BnsParams& p, hipStream_t s) {
@@ -1708,7 +1572,7 @@ extern "C" int ft_bottleneck_stream_fwd(const ft_bottleneck_desc* d, const void*
   p.y_bytes = (unsigned)((size_t)d->N * d->H * d->W * d->y_cstride * 2);
   p.ws_bytes = (unsigned)ft_bottleneck_stream_weight_bytes(d);
   if (pl.variant == 4) p.y_bytes = (unsigned)((size_t)d->N * p.Ho * p.Wo * d->y_cstride * 2);
-  static const int dbg = getenv("FT_BNS_DBG") ? atoi(getenv("FT_BNS_DBG")) : 0;
+  static const int dbg = dev_env_int("FT_BNS_DBG", 0);
   p.dbg = dbg;
   if (dbg & 64) p.ws_bytes = 0;     // dev: every weight load out of range (returns 0, no L2 access): the kernel's time without its weight stream
   if (dbg & 128) p.x_bytes = 0;     // dev: likewise the input
@@ -1717,16 +1581,14 @@ extern "C" int ft_bottleneck_stream_fwd(const ft_bottleneck_desc* d, const void*
   // for the column-split form (R101 384x288 at 16 crops: 34.4 -> 33.3 us per block, R50 at 16 crops 30.0 -> 28.5), four for the
   // full-width strips (batch 64: 46.1 vs 46.0 us — the eight-wave form gains in phases 1 and 3 what its doubled pixel-operand
   // reads cost in phase 2; both forms sit on the CU's 64 B/clk weight path: 32 KiB of fragments per 16-MFMA step)
-  const bool waves8 = getenv("FT_BNS_WAVES") ? atoi(getenv("FT_BNS_WAVES")) == 8 : (FT_BNS_WAVES_DEFAULT == 8 || pl.variant == 3);
-  static const bool no_direct = getenv("FT_BNS_DIRECT") && atoi(getenv("FT_BNS_DIRECT")) == 0;
+  const bool waves8 = dev_env_int("FT_BNS_WAVES", pl.variant == 3 ? 8 : 4) == 8;
   if (d->folded) {
     switch (pl.variant) {
       case 0: return bns_launch<128, 4, 3, true>(p, s);
       case 5: return bns_launch<128, 3, 2, true>(p, s);
       case 1: return bns_launch<256, 4, 3, true>(p, s);
       case 3: return waves8 ? bns_launch_direct<2, 1, true, 0, 8, true>(p, s) : bns_launch_direct<2, 1, true, 0, 4, true>(p, s);
-      default: return no_direct ? bns_launch<256, 3, 2, true>(p, s)
-                                : (waves8 ? bns_launch_direct<3, 2, false, 0, 8, true>(p, s) : bns_launch_direct<3, 2, false, 0, 4, true>(p, s));
+      default: return waves8 ? bns_launch_direct<3, 2, false, 0, 8, true>(p, s) : bns_launch_direct<3, 2, false, 0, 4, true>(p, s);
     }
   }
   switch (pl.variant) {
@@ -1735,9 +1597,7 @@ extern "C" int ft_bottleneck_stream_fwd(const ft_bottleneck_desc* d, const void*
     case 1: return bns_launch<256, 4, 3>(p, s);
     case 3: return waves8 ? bns_launch_direct<2, 1, true, 0, 8>(p, s) : bns_launch_direct<2, 1, true>(p, s);
     case 4: return waves8 ? bns_launch_direct<4, 1, false, 8, 8>(p, s) : bns_launch_direct<4, 1, false, 8>(p, s);
-    default: {
-      // 64-pixel strips at 256 planes: weights straight to registers (FT_BNS_DIRECT=0: through the LDS ring, dev A/B)
-      return no_direct ? bns_launch<256, 3, 2>(p, s) : (waves8 ? bns_launch_direct<3, 2, false, 0, 8>(p, s) : bns_launch_direct<3, 2, false>(p, s));
-    }
+    default:     // 64-pixel strips at 256 planes: weights straight to registers
+      return waves8 ? bns_launch_direct<3, 2, false, 0, 8>(p, s) : bns_launch_direct<3, 2, false>(p, s);
   }
 }

@@ -8,9 +8,6 @@
 
 #include "ft_common.h"
 
-#ifndef FT_EPI_NT
-#define FT_EPI_NT 0     // non-temporal stores in the fp16 epilogue (dev A/B)
-#endif
 // Workgroup barrier of the K-loops.  The builtin is IntrNoMem for LLVM: ds_reads that follow it in program order may be
 // hoisted ABOVE it (measured: the stem kernel read patch rows other waves' LDS-DMA had not landed yet, ~0.1 % of the
 // tiles wrong once workgroups are recycled on a CU).  The inline-asm form with a memory clobber pins the order.
@@ -295,11 +292,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, float16_t (&a
         const long long o = s_opix[pl];
         if (o >= 0 && co0 + ch * 8 < p.Cout) {
           const uint4_t v = *reinterpret_cast<const uint4_t*>(s_tile + pl * ROWB + ((ch ^ (pl & (NCH - 1))) << 4));
-#if FT_EPI_NT && FT_YSTORE_AUX == 0
-          __builtin_nontemporal_store(v, reinterpret_cast<uint4_t*>(ybase + o * p.y_cstride + ch * 8));
-#else
           store_out16(ybase + o * p.y_cstride + ch * 8, v);
-#endif
         }
       }
       return;

@@ -56,7 +56,7 @@ static inline int cd_wmajor(long long x_bytes, long long w_bytes, int npt, int n
   // Measured (round 6, one call): alone and L2-warm conv6_1 36.2 -> 27.1 us, conv6 21.4 -> 20.2 us; behind cold caches 35.7 -> 32.8 us;
   // FlowNet2S with the rule below 18.93 / 19.00 / 19.00 k against 19.00 / 19.02 / 19.06 k pairs/s without: nothing in the network, so
   // the order is OFF unless FT_CD_WMAJOR says otherwise (1 = every layer, 2 = the byte rule).
-  static const int mode = getenv("FT_CD_WMAJOR") ? atoi(getenv("FT_CD_WMAJOR")) : 0;
+  static const int mode = dev_env_int("FT_CD_WMAJOR", 0);
   if (mode != 2) return mode == 1;
   if (ncb < 8 || npt < 2) return 0;
   return 8 * x_bytes + w_bytes < x_bytes + 8 * w_bytes;
@@ -76,20 +76,13 @@ __host__ __device__ constexpr int cd_sigma(int r) { return 16 * ((r >> 2) & 1) +
 
 // XOR key of a ring row's 16-byte chunk position.  128-byte rows (CPR = 8): two rows share a 256-byte bank row, so the key
 // changes every second row (`row & 7` made rows r and r + 8 collide: 27-44 % bank-conflict cycles in the PMC); 512-byte rows: row & 15.
-#ifndef FT_CD_KEY_SHIFT
-#define FT_CD_KEY_SHIFT 1
-#endif
 template <int CPR>
-__device__ __forceinline__ int cd_key(int row) { return CPR < 16 ? ((row >> FT_CD_KEY_SHIFT) & (CPR - 1)) : (row & 15); }
+__device__ __forceinline__ int cd_key(int row) { return CPR < 16 ? ((row >> 1) & (CPR - 1)) : (row & 15); }
 
 #ifndef FT_CD_WSLOTS
 #define FT_CD_WSLOTS 3
 #endif
-#ifndef FT_CD_L2_TOUCH
-#define FT_CD_L2_TOUCH 0   // conv_direct_kernel: every wave touches its weight stream once at kernel start (cold L2 inside a network).
-                           // Measured in the R50 network (net_bench.py, NB_HOT=1, two runs each): the K-concat exits 27 -> 31-35 us, the step
-                           // 1.147 -> 1.169 ms: up to 36 LDS-DMA issues per wave in front of the first x load cost more than the misses they hide
-#endif
+// (an up-front touch of every wave's weight stream against the cold L2 inside a network was tried, slower: profiles/HISTORY.md)
 template <int KSPLIT>
 struct CdGeom {
   static constexpr int MT = 3, BP = 96;                       // pixel tiles per wave, pixels per workgroup
@@ -148,17 +141,6 @@ __global__ __launch_bounds__(256, 1) void conv_direct_kernel(const CdParams p) {
   const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.ws), 0, p.ws_bytes, 0x00020000);
   constexpr unsigned kOOB = 0x80000000u;
 
-#if FT_CD_L2_TOUCH
-  // Inside a network this layer's weights are not in the XCD's L2 when the kernel starts, and the register ring keeps only
-  // WS - 1 chunks (16 KiB per wave) in flight: a cold stream is paced by the miss latency.  Every wave therefore asks for all
-  // lines of ITS stream once, up front (one dword per 128-byte line, LDS-DMA into a scratch corner: the oldest vector-memory
-  // operations of the wave, every counted wait below covers them).  FT_CD_DBG & 512 switches it off.
-  if (!(p.dbg & 512)) {
-    for (int c = (NCH > 0 ? FT_CD_WSLOTS : 3) - 1; c < nchunk; ++c)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (lds_ptr)(smem + G::LDS_BYTES + wave * 256), 4, (unsigned)lane * 128u,
-                                               ((cb * nchunk + c) * 4 + wave) * 8192, 0, 0);
-  }
-#endif
   // ---- loaders ---------------------------------------------------------------------------------------------------------
   // ring row = pixel, ROWB bytes; a 1-KiB wave load covers 1024 / ROWB rows; XOR swizzle on the SOURCE 16-byte position
   constexpr int CPR = ROWB / 16;                  // 16-byte positions per row: 8 or 32
@@ -1290,7 +1272,7 @@ struct C3Plan {
 
 static int c3_plan(const ft_conv_desc* d, C3Plan* out) {
   if (!d) return FT_ERR_INVALID_ARG;
-  if (d->act == FT_ACT_LEAKY && !(d->slope >= 0.f && d->slope <= 1.f)) return FT_ERR_UNSUPPORTED;   // epilogues use max(v, k * v): valid for 0 <= k <= 1 only
+  if (d->act == FT_ACT_LEAKY && !(d->slope >= 0.f && d->slope <= 1.f)) return FT_ERR_UNSUPPORTED;   // the act_mul select of the epilogues takes any k; the rejection stays because lifting it would change which layers run here
   if (d->dtype != FT_F16 || d->transposed || d->kh != 3 || d->kw != 3 || (d->stride != 1 && d->stride != 2) || d->pad != 1) return FT_ERR_UNSUPPORTED;
   if (d->tail_cout || d->pool || d->x_wpitch || d->x2_cin || d->has_residual || d->out_layout != FT_LAYOUT_NHWC) return FT_ERR_UNSUPPORTED;
   if (d->N <= 0 || d->Hi <= 0 || d->Wi <= 0) return FT_ERR_UNSUPPORTED;
@@ -1299,15 +1281,13 @@ static int c3_plan(const ft_conv_desc* d, C3Plan* out) {
   const int hw = d->Hi * d->Wi;
   if (d->stride == 2) {
     // one image per workgroup, its whole INPUT map (<= 256 pixels) resident 256 channels at a time (conv3x3s2_direct_kernel)
-    static const bool no_s2 = getenv("FT_CD_NO_S2") != nullptr;                                   // dev A/B
-    if (no_s2 || d->Ho != (d->Hi + 1) / 2 || d->Wo != (d->Wi + 1) / 2) return FT_ERR_UNSUPPORTED;
+    if (d->Ho != (d->Hi + 1) / 2 || d->Wo != (d->Wi + 1) / 2) return FT_ERR_UNSUPPORTED;
     if (d->Cin != 512) return FT_ERR_UNSUPPORTED;                // (instantiated for two 256-channel passes)
     if (hw > 256 || d->Ho * d->Wo > 64) {
       // strips of R output rows: (2 R + 1) * Wi <= 256 tile rows, R * Wo <= 64 output pixels (FlowNet's conv5 on 24 x 32: R = 3)
-      static const bool no_strip = getenv("FT_CD_NO_STRIP") != nullptr;                            // dev A/B
       int R = (256 / d->Wi - 1) / 2;
       if (R * d->Wo > 64) R = 64 / d->Wo;
-      if (no_strip || R < 1) return FT_ERR_UNSUPPORTED;
+      if (R < 1) return FT_ERR_UNSUPPORTED;
       const int nstrips = (d->Ho + R - 1) / R;
       const long long nwg = (long long)d->N * nstrips * (d->Cout / 64);
       if (nwg < 200 || nwg > 1024) return FT_ERR_UNSUPPORTED;
@@ -1320,9 +1300,8 @@ static int c3_plan(const ft_conv_desc* d, C3Plan* out) {
       return FT_ERR_UNSUPPORTED;
     // two images per workgroup (conv3x3s2p_direct_kernel: half the weight stream per output pixel) where that still gives about one
     // workgroup per CU; else one image per workgroup
-    static const bool no_pair = getenv("FT_CD_NO_S2P") != nullptr;                                 // dev A/B
     const int npo = d->Ho * d->Wo;
-    if (!no_pair && 2 * npo <= 96 && 2 * hw <= 512 && (long long)((d->N + 1) / 2) * (d->Cout / 64) >= 200) {
+    if (2 * npo <= 96 && 2 * hw <= 512 && (long long)((d->N + 1) / 2) * (d->Cout / 64) >= 200) {
       *out = C3Plan{(2 * npo + 31) / 32, d->Cin / 256, 2, (d->N + 1) / 2, d->Cout / 64, 2};
       return FT_OK;
     }
@@ -1336,10 +1315,9 @@ static int c3_plan(const ft_conv_desc* d, C3Plan* out) {
   if (d->Cin == 512 && hw > 128) {
     // maps too large to be resident whole: strips of R output rows + a halo row on either side, (R + 2) * W <= 128 tile rows and
     // R * W <= 96 output pixels (FlowNet's conv5_1 on 12 x 16: R = 6), where that gives about one workgroup per CU or more
-    static const bool no_strip = getenv("FT_CD_NO_STRIP") != nullptr;                              // dev A/B
     int R = 128 / d->Wi - 2;
     if (R * d->Wi > 96) R = 96 / d->Wi;
-    if (no_strip || R < 2) return FT_ERR_UNSUPPORTED;
+    if (R < 2) return FT_ERR_UNSUPPORTED;
     const int nstrips = (d->Hi + R - 1) / R;
     const long long nwg = (long long)d->N * nstrips * (d->Cout / 64);
     if (nwg < 200 || nwg > 1024) return FT_ERR_UNSUPPORTED;
@@ -1585,7 +1563,7 @@ struct CdPlan {
 
 static int cd_plan(const ft_conv_desc* d, CdPlan* out) {
   if (!d) return FT_ERR_INVALID_ARG;
-  if (d->act == FT_ACT_LEAKY && !(d->slope >= 0.f && d->slope <= 1.f)) return FT_ERR_UNSUPPORTED;   // epilogues use max(v, k * v): valid for 0 <= k <= 1 only
+  if (d->act == FT_ACT_LEAKY && !(d->slope >= 0.f && d->slope <= 1.f)) return FT_ERR_UNSUPPORTED;   // the act_mul select of the epilogues takes any k; the rejection stays because lifting it would change which layers run here
   if (d->dtype != FT_F16 || d->transposed) return FT_ERR_UNSUPPORTED;
   const bool taps = d->kh != 1 || d->kw != 1;
   if (taps) {        // the gather form: 3x3, stride 1 or 2, pad 1, no second input, no residual
@@ -1606,7 +1584,7 @@ static int cd_plan(const ft_conv_desc* d, CdPlan* out) {
   // many pixels, short K, plain epilogue: the weight-stationary persistent form (the HBM-bound ResNet layer2.0.conv1: K = 256
   // in 128-channel blocks).  FT_CD_STATIONARY=2 (dev) also sends K = 512 -> 256 layers with >= 32768 pixels (layer3.0.conv1)
   // to the 8-wave form: measured 24.7 us against 22.3 us for the K-split kernel, and 1.8 % slower over the whole pose step.
-  static const int cs_mode = getenv("FT_CD_STATIONARY") ? atoi(getenv("FT_CD_STATIONARY")) : 1;
+  static const int cs_mode = dev_env_int("FT_CD_STATIONARY", 1);
   const bool cs256 = d->Cin == 256 && d->Cout % 128 == 0 && M > 65536, cs512 = cs_mode == 2 && d->Cin == 512 && d->Cout == 256 && M >= 32768;
   if (!taps && cs_mode != 0 && !d->x2_cin && !d->has_residual && (cs256 || cs512)) {
     const int bp = cs256 ? 128 : 64;
@@ -1615,7 +1593,6 @@ static int cd_plan(const ft_conv_desc* d, CdPlan* out) {
   }
   if (!taps && M > 65536) return FT_ERR_UNSUPPORTED;
   const int npt = (int)((M + 95) / 96);
-  static const int force = getenv("FT_CD_KSPLIT") ? atoi(getenv("FT_CD_KSPLIT")) : 0;
   const bool a_ok = d->Cout % 256 == 0 && d->Cin % 64 == 0 && d->x2_cin % 64 == 0;
   const bool b_ok = d->Cin % 256 == 0 && d->x2_cin % 256 == 0;
   if (!a_ok && !b_ok) return FT_ERR_UNSUPPORTED;
@@ -1624,8 +1601,6 @@ static int cd_plan(const ft_conv_desc* d, CdPlan* out) {
   // vs 18 us in conv_igemm_dma_kernel)
   int ks = a_ok ? 1 : 4;
   if (a_ok && b_ok && (long long)npt * (d->Cout / 256) < 160 && d->Cout <= 512) ks = 4;
-  if (force == 1 && a_ok) ks = 1;
-  if (force == 4 && b_ok) ks = 4;
   const int ck = ks == 1 ? 64 : 256;
   *out = CdPlan{ks, d->kh * d->kw * (d->Cin / ck), d->x2_cin / ck, npt, d->Cout / (ks == 1 ? 256 : 64)};
   return FT_OK;
@@ -1634,7 +1609,7 @@ static int cd_plan(const ft_conv_desc* d, CdPlan* out) {
 template <int KSPLIT, bool HAS_RES, int NCH, bool TAPS = false>
 static int cd_launch(const CdParams& p, hipStream_t s) {
   auto k = conv_direct_kernel<KSPLIT, HAS_RES, NCH, TAPS>;
-  constexpr int lds = CdGeom<KSPLIT>::LDS_BYTES + (FT_CD_L2_TOUCH ? 1024 : 0);     // (+ the L2 touch's scratch)
+  constexpr int lds = CdGeom<KSPLIT>::LDS_BYTES;
   static_assert(lds <= 163840, "LDS map");
   static bool attr_done[64] = {};
   int dev = 0;
@@ -1648,17 +1623,12 @@ static int cd_launch(const CdParams& p, hipStream_t s) {
   return FT_OK;
 }
 
-#ifndef FT_CD_TAPS72
-#define FT_CD_TAPS72 1
-#endif
 template <int KSPLIT>
 static int cd_dispatch_taps(const CdParams& p, hipStream_t s) {
   if (KSPLIT == 1) {
     switch (p.nc1) {   // 3x3 on 256 channels in 64-channel chunks; longer walks take the run-time loop
       case 36: return cd_launch<KSPLIT, false, 36, true>(p, s);
-#if FT_CD_TAPS72
       case 72: return cd_launch<KSPLIT, false, 72, true>(p, s);     // 3x3 on 512 channels (FlowNet conv4_1 / conv5 / conv5_1)
-#endif
       default: return cd_launch<KSPLIT, false, 0, true>(p, s);
     }
   }
@@ -1671,8 +1641,7 @@ static int cd_dispatch_taps(const CdParams& p, hipStream_t s) {
 
 template <int KSPLIT, bool HAS_RES>
 static int cd_dispatch(const CdParams& p, hipStream_t s) {
-  static const bool no_unroll = getenv("FT_CD_NO_UNROLL") != nullptr;     // dev A/B: the run-time-loop form
-  const int n = no_unroll ? 0 : p.nc1 + p.nc2;
+  const int n = p.nc1 + p.nc2;
   if (KSPLIT == 1) {
     switch (n) {     // K = 256 / 384 / 512 / 768 / 1024 / 1536 (ResNet layer2-4 1x1 convs and their K-concatenated block exits)
       case 4: return cd_launch<KSPLIT, HAS_RES, 4>(p, s);
@@ -1871,7 +1840,7 @@ extern "C" int ft_conv_direct_fwd(const ft_conv_desc* d, const void* x, const vo
     p.res_cstride = d->res_cstride; p.res_coff = d->res_coff;
     p.res_bytes = (unsigned)((size_t)p.M * d->res_cstride * 2);
   }
-  static const int dbg = getenv("FT_CD_DBG") ? atoi(getenv("FT_CD_DBG")) : 0;
+  static const int dbg = dev_env_int("FT_CD_DBG", 0);
   p.dbg = dbg;
   p.wmajor = cd_wmajor((long long)d->N * d->Hi * d->Wi * d->Cin * 2 + (d->x2_cin ? (long long)d->N * d->x2_hi * d->x2_wi * d->x2_cin * 2 : 0), p.ws_bytes,
                        p.npt, p.ncb);

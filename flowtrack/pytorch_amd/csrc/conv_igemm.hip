@@ -33,9 +33,6 @@
 
 #include "ft_common.h"
 
-#ifndef FT_DMA_FRAGDB
-#define FT_DMA_FRAGDB 0   // 1: double-buffer the MFMA fragments in registers across K-steps (+32 VGPRs)
-#endif
 #ifndef FT_DMA_BKB
 #define FT_DMA_BKB 64
 #endif
@@ -219,22 +216,6 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvParams p) {
 // pixel stride (x_cstride >= x_coff + cin_pad, padding channels zero), buffers < 2 GiB.
 // Occupancy target (waves per SIMD) the register allocator must respect: the K-loop is latency-bound per
 // workgroup (one barrier per K-step), so co-resident workgroups are what keeps the MFMA pipe fed.
-// Workgroup barrier of the K-loops.  The builtin is IntrNoMem for LLVM: ds_reads that follow it in program order may be
-// hoisted ABOVE it (measured: the stem kernel read patch rows other waves' LDS-DMA had not landed yet, ~0.1 % of the
-// tiles wrong once workgroups are recycled on a CU).  The inline-asm form with a memory clobber pins the order.
-#define FT_LDS_BARRIER() asm volatile("s_barrier" ::: "memory")
-#ifndef FT_HALO_KEY_SHIFT
-#define FT_HALO_KEY_SHIFT 1    // dev A/B: 0 = the old `r & 7` patch key of conv_halo_kernel's 128-byte rows
-#endif
-#ifndef FT_EPI_NT
-#define FT_EPI_NT 0     // non-temporal stores in the fp16 epilogue (dev A/B)
-#endif
-#ifndef FT_DMA_INTERLEAVE
-#define FT_DMA_INTERLEAVE 1
-#endif
-#ifndef FT_DMA_LEAN
-#define FT_DMA_LEAN 1
-#endif
 #ifndef FT_DMA_WAVES_BIG
 #define FT_DMA_WAVES_BIG 3   // 128x128 tile: 64 accumulator + <= 104 other registers
 #endif
@@ -263,7 +244,7 @@ void conv_igemm_dma_kernel(const ConvParams p) {
   static_assert((NW == 4 || NW == 8) && NIA >= 1 && NIB >= 1 && (KS == 1 || NW == 4), "tile shape");
   static_assert(BC % (RPI * NW) == 0 && BP % (RPI * NW) == 0, "tile rows must split evenly over the waves");
   static_assert(NL * (STAGES - 1) <= 63, "vmcnt is a 6-bit counter");
-  static_assert(STAGES >= (FT_DMA_FRAGDB ? 3 : 2), "ring depth");
+  static_assert(STAGES >= 2, "ring depth");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef __attribute__((address_space(3))) void* lds_ptr;
@@ -415,7 +396,7 @@ void conv_igemm_dma_kernel(const ConvParams p) {
 
   // issue state of the stage being filled (wave-uniform scalars), split from the loads themselves so the
   // K-loop can interleave ONE load after each MFMA: a blocked vector-memory issue then hides under the
-  // matrix instruction that is still executing instead of leaving the pipe empty (FT_DMA_INTERLEAVE)
+  // matrix instruction that is still executing instead of leaving the pipe empty
   char* is_sA = gsm;
   bool is_live = false;
   int is_asoff = 0, is_delta = 0;
@@ -507,47 +488,6 @@ void conv_igemm_dma_kernel(const ConvParams p) {
   for (int s = 0; s < STAGES - 1; ++s) issue(s);
 
   int cur = 0, nxt = STAGES - 1;   // ring slot of K-step ks; slot the next issue() fills
-#if FT_DMA_FRAGDB
-  // Fragment registers are double-buffered: while the MFMAs of K-step ks run from set P, the
-  // ds_read_b128s of K-step ks+1 fill set P^1, so no MFMA ever waits on LDS latency right after a
-  // barrier.  (Static set indices: the loop is unrolled by two through step<P>().)
-  uint4_t fa[2][KK][MT_C], fb[2][KK][MT_P];
-  auto load_frags = [&](auto set, int slot) {
-    constexpr int P = decltype(set)::value;
-    const char* st = gsm + slot * STAGE;
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk) {
-#pragma unroll
-      for (int i = 0; i < MT_C; ++i) fa[P][kk][i] = *reinterpret_cast<const uint4_t*>(st + (a_off[i] ^ (kk << 5)));
-#pragma unroll
-      for (int j = 0; j < MT_P; ++j) fb[P][kk][j] = *reinterpret_cast<const uint4_t*>(st + (b_off[j] ^ (kk << 5)));
-    }
-  };
-  auto step = [&](auto set) {
-    constexpr int P = decltype(set)::value;
-    const int cur1 = cur + 1 == STAGES ? 0 : cur + 1;
-    // this wave's loads of K-step ks+1 have landed (STAGES-3 younger stages may still be in flight) ...
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL * (STAGES - 3)) : "memory");
-    // ... after the barrier everyone's have, and everyone is done reading the slot issue() refills
-    FT_LDS_BARRIER();
-    issue(nxt);
-    load_frags(std::integral_constant<int, P ^ 1>{}, cur1);
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk) mma_slice<MT_C, MT_P>(fa[P][kk], fb[P][kk], acc, (T*)nullptr);
-    cur = cur1;
-    nxt = nxt + 1 == STAGES ? 0 : nxt + 1;
-  };
-
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL * (STAGES - 2)) : "memory");
-  FT_LDS_BARRIER();
-  load_frags(std::integral_constant<int, 0>{}, 0);
-  int ks = 0;
-  for (; ks + 1 < nk_g; ks += 2) {
-    step(std::integral_constant<int, 0>{});
-    step(std::integral_constant<int, 1>{});
-  }
-  if (ks < nk_g) step(std::integral_constant<int, 0>{});
-#else
 #ifdef FT_CONV_TIMING   // developer build: per-phase s_memtime accounting of the K-loop, dumped through p.y
   unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0};
   const unsigned long long t_start = __builtin_readcyclecounter();
@@ -560,7 +500,7 @@ void conv_igemm_dma_kernel(const ConvParams p) {
 #else
 #define FT_T(i) do { } while (0)
 #endif
-#if FT_DMA_LEAN && !defined(FT_CONV_TIMING)
+#ifndef FT_CONV_TIMING
   constexpr bool kLean = (KS == 1);
 #else
   constexpr bool kLean = false;
@@ -725,7 +665,7 @@ void conv_igemm_dma_kernel(const ConvParams p) {
     // ... after the barrier everyone's have, and everyone is done reading the slot issue() refills
     FT_LDS_BARRIER();
     FT_T(1);
-#if FT_DMA_INTERLEAVE && !defined(FT_CONV_TIMING)
+#ifndef FT_CONV_TIMING
     if constexpr (sizeof(T) == 2) {
       issue_prep(nxt);
       const char* st = gsm + cur * STAGE;
@@ -797,7 +737,6 @@ void conv_igemm_dma_kernel(const ConvParams p) {
     }
     return;
   }
-#endif
 #endif
   // drain the (all out-of-range) tail loads before LDS is reused by the epilogue
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1013,7 +952,7 @@ __global__ __launch_bounds__(256, (CCH == 32 ? 3 : 2)) void conv_halo_kernel(con
   // (SQ_WAIT_INST_LDS 4-8 % of wave cycles), so removing conflict cycles does not show.  Kept because it is the consistent key;
   // it is not a speed-up.  64-byte rows (CCH == 32) keep (r >> 2) & 3: their conflicts (40-56 %) come from the jump of PW - TW
   // rows between tile rows inside one 16-lane group, which no per-row key addresses.
-  auto pswz = [](int r) { return CCH == 64 ? ((r >> FT_HALO_KEY_SHIFT) & 7) : ((r >> 2) & 3); };
+  auto pswz = [](int r) { return CCH == 64 ? ((r >> 1) & 7) : ((r >> 2) & 3); };
   unsigned p_voff[NPWW_MAX];      // patch pixel rows of ROWB bytes: LPP lanes per pixel
   {
     const int ppl = lane / LPP, pos = lane % LPP;
@@ -1558,13 +1497,7 @@ __global__ __launch_bounds__(512, 1) void conv_stem_persist_kernel(const ConvPar
 // fp16 in LDS, and writes only the pooled maxima: the [N, H/2, W/2, 64] stem map — the largest activation of the trunk,
 // 100 MB at batch 64 — is never written or re-read.  Pooling happens on the same fp16 values the separate launches
 // would pool, so the result is bit-identical to conv_stem_kernel + maxpool3x3s2.
-// Round 6, tried and left OFF (FT_STEM_POOL_ALLW=1): all seven kernel rows' weights (28 KiB) DMA'd into LDS in the prologue and the K
-// walk without a wait or a barrier (the three-slot ring puts a full vmcnt(0) + s_barrier in front of every ten MFMAs of a wave).
-// Bit-identical, and SLOWER: 54.3 vs 50.3 us in the network (three interleaved runs each, one box) — a workgroup then waits for 28 KiB of
-// weights before its first MFMA instead of 8, and the barriers were not what the patch gather leaves exposed.
-#ifndef FT_STEM_POOL_ALLW
-#define FT_STEM_POOL_ALLW 0
-#endif
+// (all seven kernel rows' weights resident in LDS instead of the three-slot ring was tried, slower: profiles/HISTORY.md)
 #ifndef FT_STEM_ABL
 #define FT_STEM_ABL 0     // dev ablations (timing only, wrong results): 1 = no planar gather loads, 2 = no output stores, 4 = no weight loads, 8 = no MFMAs
 #endif
@@ -1582,7 +1515,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_pool_kernel(const ConvParams
   constexpr int KH = 7, STRIDE = 2, BC = 64, NW = 4, WGP = 2;
   constexpr int PT = 8, TS = 2 * PT + 1, NPX = TS * TS;      // pooled tile edge, stem patch edge (17), stem pixels (289)
   constexpr int MT_P = 5, WT_P = MT_P * 32;                  // 2 x 160 >= 289 pixels
-  constexpr int S = FT_STEM_POOL_ALLW ? KH : 3, A_STAGE = BC * RUNB;
+  constexpr int S = 3, A_STAGE = BC * RUNB;
   constexpr int CH = RUNB / 16, SWZ_DIV = 256 / RUNB >= 1 ? 256 / RUNB : 1, RPI = 64 / CH;
   constexpr int NIA = BC / RPI / NW;
   constexpr int G = RUNB / 32;
@@ -1707,7 +1640,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_pool_kernel(const ConvParams
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_a, (lds_ptr)(ring + slot * A_STAGE + (wave + NW * t) * 1024), 16,
                                                (live && !(FT_STEM_ABL & 4)) ? a_voff[t] : kOOB, live ? ky * RUNB : 0, 0, 0);
   };
-  static_for<FT_STEM_POOL_ALLW ? S : S - 1>([&](auto sc) { load_a(sc, decltype(sc)::value < KH, decltype(sc)::value); });
+  static_for<S - 1>([&](auto sc) { load_a(sc, decltype(sc)::value < KH, decltype(sc)::value); });
   if (p.x_planar) {                            // the gathered pixels land in the patch while the first weight rows are on their way
 #pragma unroll
     for (int t = 0; t < NR; ++t) {
@@ -1741,11 +1674,9 @@ __global__ __launch_bounds__(256, 2) void conv_stem_pool_kernel(const ConvParams
   static_for<KH>([&](auto ky_c) {
     constexpr int ky = decltype(ky_c)::value;
     constexpr int slot = ky % S, nslot = (ky + S - 1) % S;
-    if constexpr (!FT_STEM_POOL_ALLW || ky == 0) {
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // full wait: see conv_stem_kernel
-      FT_LDS_BARRIER();
-    }
-    if constexpr (!FT_STEM_POOL_ALLW) load_a(std::integral_constant<int, nslot>{}, ky + S - 1 < KH, ky + S - 1);
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // full wait: see conv_stem_kernel
+    FT_LDS_BARRIER();
+    load_a(std::integral_constant<int, nslot>{}, ky + S - 1 < KH, ky + S - 1);
     const char* sa = ring + slot * A_STAGE;
     const char* pb = patch + ky * RBp;
 #pragma unroll
@@ -2418,8 +2349,7 @@ static int launch_dma_r(const ConvParams& p, dim3 grid, hipStream_t s) {
 template <typename T, int BP, int BC, int WGP, int WGC, int KS = 1, int BKB = kDmaBKB, int S = kDmaStages>
 static int launch_dma(const ConvParams& p, dim3 grid, hipStream_t s) {
   // the residual-prefetch variant exists for the fp16 LDS-transposed epilogue only
-  static const bool no_respre = getenv("FT_NO_RESPRE") != nullptr;   // dev A/B: load the residual in the epilogue instead
-  if (sizeof(T) == 2 && p.res && p.epi_lds && !no_respre) return launch_dma_r<T, BP, BC, WGP, WGC, true, KS, BKB, S>(p, grid, s);
+  if (sizeof(T) == 2 && p.res && p.epi_lds) return launch_dma_r<T, BP, BC, WGP, WGC, true, KS, BKB, S>(p, grid, s);
   return launch_dma_r<T, BP, BC, WGP, WGC, false, KS, BKB, S>(p, grid, s);
 }
 
@@ -2456,7 +2386,6 @@ static int launch_stem_nt(const ConvParams& p, int nt, dim3 grid, size_t lds, hi
 
 // geometry of the persistent stem form for `d` (pw / npww / lds), or false where it does not apply
 static bool stem_persist_plan(const ft_conv_desc* d, const Geometry& g, int* pw_out, int* npww_out, size_t* lds_out, int* ntiles_out) {
-  static const bool no_persist = getenv("FT_STEM_PERSIST") && atoi(getenv("FT_STEM_PERSIST")) == 0;
   const int runb = g.cin_pad * 2, cpb = d->x_cstride * 2;
   const int ph = 7 * d->stride + d->kh;
   const int rb1 = 15 * d->stride * cpb + runb;
@@ -2465,7 +2394,7 @@ static bool stem_persist_plan(const ft_conv_desc* d, const Geometry& g, int* pw_
   const size_t lds = (size_t)d->kh * 64 * runb + 2 * (2 * (size_t)npww * 4096 + 16384);   // weights + two quartets' patch pair and output tile
   const long long ybytes = (long long)d->N * d->Ho * d->Wo * d->y_cstride * 2;
   const int ntiles = d->N * ceil_div(d->Ho, 8) * ceil_div(d->Wo, 16);
-  if (no_persist || d->kh != 7 || npww > 12 || lds > 160 * 1024 || ybytes >= (1LL << 31) || ntiles < 512) return false;
+  if (d->kh != 7 || npww > 12 || lds > 160 * 1024 || ybytes >= (1LL << 31) || ntiles < 512) return false;
   *pw_out = pw; *npww_out = npww; *lds_out = lds; *ntiles_out = ntiles;
   return true;
 }
@@ -2475,12 +2404,11 @@ static int launch_stem(ConvParams p, const ft_conv_desc* d, const Geometry& g, h
   const int ph = 7 * d->stride + d->kh;
   // super-tile = nt tiles of 8x16 outputs side by side share one pass over the weights.  Measured (in situ, us):
   // pose stem (64-byte rows) nt 1/2/4 = 47.5 / 53.6 / 73; FlowNet stem (128-byte rows) 72.2 / 67.6 / 81.4
-  static const int force_nt = getenv("FT_STEM_NT") ? atoi(getenv("FT_STEM_NT")) : 0;   // dev knob (1 or 2)
-  int nt = force_nt == 1 || force_nt == 2 ? force_nt : (runb >= 128 ? 2 : 1);
+  int nt = runb >= 128 ? 2 : 1;
   if (nt == 2 && ((ceil_div(d->Wo, 32) * 32 - d->Wo) * 100 / d->Wo >= 10 || ph * round_up(31 * d->stride * cpb + runb, 16) > 56 * 1024))
     nt = 1;
   {
-    // persistent weight-stationary form (one workgroup per CU walks many 8 x 16 tiles): FT_STEM_PERSIST=0 keeps the per-tile kernel
+    // persistent weight-stationary form (one workgroup per CU walks many 8 x 16 tiles) where stem_persist_plan offers it
     int pw, npww, ntiles;
     size_t lds;
     const long long ybytes = (long long)d->N * d->Ho * d->Wo * d->y_cstride * 2;
@@ -2549,7 +2477,7 @@ static int launch_stem_pool(ConvParams p, const ft_conv_desc* d, const Geometry&
   p.h_tx = ceil_div(Wp, 8);
   p.npt = d->N * p.h_ty * p.h_tx;
   p.nct = 1;
-  size_t lds = (size_t)(FT_STEM_POOL_ALLW ? 7 : 3) * 64 * runb + p.h_pb;
+  size_t lds = (size_t)3 * 64 * runb + p.h_pb;
   if (lds < 320 * 128) lds = 320 * 128;
   if (p.x_planar && p.h_pw == 20 && d->Cin == 3)      // the pose stem from the NCHW fp32 crop: compile-time patch pitch, division-free gather
     hipLaunchKernelGGL((conv_stem_pool_kernel<64, 20>), dim3(p.npt), dim3(256), lds, s, p, Hp, Wp);
@@ -2692,11 +2620,6 @@ static bool tile_valid(const ft_conv_desc* d, const Geometry& g, int bp, int bc,
   return true;
 }
 
-static int env_int(const char* name) {  // developer tile overrides (FT_CONV_BP / FT_CONV_BC), 0 = heuristic
-  const char* v = getenv(name);
-  return v ? atoi(v) : 0;
-}
-
 }  // namespace ft
 
 using namespace ft;
@@ -2745,7 +2668,7 @@ extern "C" int ft_conv_tile_candidates(const ft_conv_desc* d, int* hints, int ma
     const int Hq = d->transposed ? d->Hi : d->Ho, Wq = d->transposed ? d->Wi : d->Wo;
     const long long M = (long long)d->N * Hq * Wq;
     static const int kSkTiles[3][2] = {{128, 128}, {64, 128}, {64, 64}};
-    static const int sk_max_blocks = getenv("FT_SK_MAX_BLOCKS") ? atoi(getenv("FT_SK_MAX_BLOCKS")) : 256;   // dev knob
+    constexpr int sk_max_blocks = 256;
     for (const auto& t : kSkTiles) {
       if (g.cout_pad % t[1] != 0) continue;
       const long long nblk = (long long)ceil_div((int)M, t[0]) * (g.cout_pad / t[1]) * g.nphases;
@@ -2755,10 +2678,7 @@ extern "C" int ft_conv_tile_candidates(const ft_conv_desc* d, int* hints, int ma
           hints[n++] = t[0] | (t[1] << 12) | (1 << 24) | (wide << kHintWideShift) | (lg << kHintSkShift);
     }
   }
-  // dev: A/B the tile benchmark without the halo variants ("1": none, "stem": no stem kernel, "conv": no conv_halo_kernel)
-  static const char* nh = getenv("FT_CONV_NO_HALO");
-  const bool no_halo = nh && (nh[0] == '1' || (nh[0] == 's' && g.rowpack) || (nh[0] == 'c' && !g.rowpack));
-  for (int bc = 128; bc >= 64 && !no_halo; bc >>= 1)
+  for (int bc = 128; bc >= 64; bc >>= 1)
     if (n < max && tile_valid(d, g, 128, bc, 1, 0, true)) hints[n++] = 128 | (bc << 12) | (1 << 24) | kHintHalo;
   return n;
 }
@@ -2908,7 +2828,7 @@ static int conv2d_fwd_impl(const ft_conv_desc* d, const void* x, const void* w_p
   p.act = d->act;
   p.slope = d->slope;
   p.nph = g.nphases;
-  static const int dbg = env_int("FT_CONV_DBG");
+  static const int dbg = dev_env_int("FT_CONV_DBG", 0);
   p.dbg = dbg;
   p.shift_n = d->shift_nstride;
   p.x_planar = 0;
@@ -2946,13 +2866,9 @@ static int conv2d_fwd_impl(const ft_conv_desc* d, const void* x, const void* w_p
     p.tail_w = static_cast<const char*>(residual);
     p.tail_cout = d->tail_cout;
     p.epi_lds = 1;
-    // FT_TAIL_BP=256 (dev A/B): 256 pixels x 256 channels per 8-wave workgroup (wide-K form).  Half the weight-tile traffic
-    // per pixel, but one workgroup per CU with its 8 waves in lock-step: measured 160 vs 146 us on deconv.6 + heatmap at
-    // batch 64 — the 128-pixel tile (two workgroups per CU) stays the default.
-    static const int tail_bp = env_int("FT_TAIL_BP");
-    const bool big = d->Cout == 256 && g.kc % 2 == 0 && tail_bp == 256;
-    static const int tail_8ph = env_int("FT_TAIL_8PH");   // dev: 1 forces the 8-phase tile, -1 forbids it
-    const bool want8 = tail_8ph > 0 || (tail_8ph == 0 && ((d->tile_hint >> kHintWideShift) & 3) == kWide8);
+    // the 128-pixel tile (two workgroups per CU) unless the hint asks for the 8-phase 256 x 256 tile; a 256-pixel wide-K dma tile
+    // was tried and was slower: profiles/HISTORY.md
+    const bool want8 = ((d->tile_hint >> kHintWideShift) & 3) == kWide8;
     if (want8 && d->Cout == 256 && tile_valid(d, g, 256, 256, 1, kWide8)) {
       p.npt = ceil_div(p.M, 256);
       p.nct = 1;
@@ -2966,18 +2882,11 @@ static int conv2d_fwd_impl(const ft_conv_desc* d, const void* x, const void* w_p
       FT_LAUNCH_CHECK("conv_igemm8_kernel (tail)");
       return FT_OK;
     }
-    static const bool tail_lo_off = getenv("FT_TAIL_LO") && atoi(getenv("FT_TAIL_LO")) == 0;   // dev A/B: hi weights only
-    if (tail_lo_off) p.dbg |= 128;
-    p.npt = ceil_div(p.M, big ? 256 : 128);
+    p.npt = ceil_div(p.M, 128);
     p.nct = 1;
     if ((long long)p.npt * p.nph > 0x7fffffffLL) return FT_ERR_UNSUPPORTED;
     dim3 grid(p.npt * p.nph);
-    if (big) {
-      p.kc = g.kc >> 1;
-      p.nk = g.nk >> 1;
-    }
-    const int rc = big ? launch_dma<half_t, 256, 256, 4, 2, 1, 128, 2>(p, grid, s)
-                   : d->Cout == 256 ? launch_dma<half_t, 128, 256, 2, 4>(p, grid, s)
+    const int rc = d->Cout == 256 ? launch_dma<half_t, 128, 256, 2, 4>(p, grid, s)
                    : d->Cout == 128 ? launch_dma<half_t, 128, 128, 2, 2>(p, grid, s) : launch_dma<half_t, 128, 64, 2, 2>(p, grid, s);
     if (rc != FT_OK) return rc;
     FT_LAUNCH_CHECK("conv_igemm_dma_kernel (tail)");
@@ -3012,8 +2921,6 @@ static int conv2d_fwd_impl(const ft_conv_desc* d, const void* x, const void* w_p
         }
       }
     }
-    // explicit choice: the caller's benchmarked hint, or the developer override from the environment
-    static const int force = (env_int("FT_CONV_BP") & 0xfff) | ((env_int("FT_CONV_BC") & 0xfff) << 12) | (env_int("FT_CONV_KS") << 24);
     // few workgroups + long K: the K-loop is latency-bound (one barrier per step, <= 2 waves per SIMD), so take
     // 128 bytes of K per step instead of splitting K (measured in situ on R50 / FlowNet2S: 15-25 % on those layers)
     int wide = 0, sk = 1;
@@ -3026,8 +2933,7 @@ static int conv2d_fwd_impl(const ft_conv_desc* d, const void* x, const void* w_p
       ks = 1;
       if (wide && !tile_valid(d, g, bp, bc, 1, wide)) wide = 0;
     }
-    static const int force_wide = env_int("FT_CONV_WIDE"), force_halo = env_int("FT_CONV_HALO");
-    const int hint = force ? (force | ((force_wide & 3) << kHintWideShift) | (force_halo ? kHintHalo : 0)) : d->tile_hint;
+    const int hint = d->tile_hint;       // explicit choice: the caller's benchmarked hint
     if (hint) {
       const int hbp = hint & 0xfff, hbc = (hint >> 12) & 0x1ff, hks = (hint >> 24) & 0xf;
       const int hwide = (hint >> kHintWideShift) & 3;
@@ -3120,17 +3026,15 @@ static int conv2d_fwd_impl(const ft_conv_desc* d, const void* x, const void* w_p
   }
   if (g.dma) return FT_ERR_UNSUPPORTED;  // packed for the dma layout but the activation buffer is >= 2 GiB
 
-  static const bool no_pflow = getenv("FT_CONV_NO_PFLOW") != nullptr;   // dev: A/B against the few-output kernel
-  if (!no_pflow && !d->transposed && d->Cout <= 2 && d->dtype == FT_F16 && d->kh == 3 && d->kw == 3 && d->stride == 1 &&
+  if (!d->transposed && d->Cout <= 2 && d->dtype == FT_F16 && d->kh == 3 && d->kw == 3 && d->stride == 1 &&
       d->pad == 1 && !d->has_residual && d->x_wpitch == 0 && d->x_cstride % 8 == 0 && d->x_coff % 8 == 0 && x_bytes < (1ull << 31)) {
     p.x_bytes = (unsigned)x_bytes;
     {
-      // the matrix-pipe form (12 x 16 output tiles, input streamed once): FT_CONV_PFLOW_MFMA=0 keeps the dot-product kernel
-      static const bool no_mfma = getenv("FT_CONV_PFLOW_MFMA") && atoi(getenv("FT_CONV_PFLOW_MFMA")) == 0;
+      // the matrix-pipe form (12 x 16 output tiles, input streamed once) where it applies; else the dot-product kernel
       const int nchunks = ceil_div(g.cin_groups, 4);                 // 32-channel chunks
       const int ty = ceil_div(d->Ho, 12), tx = ceil_div(d->Wo, 16);
       const size_t lds = (size_t)4 * 16384 + (size_t)nchunks * 2048;
-      if (!no_mfma && (long long)d->N * ty * tx >= 256 && lds <= 160 * 1024 &&
+      if ((long long)d->N * ty * tx >= 256 && lds <= 160 * 1024 &&
           (long long)ty * 12 * tx * 16 * 100 <= (long long)d->Ho * d->Wo * 125) {     // ragged edges waste < 25 % of the tiles
         p.h_ty = ty;
         p.h_tx = tx;

@@ -368,7 +368,7 @@ __global__ __launch_bounds__(256, 1) void correlation_mfma_rows_kernel(const hal
   // .. and the compiler has to know it: it cannot see the wait above, and with the products behind branches it kept "a[] may still be
   // in flight" alive at every join, i.e. s_waitcnt vmcnt(15) .. vmcnt(0) in front of the sixteen MFMAs of EVERY step — the last one
   // drains the whole queue (look-ahead ring rows and the band stores of the previous steps).  An empty asm that redefines the
-  // registers ends that (round 6; found in the ISA of the DIRECT form: 23 x sixteen descending waits).
+  // registers ends that (round 6; found in the ISA of correlation_mfma_rows64_kernel: 23 x sixteen descending waits).
 #pragma unroll
   for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -427,19 +427,18 @@ __global__ __launch_bounds__(256, 1) void correlation_mfma_rows_kernel(const hal
 }
 
 // ---- the rows kernel for maps up to 64 pixels wide ---------------------------------------------------------------------
-// Shipped form (STAGED = false, NRS = 2): 64-column ring slots, EIGHT waves — R = 4 output rows per workgroup, the upper
-// two owned by waves 4..7 with their own f1 fragments on the same ring — and the rows kernel's 2-byte band stores:
-// 61.9-63.5 us at [16,256,48,64] against 65.6-67.3 for the 104-column, four-wave rows kernel (same box).
-// The STAGED form below was the attempt to get rid of the 1008 two-byte stores per lane; it is correct and slower:
-// At W <= 64 (FlowNetC at 512x384: 48 x 64) only 64 of the 104 window columns of an f2 row exist, so a ring slot shrinks
-// from 52 to 32 KiB (window columns outside the image read one shared zero row) and the 64 KiB that frees hold a TRANSPOSE
-// tile per output row: the band products of GD = 8 consecutive dy displacements are written (ds_write_b16, band lanes
-// only) into [64 pixels][8 x 21] fp16 = 336 contiguous, 16-byte-aligned bytes of each pixel's 441-channel run, and leave
-// as whole 16-byte pieces (21 per pixel) when the group is complete: ~50 b128 stores per thread instead of 1008 two-byte
-// stores per lane, at the price of one extra barrier per flush (9 per workgroup).  The last group holds 5 x 21 values =
-// 210 bytes: thirteen pieces and one 2-byte store.  Same MFMA order and fp32 -> fp16 step as the rows kernel.
-// Every step waits with vmcnt(NL): loads return in order among loads, so "at most NL vector-memory operations in flight"
-// means row jj has landed whatever the stores of the previous flush are doing.
+// At W <= 64 (FlowNetC at 512x384: 48 x 64) only 64 of the 104 window columns of an f2 row exist, so a ring slot shrinks from 52
+// to 32 KiB and four of them fit.  The MFMA tile's columns are the IMAGE columns of one parity (32 of them) instead of two
+// 32-column halves of the 104-column window: half the MFMAs and half the band store instructions per (f2 row, output row).
+// The band of f1 pixel i then is f2 pixel i2 = i + dxi - DRAD in [0, 32); the displacements that fall off the image (i2 < 0 or
+// >= 32: structural zeros) are written by the lanes of the columns i2 mod 32, which are out of band for that row: every lane slot
+// with (c - i + DRAD) mod 32 < D stores, a real product where the difference did not wrap, zero where it did.  Six waves =
+// R = 3 output rows x 2 column parities, one row per wave (256 workgroups at 16 x 48 rows): 50.2-51.2 us at [16,256,48,64]
+// against 65.6-67.3 for the 104-column, four-wave rows kernel (same box).  Window-column tiles with four or eight waves, an
+// eight-wave R = 4 form of this one, a transposed band and bands staged through LDS were all tried and were slower, as were three
+// rewrites of the band's way out: profiles/HISTORY.md ("Retired A/B switches").  Ablations of this kernel (FT_CORR_DBG, same box):
+// full 54.2 us; no band store instructions 37.5 (stores kept but all out of range: 40.8 of 50.2); also no MFMAs 27.2; also no
+// fragment reads 26.9; also no ring loads 20.4; also no barriers 17.7 (launch + the f1 fragments + 23 empty steps).
 template <int N, int I = 0, typename F>
 __device__ __forceinline__ void corr_unroll(F&& f) {
   if constexpr (I < N) {
@@ -448,63 +447,34 @@ __device__ __forceinline__ void corr_unroll(F&& f) {
   }
 }
 
-// STAGED = false keeps the rows kernel's 2-byte band stores (and its store-counting waits) on the narrow ring: measured at
-// [16,256,48,64], the transpose costs more in ds_write_b16 issue than it saves in stores (75 us staged; 86 us with a branch
-// per band register instead of the scratch-slot select; 63.5 us unstaged with four waves, 62 us with eight).  Pulling the f2
-// window straight into registers instead of through the ring (each wave uses its own 32 window pixels) was also tried with
-// the staged band: 87 us.
-// NRS = 2: eight waves, the second four take the upper half of the R output rows with their own f1 fragments and read the
-// same ring: two waves per SIMD, one's band stores issue while the other's products run on the matrix pipe.
-typedef uint32_t corr_u2_t __attribute__((ext_vector_type(2)));
-// TR (round 4): the products TRANSPOSED — f2 window columns as the MFMA's rows, f1 pixels as its columns — so that a lane owns ONE
-// output pixel and its accumulator registers walk the displacement axis: the four registers of a group are four CONSECUTIVE
-// x-displacements = 8 contiguous output bytes.  A group that lies wholly inside the band leaves as one 8-byte store (2-byte
-// aligned: the 441-channel rows have no better alignment), a group cut by the band's end as up to three 2-byte stores: 7.5 lane
-// stores per pixel and y-displacement on average instead of 21 — the kernel is bound by the issue of scattered lane stores.
-// DIRECT (round 4, second form): the tile's columns are the IMAGE columns of this parity (32 of them at W <= 64) instead of two
-// 32-column halves of the 104-column window — half the MFMAs and half the band store instructions per (f2 row, output row).
-// The band of f1 pixel i then is f2 pixel i2 = i + dxi - DRAD in [0, 32); the displacements that fall off the image
-// (i2 < 0 or >= 32: structural zeros the window form produced from its zero columns) are written by the lanes of the
-// columns i2 mod 32, which are out of band for that row: every lane slot with (c - i + DRAD) mod 32 < D stores, a real product
-// where the difference did not wrap, zero where it did.  NWV waves = NWV / 2 output rows x 2 column parities, one row per wave
-// (six waves / R = 3 give 256 workgroups at 16 x 48 rows, eight / R = 4 give 192).  62.4 -> 50.2-51.2 us at [16,256,48,64] (same box).
-// Ablations of this form (FT_CORR_DBG, same box): full 54.2 us; no band store instructions 37.5 (stores kept but all out of range:
-// 40.8 of 50.2); also no MFMAs 27.2; also no fragment reads 26.9; also no ring loads 20.4; also no barriers 17.7 (launch + the f1
-// fragments + 23 empty steps).  Three rewrites of the band's way out, each correct, none faster: (a) pairs of lanes packed into
-// aligned 4-byte stores (ds_bpermute for the neighbour, the odd element carried to the next dy): 70.0 us; (b) the band through
-// wave-private LDS tiles [32 px][8 dy x 21 dx] and out as 16-byte pieces (30 store instructions per wave instead of 336): 51.2-
-// 51.7 us — so it is neither the address unit's instruction rate nor the 2-byte granularity; (c) the epilogue of step jj - 1
-// woven between the MFMAs of step jj (one store per MFMA in the ISA): 56.8-57.9 vs 54.8-55.3 us.  What a step costs is spread
-// over products, epilogue ALU work, stores and the ring, none of them alone; (a)-(c) were removed again.
-template <int KS, int R, int DRAD, bool STAGED, int NRS, bool TR = false, bool DIRECT = false, int NWV = 4 * NRS>
-__global__ __launch_bounds__(64 * NWV, 1) void correlation_mfma_rows64_kernel(const half_t* __restrict__ f1, const half_t* __restrict__ f2,
-                                                                          half_t* __restrict__ y, int H, int W, unsigned f2_bytes,
-                                                                          unsigned y_bytes, int f_cstride, int y_cstride, int y_coff,
-                                                                          int act, float slope, int ngy) {
+constexpr int kCorr64Waves = 6;
+template <int KS, int R, int DRAD>
+__global__ __launch_bounds__(64 * kCorr64Waves, 1) void correlation_mfma_rows64_kernel(const half_t* __restrict__ f1, const half_t* __restrict__ f2,
+                                                                                   half_t* __restrict__ y, int H, int W, unsigned f2_bytes,
+                                                                                   unsigned y_bytes, int f_cstride, int y_cstride, int y_coff,
+                                                                                   int act, float slope, int ngy) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  constexpr int NWV = kCorr64Waves;
   constexpr int C = KS * 16, ROWB = C * 2;
-  constexpr int D = 2 * DRAD + 1, WROWS = 64 + 4 * DRAD;
+  constexpr int D = 2 * DRAD + 1;
   constexpr int NJ = R + 2 * DRAD;          // f2 rows of the class this workgroup walks
-  constexpr int NSETS = DIRECT ? NWV / 2 : NRS;   // row sets among the waves
+  constexpr int NSETS = NWV / 2;            // row sets among the waves: each a pair of waves, one per column parity
   constexpr int RW = R / NSETS;             // output rows per wave
   constexpr int SLOT = 64 * ROWB, NL = (SLOT / 1024 + NWV - 1) / NWV;   // wave-loads per wave and ring row (the last ones may fall behind the slot: scratch)
-  static_assert(R % NSETS == 0 && (NRS == 1 || !STAGED) && !(DIRECT && (STAGED || TR)) && (!DIRECT || D <= 32) && NWV % 2 == 0, "row sets");
-  // DIRECT: four ring slots, rows issued THREE steps ahead.  vmcnt counts loads and stores in one queue, in order, so "row jj has
+  static_assert(R % NSETS == 0 && D <= 32 && NWV % 2 == 0, "row sets");
+  // Four ring slots, rows issued THREE steps ahead.  vmcnt counts loads and stores in one queue, in order, so "row jj has
   // landed" can only be asked as "everything older than the ops issued after it is done"; at distance three the stores of three
   // steps may still be in flight (vmcnt(2 NL + 48) <= 63).  Measured: no gain over distance two (52.0 vs 51.6 us) — the store
   // round trip is not what a step waits for; kept because it costs nothing.
-  constexpr int DEPTH = DIRECT ? 3 : 2, NSLOT = DEPTH + 1;
-  constexpr int ZROW = NSLOT * SLOT, STG = ZROW + ROWB;
-  constexpr int GD = 8;
-  constexpr int PROW = GD * D * 2;          // bytes of a pixel's run per group
-  constexpr int TILE = 64 * PROW;           // the transpose tile of one output row
-  constexpr int DUMMY = STG + R * TILE;     // 128 bytes: where the lanes outside the band write
-  static_assert(PROW % 16 == 0 && (!STAGED || DUMMY + 128 <= 160 * 1024) && ROWB == 512 && (DIRECT || NL * NWV * 1024 == SLOT), "shape");
+  constexpr int DEPTH = 3, NSLOT = DEPTH + 1;
+  constexpr int ZROW = NSLOT * SLOT;        // one zero row behind the ring: operand B of the columns outside the image
+  constexpr int SPILL = ZROW + ROWB + 128;  // 1 KiB behind it: where the wave-loads past the end of a slot land
+  static_assert(ROWB == 512, "shape");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef __attribute__((address_space(3))) void* lds_ptr;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int par = wave & 1, jt = DIRECT ? 0 : (wave >> 1) & 1, rs = DIRECT ? wave >> 1 : wave >> 2;
+  const int par = wave & 1, rs = wave >> 1;  // column parity and row set of this wave
   const int c = lane & 31, h = lane >> 5;
   int n, q, i0;
   {
@@ -519,10 +489,10 @@ __global__ __launch_bounds__(64 * NWV, 1) void correlation_mfma_rows64_kernel(co
   const int Hq = (H - q + 1) >> 1;          // rows of this parity class
   const float inv_c = 1.0f / (float)C;
   constexpr unsigned kOOB = 0x80000000u;
-  // developer ablation (FT_CORR_DBG, DIRECT form, timing only): 1 = every band store out of range, 2 = no MFMAs, 4 = no fragment
+  // developer ablation (FT_CORR_DBG, timing only): 1 = every band store out of range, 2 = no MFMAs, 4 = no fragment
   // reads, 8 = no ring loads, 16 = no barriers, 32 = no band store instructions at all; 0 in production
-  const int cdbg = DIRECT ? act >> 8 : 0;
-  if constexpr (DIRECT) act &= 0xff;
+  const int cdbg = act >> 8;
+  act &= 0xff;
 
   // f1 fragments of the R rows (operand A: row = f1 pixel of this column parity, k = channel)
   uint4_t a[RW][KS];
@@ -537,17 +507,15 @@ __global__ __launch_bounds__(64 * NWV, 1) void correlation_mfma_rows64_kernel(co
       for (int s = 0; s < KS; ++s) a[r][s] = __builtin_amdgcn_raw_buffer_load_b128(rsrc1, voff, s * 32, 0);
     }
   }
-  // operand B: column = window pixel 64*jt + 2*c + par = image column x2 (ring row x2), the zero row outside the image
-  int wr = 64 * jt + 2 * c + par;
-  wr = wr < WROWS ? wr : WROWS - 1;
-  const int x2 = DIRECT ? 2 * c + par : wr - 2 * DRAD;
+  // operand B: column = image column x2 = 2*c + par (ring row x2), the zero row outside the image
+  const int x2 = 2 * c + par;
   const bool in_img = (unsigned)x2 < (unsigned)W;
-  const int b_base = in_img ? x2 * ROWB : ZROW - 0;      // slot-relative for image columns; ZROW is absolute (see b_abs)
+  const int b_base = in_img ? x2 * ROWB : ZROW;          // slot-relative for image columns; ZROW is absolute
   const int b_key = in_img ? (x2 >> 1) & 15 : 0;
 
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<half_t*>(f2), 0, f2_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(y, 0, y_bytes, 0x00020000);
-  // loader lanes: wave-load i = t*4 + wave covers ring rows 2i, 2i+1; XOR swizzle on the source chunk
+  // loader lanes: wave-load i = t*NWV + wave covers ring rows 2i, 2i+1; XOR swizzle on the source chunk
   unsigned l_voff[NL];
 #pragma unroll
   for (int t = 0; t < NL; ++t) {
@@ -565,46 +533,39 @@ __global__ __launch_bounds__(64 * NWV, 1) void correlation_mfma_rows64_kernel(co
 #pragma unroll
     for (int t = 0; t < NL; ++t)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)(t * NWV + wave < SLOT / 1024 ? smem + slot * SLOT + (t * NWV + wave) * 1024
-                                                                                           : smem + STG + 128), 16,
+                                                                                           : smem + SPILL), 16,
                                                row_ok ? l_voff[t] : kOOB, soff, 0, 0);
   };
-  // band lanes: accumulator register g of lane (c, h) = f1 pixel rr = G(g) + 4h (of this column parity) x window column c
-  // -> displacement index dxi = c + 32*jt - rr, kept when 0 <= dxi < D and the pixel lies inside the image
-  const int dxi0 = DIRECT ? c - 4 * h + DRAD : c + 32 * jt - 4 * h;
-  const int lane_base = STG + (8 * h + par) * PROW + dxi0 * 2;     // byte of (pixel 2*(4h) + par, dxi0) of tile 0
-  int vmask = 0, realmask = 0;       // DIRECT: stores / stores that carry a product (the others are the off-image zeros)
+  // band lanes: accumulator register g of lane (c, h) = f1 pixel rr = G(g) + 4h (of this column parity) x image column c
+  // -> displacement index dxi = (c - rr + DRAD) mod 32, stored when < D and the pixel lies inside the image
+  const int dxi0 = c - 4 * h + DRAD;
+  int vmask = 0, realmask = 0;       // stores / stores that carry a product (the others are the off-image zeros)
 #pragma unroll
   for (int g = 0; g < 16; ++g) {
     const int G = (g & 3) + 8 * (g >> 2);
-    const int dr = dxi0 - G, dd = DIRECT ? dr & 31 : dr;
+    const int dr = dxi0 - G, dd = dr & 31;
     if ((unsigned)dd < (unsigned)D && 2 * (G + 4 * h) + par < W) vmask |= 1 << g;
     if (dd == dr) realmask |= 1 << g;
   }
   // act(v) = max(v, s*v) for s in [0, 1] (relu: 0, leaky: slope, none: 1); the 1/C of the correlation rides along
   const float k_pos = inv_c, k_neg = inv_c * (act == FT_ACT_RELU ? 0.f : (act == FT_ACT_LEAKY ? slope : 1.f));
   const int yrow_bytes = W * y_cstride * 2;
-  unsigned s_voff[(STAGED || TR) ? 1 : 16];      // !STAGED: the band leaves as 2-byte stores in the accumulator layout
-  // TR: lane (c, h) = f1 pixel x = 2c + par; register 4 gq + e = window column 8 gq + 4 h + e of this half: displacement index
-  // dxi = 32 jt + 8 gq + 4 h + e - c.  t_base = byte offset of (pixel, dxi of gq = e = 0); group gq / element e ride in the
-  // instruction's immediate offset.
-  const int t_dxi0 = 32 * jt + 4 * h - c;
-  const bool t_px = 2 * c + par < W;
-  const unsigned t_base = (unsigned)((((n * H) * W + 2 * c + par) * y_cstride + y_coff + t_dxi0) * 2);
-  if constexpr (!STAGED && !TR) {
+  unsigned s_voff[16];                       // the band leaves as 2-byte stores in the accumulator layout
+  // (px0 as a sum of its own on purpose: hipcc's schedule of the WHOLE kernel changes with the way this address is associated,
+  // profiles/HISTORY.md "Checks of this change"; run tools/dev/isa_diff.py after touching it)
+  const int px0 = (n * H) * W + par;         // pixel (row 0, column par) of image n
 #pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      const int G = (g & 3) + 8 * (g >> 2);
-      const int x = 2 * (G + 4 * h) + par;
-      const int dd = DIRECT ? (dxi0 - G) & 31 : dxi0 - G;
-      s_voff[g] = (((vmask >> g) & 1) && !(cdbg & 1)) ? (unsigned)(((n * H) * W + x) * y_cstride + y_coff + dd) * 2u : kOOB;
-    }
+  for (int g = 0; g < 16; ++g) {
+    const int G = (g & 3) + 8 * (g >> 2);
+    const int dd = (dxi0 - G) & 31;
+    s_voff[g] = (((vmask >> g) & 1) && !(cdbg & 1)) ? (unsigned)((px0 + 2 * (G + 4 * h)) * y_cstride + y_coff + dd) * 2u : kOOB;
   }
 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the f1 fragments sit in registers before the ring starts counting ..
   // .. and the compiler has to know it: it cannot see the wait above, and with the products behind branches it kept "a[] may still be
   // in flight" alive at every join, i.e. s_waitcnt vmcnt(15) .. vmcnt(0) in front of the sixteen MFMAs of EVERY step — the last one
   // drains the whole queue (look-ahead ring rows and the band stores of the previous steps).  An empty asm that redefines the
-  // registers ends that (round 6; found in the ISA of the DIRECT form: 23 x sixteen descending waits).
+  // registers ends that (round 6; found in the ISA: 23 x sixteen descending waits).
 #pragma unroll
   for (int r = 0; r < RW; ++r)
 #pragma unroll
@@ -614,11 +575,8 @@ __global__ __launch_bounds__(64 * NWV, 1) void correlation_mfma_rows64_kernel(co
   corr_unroll<NJ>([&](auto jc) {
     constexpr int jj = decltype(jc)::value;
     constexpr int slot = jj % NSLOT;
-    // row jj has landed (this wave's share).  !STAGED: behind it row jj+1 and the 16*R band stores of the previous step may fly
-    // (DIRECT: rows jj+1, jj+2 and the stores of up to three steps)
-    if constexpr (DIRECT) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((DEPTH - 1) * NL + 16 * RW * (jj < DEPTH ? jj : DEPTH)) : "memory");
-    else if constexpr (STAGED || jj == 0) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NL) : "memory");
-    else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(NL + (TR ? 20 : 16) * RW) : "memory");
+    // row jj has landed (this wave's share): behind it rows jj+1, jj+2 and the 16 band stores per row of up to three steps may fly
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"((DEPTH - 1) * NL + 16 * RW * (jj < DEPTH ? jj : DEPTH)) : "memory");
     if (!(cdbg & 16)) asm volatile("s_barrier" ::: "memory");   // everyone's has; everyone is done reading the slot refilled now
     issue(jj + DEPTH, (jj + DEPTH) % NSLOT);
     const int j = i0 - DRAD + jj;
@@ -634,121 +592,36 @@ __global__ __launch_bounds__(64 * NWV, 1) void correlation_mfma_rows64_kernel(co
     }
     corr_unroll<RW>([&](auto rc) {
       constexpr int rw = decltype(rc)::value;
-      constexpr int r = rw;                              // STAGED (NRS = 1): the row itself
-      constexpr int dyi = jj - r;                        // f2 row j is displacement dyi - DRAD of output row i0 + r
-      if constexpr (!STAGED) {
-        // the rows kernel's form: always 16 stores per (step, row) so that the waits can count them
-        const int r = rs * RW + rw;                      // wave-uniform
-        const int dyi = jj - r;
-        const bool live = dyi >= 0 && dyi < D && i0 + r < Hq;
-        if constexpr (TR) {
-          // always 4 x (one 8-byte + four 2-byte) stores per (step, row), most of them out of range, so that the waits can count
-          if (live) {
-            float16_t acc;
+      // always 16 stores per (step, row) so that the waits can count them
+      const int r = rs * RW + rw;                        // wave-uniform
+      const int dyi = jj - r;                            // f2 row j is displacement dyi - DRAD of output row i0 + r
+      const bool live = dyi >= 0 && dyi < D && i0 + r < Hq;
+      if (live) {
+        float16_t acc;
 #pragma unroll
-            for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-            if (row_ok) {
+        for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+        if (row_ok && !(cdbg & 2)) {
 #pragma unroll
-              for (int s = 0; s < KS; ++s)
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, b[s]), __builtin_bit_cast(half8_t, a[rw][s]), acc, 0, 0, 0);
-            }
-            const int soff = (2 * (i0 + r) + q) * yrow_bytes + dyi * D * 2;
-            corr_unroll<4>([&](auto gc) {
-              constexpr int gq = decltype(gc)::value;
-              const int d0 = t_dxi0 + 8 * gq;                          // displacement index of element 0
-              const bool full = t_px && d0 >= 0 && d0 + 3 < D;
-              half_t hv[4];
+          for (int s = 0; s < KS; ++s)
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, a[rw][s]), __builtin_bit_cast(half8_t, b[s]), acc, 0, 0, 0);
+        }
+        const int soff = (2 * (i0 + r) + q) * yrow_bytes + dyi * D * 2;
+        if (cdbg & 32) {
+          float keep = 0.f;
 #pragma unroll
-              for (int e = 0; e < 4; ++e) hv[e] = (half_t)__builtin_fmaxf(acc[4 * gq + e] * k_pos, acc[4 * gq + e] * k_neg);
-              const half4_t h4 = {hv[0], hv[1], hv[2], hv[3]};
-              __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(corr_u2_t, h4), rsrc_y, full ? t_base + 16 * gq : kOOB, soff, 0);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                const bool one = t_px && !full && (unsigned)(d0 + e) < (unsigned)D;
-                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, hv[e]), rsrc_y, one ? t_base + 16 * gq + 2 * e : kOOB, soff, 0);
-              }
-            });
-          } else {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              __builtin_amdgcn_raw_buffer_store_b64(corr_u2_t{0u, 0u}, rsrc_y, kOOB, 0, 0);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)0, rsrc_y, kOOB, 0, 0);
-            }
-          }
-        } else if (live) {
-          float16_t acc;
-#pragma unroll
-          for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-          if (row_ok && !(cdbg & 2)) {
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-              acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, a[rw][s]), __builtin_bit_cast(half8_t, b[s]), acc, 0, 0, 0);
-          }
-          const int soff = (2 * (i0 + r) + q) * yrow_bytes + dyi * D * 2;
-          if (cdbg & 32) {
-            float keep = 0.f;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) keep += acc[g];
-            if (keep == 12345.678f) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)1, rsrc_y, s_voff[0], soff, 0);
-          } else {
+          for (int g = 0; g < 16; ++g) keep += acc[g];
+          if (keep == 12345.678f) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)1, rsrc_y, s_voff[0], soff, 0);
+        } else {
 #pragma unroll
           for (int g = 0; g < 16; ++g) {
             half_t hv = (half_t)__builtin_fmaxf(acc[g] * k_pos, acc[g] * k_neg);
-            if constexpr (DIRECT) hv = ((realmask >> g) & 1) ? hv : (half_t)0.f;
+            hv = ((realmask >> g) & 1) ? hv : (half_t)0.f;   // the off-image displacements: zeros
             __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, hv), rsrc_y, s_voff[g], soff, 0);
           }
-          }
-        } else if (!(cdbg & 32)) {
-#pragma unroll
-          for (int g = 0; g < 16; ++g) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)0, rsrc_y, kOOB, 0, 0);
         }
-      } else if constexpr (dyi >= 0 && dyi < D) {
-        if (i0 + r < Hq) {                               // workgroup-uniform
-          constexpr int gg = dyi / GD, dslot = dyi % GD;
-          float16_t acc;
+      } else if (!(cdbg & 32)) {
 #pragma unroll
-          for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-          if (row_ok) {
-#pragma unroll
-            for (int s = 0; s < KS; ++s)
-              acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, a[r][s]), __builtin_bit_cast(half8_t, b[s]), acc, 0, 0, 0);
-          }
-          char* tile = smem + r * TILE + dslot * D * 2 + lane_base;
-#pragma unroll
-          for (int g = 0; g < 16; ++g) {
-            const int G = (g & 3) + 8 * (g >> 2);
-            const float v = __builtin_fmaxf(acc[g] * k_pos, acc[g] * k_neg);   // act(v / C), slopes in [0, 1]
-            // lanes outside the band write a scratch slot behind the tiles: straight-line code (a branch per register would
-            // fence the next product's MFMAs off from these writes)
-            char* dst = ((vmask >> g) & 1) ? tile + G * (2 * PROW - 2) : smem + DUMMY + lane * 2;
-            *reinterpret_cast<half_t*>(dst) = (half_t)v;
-          }
-          constexpr bool last_of_group = dslot == GD - 1 || dyi == D - 1;
-          if constexpr (last_of_group) {
-            constexpr int gbytes = (dyi == D - 1 ? D - gg * GD : GD) * D * 2;   // bytes of the group per pixel
-            constexpr int npc = gbytes / 16, tail = gbytes % 16;                 // whole 16-byte pieces, bytes behind them
-            static_assert(tail == 0 || tail == 2, "tail");
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            asm volatile("s_barrier" ::: "memory");         // every wave's band writes of this group sit in the tile
-            const char* src = smem + STG + r * TILE;
-            const int soff = (2 * (i0 + r) + q) * yrow_bytes + (y_coff + gg * GD * D) * 2;
-#pragma unroll
-            for (int k = 0; k < (64 * npc + 255) / 256; ++k) {
-              const int idx = tid + 256 * k;
-              const int px = idx / npc, pc = idx - px * npc;
-              const uint4_t v = *reinterpret_cast<const uint4_t*>(src + (px < 64 ? px : 63) * PROW + pc * 16);
-              const unsigned vo = (px < 64 && px < W) ? (unsigned)((((n * H) * W + px) * y_cstride) * 2 + pc * 16) : kOOB;
-              __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_y, vo + (unsigned)soff, 0, FT_YSTORE_BUF_AUX);
-            }
-            if constexpr (tail == 2) {
-              const int px = tid;
-              const unsigned short v = px < 64 ? *reinterpret_cast<const unsigned short*>(src + px * PROW + npc * 16) : (unsigned short)0;
-              const unsigned vo = (px < 64 && px < W) ? (unsigned)((((n * H) * W + px) * y_cstride) * 2 + npc * 16) : kOOB;
-              __builtin_amdgcn_raw_buffer_store_b16(v, rsrc_y, vo, soff, 0);
-            }
-          }
-        }
+        for (int g = 0; g < 16; ++g) __builtin_amdgcn_raw_buffer_store_b16((unsigned short)0, rsrc_y, kOOB, 0, 0);
       }
     });
   });
@@ -845,16 +718,16 @@ __global__ __launch_bounds__(256) void resample2d_pair_kernel(const float* __res
 // in their own lines (12 requests per pixel at C = 3), 38 M requests per launch at configs[3] shapes.  Here a workgroup owns a
 // 16 x 64 tile of output pixels (4 per thread): it reads the tile's flow once, reduces the bounding box of every tap the tile
 // touches (clamped indices, so the box is inside the image), loads that window of in1 — all C planes — into LDS with
-// row-contiguous, fully coalesced 4-byte-per-lane loads, and serves the four taps of every pixel from LDS.  A tile whose
-// window does not fit the LDS budget (a flow field with > ~20 px of spread inside 16 x 64 pixels) takes the direct gathers of
-// resample2d_pair_kernel for that tile only (workgroup-uniform branch).  Same weights, same order of the four products as
+// row-contiguous, fully coalesced loads (LDS-DMA), and serves the four taps of every pixel from LDS.  A tile whose box does not
+// fit the LDS budget keeps a window CLIPPED around its own pixels: per pixel, taps that lie inside the window come from LDS and
+// the pixels with a tap outside it gather theirs from memory as 8-byte pairs (see `window` / `inw` below); only a field that
+// spreads over more than four such windows skips the window altogether.  Same weights, same order of the four products as
 // Resample2d_kernel.cu:42-59 restated above: results are bit-identical to the gather kernels.
 constexpr int kRsTH = 16, kRsTW = 64, kRsPPT = 4;          // tile rows / columns, pixels per thread
 #ifndef FT_RS_CLIP_PITCH
 #define FT_RS_CLIP_PITCH 96
 #endif
 constexpr int kRsClipPitch = FT_RS_CLIP_PITCH;                           // row pitch (floats) of a window clipped around its tile: 16 + 2 x 8 rows x 64 + 2 x 15 columns at the default budget
-constexpr int kRsMaxWindow = 6656;                         // window floats per plane (row pitch x rows): 3 planes x 26 KiB = 78 KiB, two workgroups per CU
 
 template <int C>
 __global__ __launch_bounds__(256) void resample2d_window_kernel(const float* __restrict__ in1, const float* __restrict__ flow,
@@ -1112,12 +985,6 @@ template <> __device__ __forceinline__ void st8<float>(float* p, const float (&v
   reinterpret_cast<float4_t*>(p)[1] = b;
 }
 
-#ifndef FT_WARP_STORE_SC1
-#define FT_WARP_STORE_SC1 0
-#endif
-#ifndef FT_WARP_STORE_LINES
-#define FT_WARP_STORE_LINES 1     // fp16 output: whole-line stores after a lane exchange (-DFT_WARP_STORE_LINES=0: round 4's two strided pieces)
-#endif
 template <typename T>
 __global__ __launch_bounds__(256) void flow_warp_concat_kernel(const T* __restrict__ x6, const float* __restrict__ flow,
                                                                float div_flow, T* __restrict__ y, int H, int W, int xl,
@@ -1164,7 +1031,6 @@ __global__ __launch_bounds__(256) void flow_warp_concat_kernel(const T* __restri
       lo[0] = c[0]; lo[1] = c[1]; lo[2] = c[2]; lo[3] = c[3]; lo[4] = c[4]; lo[5] = c[5]; lo[6] = warp[0]; lo[7] = warp[1];
       hi[0] = warp[2]; hi[1] = dx / div_flow; hi[2] = dy / div_flow; hi[3] = sqrtf(nrm);
     }
-#if FT_WARP_STORE_LINES
     if constexpr (std::is_same<T, half_t>::value) {
       // A pixel's 32 output bytes leave as two 16-byte pieces; written straight from the pixel's lane a wave's store touches
       // every other 16 bytes of 2 KB (half of 16 lines, twice).  Round 5: the lanes trade pieces first (ds_bpermute), so that
@@ -1187,19 +1053,13 @@ __global__ __launch_bounds__(256) void flow_warp_concat_kernel(const T* __restri
             b[e] = (unsigned)__shfl((int)vh[e], src);
           }
           const uint4_t v = (lane & 1) ? b : a;
-#if FT_WARP_STORE_SC1
-          store_out16(y + (wave_first + 32 * sidx) * 16 + lane * 8, v);
-#else
           *reinterpret_cast<uint4_t*>(y + (wave_first + 32 * sidx) * 16 + lane * 8) = v;
-#endif
         }
       } else {
         *reinterpret_cast<uint4_t*>(y + i * 16) = vl;
         *reinterpret_cast<uint4_t*>(y + i * 16 + 8) = vh;
       }
-    } else
-#endif
-    {
+    } else {
       st8<T>(y + i * 16, lo);
       st8<T>(y + i * 16 + 8, hi);
     }
@@ -1675,26 +1535,12 @@ extern "C" int ft_correlation_nhwc_fwd(const void* f1, const void* f2, void* y, 
       f_bytes < (1ull << 31)) {
     const int drad = max_displacement / 2;
     const unsigned long long y_bytes = (unsigned long long)B * H * W * y_cstride * 2;
-    static const bool no_rows = getenv("FT_CORR_ROWS") && atoi(getenv("FT_CORR_ROWS")) == 0;   // dev A/B: one row per workgroup
-    static const bool no_t = getenv("FT_CORR_NARROW") && atoi(getenv("FT_CORR_NARROW")) == 0;   // dev A/B: the 104-column ring
-    if (drad == 10 && y_bytes < (1ull << 31) && !no_rows && !no_t && W <= 64 && y_coff % 8 == 0 && y_cstride % 8 == 0) {
-      // FlowNetC's shape on maps up to 64 wide: 64-column ring slots (FT_CORR_STAGED=1: band transposed through LDS)
-      static const bool stg = getenv("FT_CORR_STAGED") && atoi(getenv("FT_CORR_STAGED")) == 1;   // dev A/B: band through LDS
-      static const bool w8 = !(getenv("FT_CORR_WAVES") && atoi(getenv("FT_CORR_WAVES")) == 4);     // dev A/B: four waves, R = 3
-      static const bool tr = getenv("FT_CORR_TR") && atoi(getenv("FT_CORR_TR")) == 1;               // dev A/B: 1 = the transposed band (slower)
-      static const bool direct = !(getenv("FT_CORR_DIRECT") && atoi(getenv("FT_CORR_DIRECT")) == 0);   // dev A/B: 0 = the window-column tiles
-      static const int dwaves = getenv("FT_CORR_DIRECT_WAVES") ? atoi(getenv("FT_CORR_DIRECT_WAVES")) : 6;   // dev A/B: 8 = R 4 (192 workgroups at 16 x 48 rows)
-      static const int cdbg = getenv("FT_CORR_DBG") ? atoi(getenv("FT_CORR_DBG")) : 0;               // dev ablation (DIRECT form): 1 = no band stores, 2 = no MFMAs
-      const bool dir = direct && !stg && w8 && !tr;
-      const bool d6 = dir && dwaves == 6;
-      const int R = (stg || !w8 || d6) ? 3 : 4;
-      auto k = stg ? correlation_mfma_rows64_kernel<16, 3, 10, true, 1>
-                   : (w8 ? (tr ? correlation_mfma_rows64_kernel<16, 4, 10, false, 2, true>
-                               : (d6 ? correlation_mfma_rows64_kernel<16, 3, 10, false, 2, false, true, 6>
-                                     : (direct ? correlation_mfma_rows64_kernel<16, 4, 10, false, 2, false, true>
-                                               : correlation_mfma_rows64_kernel<16, 4, 10, false, 2>)))
-                         : correlation_mfma_rows64_kernel<16, 3, 10, false, 1>);
-      const size_t ldst = dir ? 4 * 64 * 512 + 512 + 128 + 1024 : 3 * 64 * 512 + 512 + 3 * 64 * (8 * 21 * 2) + 128;
+    if (drad == 10 && y_bytes < (1ull << 31) && W <= 64 && y_coff % 8 == 0 && y_cstride % 8 == 0) {
+      // FlowNetC's shape on maps up to 64 wide: 64-column ring slots, six waves, 3 output rows per workgroup
+      static const int cdbg = ft::dev_env_int("FT_CORR_DBG", 0);   // dev ablation, timing only: see the kernel
+      constexpr int R = 3;
+      auto k = correlation_mfma_rows64_kernel<16, R, 10>;
+      constexpr size_t ldst = 4 * 64 * 512 + 512 + 128 + 1024;     // ring, zero row, pad, scratch KiB
       static bool raised[64] = {};
       int dev = 0;
       FT_HIP_CHECK(hipGetDevice(&dev));
@@ -1703,13 +1549,13 @@ extern "C" int ft_correlation_nhwc_fwd(const void* f1, const void* f2, void* y, 
         if (dev >= 0 && dev < 64) raised[dev] = true;
       }
       const int ngy = 2 * ceil_div((H + 1) / 2, R);
-      hipLaunchKernelGGL(k, dim3(ngy * B), dim3(d6 ? 384 : ((!stg && w8) ? 512 : 256)), ldst, as_stream(stream), static_cast<const half_t*>(f1),
+      hipLaunchKernelGGL(k, dim3(ngy * B), dim3(64 * kCorr64Waves), ldst, as_stream(stream), static_cast<const half_t*>(f1),
                          static_cast<const half_t*>(f2), static_cast<half_t*>(y), H, W, (unsigned)f_bytes, (unsigned)y_bytes,
-                         f_cstride, y_cstride, y_coff, act | (dir ? cdbg << 8 : 0), slope, ngy);
+                         f_cstride, y_cstride, y_coff, act | (cdbg << 8), slope, ngy);
       FT_LAUNCH_CHECK("correlation_mfma_rows64_kernel");
       return FT_OK;
     }
-    if (drad == 10 && y_bytes < (1ull << 31) && !no_rows) {     // FlowNetC's shape: 3 output rows per workgroup
+    if (drad == 10 && y_bytes < (1ull << 31)) {     // FlowNetC's shape: 3 output rows per workgroup
       constexpr int R = 3;
       auto k = correlation_mfma_rows_kernel<16, R, 10>;
       constexpr size_t lds3 = 3 * (((size_t)(64 + 40) * 512 + 1023) / 1024 * 1024);
@@ -1765,31 +1611,20 @@ extern "C" int ft_resample2d_fwd(const float* in1, const float* flow, float* out
                                  ft_stream_t stream) {
   if (!in1 || !flow || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0) return FT_ERR_INVALID_ARG;
   const size_t total = (size_t)B * H * W;
-  static const bool no_window = getenv("FT_RESAMPLE_WINDOW") && atoi(getenv("FT_RESAMPLE_WINDOW")) == 0;   // dev A/B: the gather kernels
   const unsigned long long in_bytes = (unsigned long long)B * C * H * W * 4ull;
-  if (!no_window && C >= 1 && C <= 4 && W >= 2 && in_bytes < (1ull << 31)) {
+  if (C >= 1 && C <= 4 && W >= 2 && in_bytes < (1ull << 31)) {
     const int tiles_x = ceil_div(W, kRsTW), tiles_y = ceil_div(H, kRsTH);
     const long long nblk = (long long)B * tiles_x * tiles_y;
     if (nblk <= 0x7fffffffLL) {
       const dim3 grid((unsigned)nblk);
       // window budget per plane (floats): the LDS a workgroup reserves = C x budget x 4 bytes decides how many workgroups share a CU
-      // (26 KiB per plane: two; 9 KiB: five); tiles whose window exceeds it take the pair gathers.  FT_RESAMPLE_WBUDGET (dev A/B)
-      // Round 5, same box, configs[3] shapes (noise = per-pixel N(0, 4 px) flows, smooth = a 12 x 16 grid of N(0, 6 px) vectors upsampled):
-      //   budget 6656 (26 KiB per plane, 2 workgroups per CU): noise 45.5 us, smooth 39.7 us
-      //   budget 3328 (13 KiB, 4 per CU):                      noise 56.4 us (every tile falls back), smooth 32.3 us
-      //   budget 2304 / 1536:                                   noise 55.8 / 55.1, smooth 35.6 / 37.0
-      // Flow fields that reach this operator are network outputs (smooth): 3328 was the default of round 5.
-      // Round 6 (clipped windows: a tile whose box does not fit keeps a window around itself and gathers only the pixels outside it),
-      // same box, noise / smooth: budget 1536: 45.2 / 32.0 us, 1792: 37.5 / 29.9, 2048: 37.0 / 30.0, 2304: 36.3 / 29.4,
-      // 2560: 35.3 / 29.4 (five workgroups per CU), 2816: 37.4 / 31.3, 3072: 36.8 / 31.9, 4096: 38.8 / 33.0, 6656: 47.2 / 40.2;
-      // clip pitch 80 / 96 / 112 / 128 floats at 2560: 34.0 / 34.8-35.0 / 34.8 / 34.6 us noise, 28.0-28.7 smooth.  2560 is the default.
-      static const int wb_env = getenv("FT_RESAMPLE_WBUDGET") ? atoi(getenv("FT_RESAMPLE_WBUDGET")) : 0;
-      const int wbudget = wb_env >= 256 && wb_env <= kRsMaxWindow ? (wb_env & ~255) : 2560;
+      // (26 KiB per plane: two; 10 KiB: five); tiles whose window exceeds it keep a clipped window and gather the rest.  Budgets
+      // from 1536 to 6656 floats were timed on noise and smooth flows: profiles/HISTORY.md ("Retired A/B switches").
+      constexpr int wbudget = 2560;
       const size_t lds = (size_t)C * wbudget * sizeof(float);
 #define FT_RS_LAUNCH(CC)                                                                                                   \
   {                                                                                                                        \
     auto kw = resample2d_window_kernel<CC>;                                                                                \
-    if (lds > 64 * 1024) FT_RAISE_LDS(kw, 112 * 1024);                                                                     \
     hipLaunchKernelGGL(kw, grid, dim3(256), lds, as_stream(stream), in1, flow, out, H, W, tiles_x, tiles_y, (unsigned)in_bytes, wbudget); \
   }
       switch (C) {
@@ -1803,8 +1638,7 @@ extern "C" int ft_resample2d_fwd(const float* in1, const float* flow, float* out
       return FT_OK;
     }
   }
-  static const bool no_pair = getenv("FT_RESAMPLE_PAIR") && atoi(getenv("FT_RESAMPLE_PAIR")) == 0;   // dev A/B
-  if (!no_pair && W >= 2 && C >= 1 && C <= 4 && (long long)H * W < (1LL << 31)) {
+  if (W >= 2 && C >= 1 && C <= 4 && (long long)H * W < (1LL << 31)) {
     const dim3 grid(grid_for(total));
     switch (C) {
       case 1: hipLaunchKernelGGL(resample2d_pair_kernel<1>, grid, dim3(256), 0, as_stream(stream), in1, flow, out, H, W, total); break;

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "flowtrack_hip.h"
 
@@ -35,6 +36,13 @@ int record_hip_error(hipError_t e, const char* what);
       if (_dev >= 0 && _dev < 64) _raised[_dev] = true;                                                          \
     }                                                                                                            \
   } while (0)
+
+// The one way a developer switch ("Developer switches") reaches the library: FT_* in the environment as an integer,
+// `fallback` when unset.  Callers decide whether it is read once (static) or per call.
+static inline int dev_env_int(const char* name, int fallback) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : fallback;
+}
 
 static inline hipStream_t as_stream(ft_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
@@ -71,25 +79,13 @@ __device__ __forceinline__ float act_mul(float v, float k) {
 // v_pk_fma_f32 / v_pk_add_f32 are the same IEEE operations as the scalar forms, and ReLU commutes with the rounding to fp16
 // (monotonic, sign-preserving): the same values as `(half_t)fmaxf(a * k + b, 0.f)`; a negative result that rounds to -0 comes out
 // as a zero of either sign.
-// (FT_PK_EPILOGUE=0: the scalar forms, A/B builds: tools/dev/build_variant.sh nopk -DFT_PK_EPILOGUE=0)
-#ifndef FT_PK_EPILOGUE
-#define FT_PK_EPILOGUE 1
-#endif
 __device__ __forceinline__ half2_t bn_relu_pk(float a0, float a1, float k0, float k1, float b0, float b1) {
-#if FT_PK_EPILOGUE
   const float2_t v = __builtin_elementwise_fma(float2_t{a0, a1}, float2_t{k0, k1}, float2_t{b0, b1});
   return __builtin_elementwise_max(__builtin_convertvector(v, half2_t), half2_t{(half_t)0.f, (half_t)0.f});
-#else
-  return half2_t{(half_t)__builtin_fmaxf(a0 * k0 + b0, 0.f), (half_t)__builtin_fmaxf(a1 * k1 + b1, 0.f)};
-#endif
 }
 __device__ __forceinline__ half2_t bn_res_relu_pk(float a0, float a1, float k0, float k1, float b0, float b1, half_t r0, half_t r1) {
-#if FT_PK_EPILOGUE
   const float2_t v = __builtin_elementwise_fma(float2_t{a0, a1}, float2_t{k0, k1}, float2_t{b0, b1}) + __builtin_convertvector(half2_t{r0, r1}, float2_t);
   return __builtin_elementwise_max(__builtin_convertvector(v, half2_t), half2_t{(half_t)0.f, (half_t)0.f});
-#else
-  return half2_t{(half_t)__builtin_fmaxf(a0 * k0 + b0 + (float)r0, 0.f), (half_t)__builtin_fmaxf(a1 * k1 + b1 + (float)r1, 0.f)};
-#endif
 }
 // the sixteen results of a 32 x 32 accumulator block of one lane (register r: scale / shift [r >> 2][r & 3]) as two 16-byte halves
 __device__ __forceinline__ void bn_relu_acc16(const float16_t& acc, const float4_t (&sc)[4], const float4_t (&sh)[4], half8_t (&h8)[2]) {

@@ -554,3 +554,39 @@ def test_folded_bottleneck_operands_reproduce_batchnorm():
     bn_big = dict(bn, bias=bn["bias"].clone())
     bn_big["bias"][3] = 1.0e5
     assert hip_ops._fold_representable((conv,)) and not hip_ops._fold_representable((types.SimpleNamespace(cout=co, _weight=w, _bias=None, _bn=bn_big),))
+
+
+def test_developer_switch_table_matches_the_sources():
+    """DESIGN.md's "Developer switches" table lists every FT_* switch that is read, and nothing that is not.
+
+    Read = a string passed to getenv / ft::dev_env_int under csrc/, a name taken from os.environ in flowtrack/pytorch_amd/, or (for
+    the table's build-time rows) a name the native sources or the public header test with the preprocessor."""
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    section = design[design.index("## Appendix: Developer switches"):]
+    table = set(re.findall(r"^\| `(FT_[A-Z0-9_]+)` \|", section, flags=re.M))
+    assert len(table) > 40, "table not parsed"
+    pkg = os.path.join(ROOT, "flowtrack", "pytorch_amd")
+    csrc = os.path.join(pkg, "csrc")
+    native_env, build_time, python_env = set(), set(), set()
+    for name in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, name)).read()
+        for fn, arg in re.findall(r"\b(getenv|dev_env_int)\(\s*([^,)]*)", text):
+            if arg.strip() in ("const char* name", "name"):
+                continue                                             # ft::dev_env_int itself (ft_common.h)
+            m = re.fullmatch(r'"(FT_[A-Z0-9_]+)"', arg.strip())
+            assert m, f"{name}: {fn}({arg}...: the environment is read through a literal FT_* name only"
+            native_env.add(m.group(1))
+        build_time |= set(re.findall(r"^\s*#\s*(?:ifndef|ifdef|if|elif)\b.*?\b(FT_[A-Z0-9_]+)", text, flags=re.M))
+        build_time |= set(re.findall(r"defined\((FT_[A-Z0-9_]+)\)", text))
+    header = open(os.path.join(ROOT, "include", "flowtrack_hip.h")).read()
+    build_time |= set(re.findall(r"^\s*#\s*(?:ifndef|ifdef)\s+(FT_[A-Z0-9_]+)", header, flags=re.M)) - {"FLOWTRACK_HIP_H", "FT_API"}
+    for dirpath, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py"):
+                text = open(os.path.join(dirpath, f)).read()
+                python_env |= set(re.findall(r"""environ(?:\.get)?\s*[\[(]\s*["'](FT_[A-Z0-9_]+)["']""", text))
+    assert native_env and python_env
+    missing = (native_env | python_env) - table
+    assert not missing, f"read from the environment but not in DESIGN.md's table: {sorted(missing)}"
+    stale = table - (native_env | python_env | build_time)
+    assert not stale, f"in DESIGN.md's table but no longer read: {sorted(stale)}"
