@@ -855,11 +855,16 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
   };
   // order of every wave's (in-order) load queue: x chunk 0, the weights of step 0, the L2 touch, the tables / shift pairs, x chunks 1
   // and 2, the weights of steps 1 .. D-1
+  // (the first wait counts them: compiler fences on both sides of the touch / table group, so that the count does not rest on one
+  // compiler build's schedule)
   issue_x(0, 0);
   load_a(std::integral_constant<int, 0>{}, 0);
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
   issue_touch();
   load_tables();
   asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
   issue_x(1, 1);
   issue_x(2, 2);
   bns_unroll<D - 1>([&](auto sc) { load_a(std::integral_constant<int, decltype(sc)::value + 1>{}, decltype(sc)::value + 1); });
@@ -1307,6 +1312,460 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
 #endif
 }
 
+// ---- 256 planes, 16-pixel MFMA tiles (weights straight to registers, folded operands, four waves) ----------------------------
+// The full-width-strip form of bottleneck_stream_direct_kernel<3, 2, false, NS, 0, 4, true> on v_mfma_f32_16x16x32_f16: the R50
+// layer3 strip is 4 x 12 = 48 output pixels on a 6 x 12 = 72-pixel halo, which the 32-pixel tiles of the direct kernel run as 64
+// and 96 (a quarter of every phase multiplies zero rows).  With 16-pixel tiles the strip is 3 tiles and its halo 5 (80): per wave
+// 4 channel tiles x {5, 3, 3} pixel tiles x {32, 72, 32} K32 steps x 16 cycles = 30.7 k MFMA cycles instead of 40.8 k.
+// Same plan as the direct kernel: x-chunk ring -> T1 -> T2 in LDS, the wave's weight fragments of a 64-wide K step (8 x 1 KiB,
+// two K32 slices x four channel tiles) straight to registers NS - 1 steps ahead, L2 touch behind x chunk 0, wave-private output
+// staging.  Fragment maps (lane l, p = l & 15, h = l >> 4):
+//   A (weights)  row p of a 16-channel tile, k = 8 h .. 8 h + 7 of the K32 slice.  Row r of tile t of a wave is channel
+//                16 (r >> 2) + 4 t + (r & 3) of the wave's 64 (bns_pack16_kernel), so that
+//   C / D        pixel p, rows 4 h + reg: the lane's 4 tiles x 4 registers are the 16 CONSECUTIVE channels 16 h + 4 t + reg: T1 / T2 /
+//                the output leave as two 16-byte pieces per lane and pixel tile, the residual arrives as two.
+//   B (pixels)   pixel p, the same k: one ds_read_b128 at 16-byte piece h (+ 4 for the odd slice) of the pixel's 128 bytes of the
+//                chunk; the sixteen lanes of a piece read sixteen consecutive rows, which BNS_XKEY (x chunks: two rows per bank row)
+//                and row & 15 (T1 / T2: 512-byte rows) spread over all banks.
+//   shift        one MFMA per tile: A row = {hi, lo, 0 ..} in the lanes with h = 0, B = ones at k = 0, 1.
+//   residual     one MFMA per tile: B = the lane's residual piece t >> 1 (channels 16 h + 8 (t >> 1) + e as k = 8 h + e), A = the 0/1 matrix
+//                with row 4 h' + reg at k = 8 h' + 4 (t & 1) + reg (two matrices, by t & 1).
+template <int NS>
+__global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const BnsParams p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr int P = 256;
+  using G = BnsGeom<P>;
+  constexpr int NC1 = G::NC1, KC = G::KC, WSTEP = G::WSTEP, ROWB = G::ROWB;
+  constexpr int G2 = NC1, G3 = G2 + 9 * KC, GEND = G3 + 4 * KC;
+  constexpr int CT = 4, MT1 = 5, MT2 = 3, NT = 256;             // channel tiles per wave, halo / output pixel tiles of 16
+  constexpr int LX = (MT1 * 2 + 3) / 4;                         // x-chunk wave loads (8 rows each) per wave
+  constexpr int NOUT = MT2 * 16;
+  constexpr int ZROW = 61440, TOUCH = 77824, STG = 81920, STGB = 4 * NOUT * 128;
+  static_assert(LX * 4 * 8 * 128 <= G::XSTRIDE && MT1 * 16 * ROWB <= ZROW && STG + 2 * STGB <= 163840, "LDS map");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  typedef __attribute__((address_space(3))) void* lds_ptr;
+  using c0 = std::integral_constant<int, 0>;
+  using c1 = std::integral_constant<int, 1>;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, lq = lane >> 4;
+
+  int logical;
+  {
+    const int b = blockIdx.x;
+    const int q = p.total >> 3, r = p.total & 7, xcd = b & 7, loc = b >> 3;
+    logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+  }
+  const int n = logical / p.ppi;
+  const int W = p.W;
+  const int y0 = (logical - n * p.ppi) * p.TH;
+  const int rows_out = p.H - y0 < p.TH ? p.H - y0 : p.TH;
+  const int npix_out = rows_out * W;
+  const int npix_halo = (p.TH + 2) * W;
+  const int iy0 = y0 - 1;
+
+  const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.x), 0, p.x_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.ws), 0, p.ws_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.tab), 0, (2 * P + G::C) * 4, 0x00020000);
+  constexpr unsigned kOOB = 0x80000000u;
+
+  unsigned x_voff[LX];
+#pragma unroll
+  for (int t = 0; t < LX; ++t) {
+    const int hp = (t * 4 + wave) * 8 + (lane >> 3);
+    const int hr = hp / W, hc = hp - hr * W;
+    const int iy = iy0 + hr;
+    unsigned v = kOOB;
+    if (hp < npix_halo && (unsigned)iy < (unsigned)p.H)
+      v = (unsigned)((((n * p.H + iy) * W + hc) * p.x_cstride + p.x_coff) * 2 + (((lane & 7) ^ BNS_XKEY(hp)) << 4));
+    x_voff[t] = v;
+  }
+  const unsigned lane16 = (unsigned)lane * 16u;
+  auto issue_x = [&](int c, int buf) {
+    char* dst = smem + buf * G::XSTRIDE;
+#pragma unroll
+    for (int t = 0; t < LX; ++t)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (lds_ptr)(dst + (t * 4 + wave) * 1024), 16, x_voff[t], c * 128, 0, 0);
+  };
+  // the weight fragments of step g for this wave: (slice ks, tile 4 * wave + t) at g * WSTEP + (ks * 16 + 4 * wave + t) KiB
+  static_assert(NS >= 3 && 12 % NS == 0, "ring phase of the unrolled phase-2 body (12 steps per kernel row)");
+  constexpr int D = NS - 1;
+  uint4_t areg[NS][2][CT];
+  auto load_a_slice = [&](auto slotc, int g, auto ksc) {   // past the end of the stream: out of range, zeros, never multiplied
+    constexpr int SL = decltype(slotc)::value, ks = decltype(ksc)::value;
+#pragma unroll
+    for (int t = 0; t < CT; ++t)
+      areg[SL][ks][t] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, lane16, g * WSTEP + (ks * 16 + CT * wave + t) * 1024, 0);
+  };
+  auto load_a = [&](auto slotc, int g) {
+    load_a_slice(slotc, g, c0{});
+    load_a_slice(slotc, g, c1{});
+  };
+  unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  BNSD_TS(0);
+  // the L2 touch of the direct kernel: exactly kTouch loads per thread, behind x chunk 0 and the weights of step 0
+  constexpr int kTouch = 6;
+  auto issue_touch = [&]() {
+    const bool on = blockIdx.x < 256 && !(p.dbg & 512);
+    const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
+    const int first = p.total < 256 ? p.total : 256;
+    const int nloc = (first - xcd + 7) >> 3;                       // workgroups of the first round on this XCD
+    const unsigned lines = (p.ws_bytes + 127u) >> 7;
+    const unsigned per = (lines + nloc - 1) / nloc;
+    const unsigned lo = loc * per, hi = lo + per < lines ? lo + per : lines;
+#pragma unroll
+    for (int k = 0; k < kTouch; ++k) {
+      const unsigned l = lo + tid + (unsigned)(NT * k);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (lds_ptr)(smem + TOUCH + wave * 256), 4, (on && l < hi) ? l << 7 : kOOB, 0, 0, 0);
+    }
+  };
+  // the shift pair of MFMA row l15 of every (epilogue, channel tile) of this wave (lanes 16..63 hold k = 8..31 of the shift slice: zeros,
+  // fetched out of range; those of phase 3 are fetched behind phase 1, where its registers are free), and the two 0/1 matrices of the
+  // residual MFMAs
+  unsigned shp[6][CT];
+  uint4_t permA[2];
+  const uint4_t onesB = uint4_t{0x3C003C00u, 0u, 0u, 0u};
+  {
+    const bool on = lq == (l15 >> 2);
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+      const int pe = 4 * o + (l15 & 3);
+      unsigned w[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) w[k] = (on && (pe >> 1) == k) ? (0x3C00u << (16 * (pe & 1))) : 0u;
+      permA[o] = uint4_t{w[0], w[1], w[2], w[3]};
+    }
+  }
+  constexpr int kTabLoads = 2 * CT;
+  auto load_tables = [&](int e0, int e1) {
+    const unsigned so = lq == 0 ? 4u * (unsigned)(16 * (l15 >> 2) + (l15 & 3)) : kOOB;
+#pragma unroll
+    for (int e = e0; e < e1; ++e)
+#pragma unroll
+      for (int t = 0; t < CT; ++t)
+        shp[e][t] = __builtin_amdgcn_raw_buffer_load_b32(rsrc_t, so, 4 * (e * P + 64 * wave + 4 * t), 0);
+  };
+  auto add_shift = [&](int e, auto& A, auto mtc) {      // A[t][j] += shift of epilogue e (one MFMA per tile)
+    constexpr int MT = decltype(mtc)::value;
+#pragma unroll
+    for (int t = 0; t < CT; ++t) {
+      const uint4_t sa = uint4_t{shp[e][t], 0u, 0u, 0u};
+#pragma unroll
+      for (int j = 0; j < MT; ++j)
+        A[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, sa), __builtin_bit_cast(half8_t, onesB), A[t][j], 0, 0, 0);
+    }
+  };
+  // order of every wave's (in-order) load queue: x chunk 0, the weights of step 0, the L2 touch, the shift pairs, x chunks 1 and 2,
+  // the weights of steps 1 .. D-1.  The first wait below counts them: nothing may move across the touch / shift-pair group.
+  issue_x(0, 0);
+  load_a(c0{}, 0);
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  issue_touch();
+  load_tables(0, 2);
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  issue_x(1, 1);
+  issue_x(2, 2);
+  bns_unroll<D - 1>([&](auto sc) { load_a(std::integral_constant<int, decltype(sc)::value + 1>{}, decltype(sc)::value + 1); });
+  if (tid < ROWB / 16) *reinterpret_cast<uint4_t*>(smem + ZROW + tid * 16) = uint4_t{0u, 0u, 0u, 0u};
+
+  uint4_t res[4][MT2][2];
+  int m_out[MT2], hp_out[MT2];          // output pixel of the lane in tile j, and its index in the halo strip
+#pragma unroll
+  for (int j = 0; j < MT2; ++j) {
+    m_out[j] = j * 16 + l15;
+    hp_out[j] = m_out[j] + W;
+  }
+
+  // ================= phase 1 ============================================================================================
+  float4_t acc1[CT][MT1];
+#pragma unroll
+  for (int t = 0; t < CT; ++t)
+#pragma unroll
+    for (int j = 0; j < MT1; ++j) acc1[t][j] = float4_t{0.f, 0.f, 0.f, 0.f};
+  int b1_off[MT1];
+#pragma unroll
+  for (int j = 0; j < MT1; ++j) {
+    const int hp = j * 16 + l15;
+    b1_off[j] = hp * 128 + ((lq ^ BNS_XKEY(hp)) << 4);
+  }
+  {
+    uint4_t fx[2][MT1];
+    auto ldx = [&](auto setc, int buf, int ks) {
+      constexpr int S = decltype(setc)::value;
+      const char* xb = smem + buf * G::XSTRIDE;
+#pragma unroll
+      for (int j = 0; j < MT1; ++j) fx[S][j] = *reinterpret_cast<const uint4_t*>(xb + (b1_off[j] ^ (ks << 6)));
+    };
+    auto mma1 = [&](auto setc, auto slotc, auto ksc) {
+      constexpr int S = decltype(setc)::value, SL = decltype(slotc)::value, ks = decltype(ksc)::value;
+#pragma unroll
+      for (int j = 0; j < MT1; ++j)
+#pragma unroll
+        for (int t = 0; t < CT; ++t)
+          acc1[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, areg[SL][ks][t]),
+                                                              __builtin_bit_cast(half8_t, fx[S][j]), acc1[t][j], 0, 0, 0);
+    };
+    // x chunk 0 has landed (this wave's share): behind it the touch, the shift pairs, chunks 1, 2 and D weight steps may fly
+    static_assert(2 * LX + 2 * CT * D + kTouch + kTabLoads <= 63, "vmcnt immediate");
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * LX + 2 * CT * D + kTouch + kTabLoads) : "memory");
+    BNS_BARRIER();
+    BNSD_TS(7);             // start-up: x chunk 0 of every wave has landed
+    ldx(c0{}, 0, 0);
+    bns_unroll<NC1>([&](auto cc) {
+      constexpr int c = decltype(cc)::value;
+      constexpr int buf = c % 3;
+      using slot = std::integral_constant<int, c % NS>;
+      using nslot = std::integral_constant<int, (c + D) % NS>;
+      // The wave-uniform branch below (residual pick-up) splits the chunk into two scheduling regions, each with one slice's weight
+      // loads of step c + D.  Region 1: [x chunk c+2 DMA, slice-0 reads of this chunk, slice 1 of chunk c-1] (behind the last
+      // barrier) + slice 0 of this chunk: one LDS read or one weight load behind every two MFMAs.
+      load_a_slice(nslot{}, c + D, c0{});
+      ldx(c1{}, buf, 1);
+      mma1(c0{}, slot{}, c0{});
+      __builtin_amdgcn_sched_group_barrier(0x020, LX, 0);
+      bns_unroll<MT1>([&](auto) {
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      });
+      bns_unroll<CT>([&](auto) {
+        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      });
+      __builtin_amdgcn_sched_group_barrier(0x008, CT * MT1 - 2 * MT1 - 2 * CT, 0);
+      bns_unroll<MT1>([&](auto) {
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      });
+      if (c % 4 == wave) {  // this chunk holds the channels of this wave for quarter c / 4: the lane's own 16 channels, two pieces
+        constexpr int q = c / 4;
+        const char* xb = smem + buf * G::XSTRIDE;
+#pragma unroll
+        for (int j = 0; j < MT2; ++j) {
+          const int hp = hp_out[j];
+          const char* rowp = xb + hp * 128;
+#pragma unroll
+          for (int h = 0; h < 2; ++h)
+            res[q][j][h] = *reinterpret_cast<const uint4_t*>(rowp + (((2 * lq + h) ^ BNS_XKEY(hp)) << 4));
+        }
+      }
+      load_a_slice(nslot{}, c + D, c1{});
+      if constexpr (c + 1 < NC1) {
+        // x chunk c+1 has landed and every read of chunk c's buffer is complete: refill it with chunk c+3.  Younger than x chunk
+        // c+1 are the weights of steps c+D-1 and c+D and x chunk c+2 (the weights of step c+1 are older: D >= 2 steps ahead)
+        if constexpr (c + 2 < NC1) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(LX + 4 * CT) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(4 * CT) : "memory");
+        BNS_BARRIER();
+        if constexpr (c + 3 < NC1) issue_x(c + 3, buf);
+        ldx(c0{}, (c + 1) % 3, 0);
+      }
+      mma1(c1{}, slot{}, c1{});
+    });
+  }
+  BNSD_TS(1);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  BNS_BARRIER();          // every wave is past its last x-chunk read: the x buffers become T1
+  // the lane's 16 consecutive channels of pixel tile j as two 16-byte pieces: fp16(relu(acc))
+  auto pieces = [&](auto& A, int j, half8_t (&h8)[2]) {
+    h8[0] = relu_acc4x2(A[0][j], A[1][j]);
+    h8[1] = relu_acc4x2(A[2][j], A[3][j]);
+  };
+  {
+    add_shift(0, acc1, std::integral_constant<int, MT1>{});
+#pragma unroll
+    for (int j = 0; j < MT1; ++j) {
+      const int hp = j * 16 + l15;
+      const int iy = iy0 + hp / W;
+      const bool inside = (unsigned)iy < (unsigned)p.H;
+      half8_t h8[2];
+      pieces(acc1, j, h8);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        uint4_t u = __builtin_bit_cast(uint4_t, h8[h]);
+        u.x = inside ? u.x : 0u; u.y = inside ? u.y : 0u; u.z = inside ? u.z : 0u; u.w = inside ? u.w : 0u;
+        h8[h] = __builtin_bit_cast(half8_t, u);
+      }
+      if (hp < npix_halo) {
+        char* rowp = smem + hp * ROWB;
+        const int cb = wave * 8 + 2 * lq;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) *reinterpret_cast<half8_t*>(rowp + (((cb + h) ^ (hp & 15)) << 4)) = h8[h];
+      }
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  BNS_BARRIER();          // T1 complete
+  BNSD_TS(2);
+  load_tables(2, 6);
+
+  // ================= phases 2 + 3 =======================================================================================
+  float4_t acc[CT][MT2];
+  auto zero_acc = [&]() {
+#pragma unroll
+    for (int t = 0; t < CT; ++t)
+#pragma unroll
+      for (int j = 0; j < MT2; ++j) acc[t][j] = float4_t{0.f, 0.f, 0.f, 0.f};
+  };
+  zero_acc();
+  int edge[MT2];
+#pragma unroll
+  for (int j = 0; j < MT2; ++j) {
+    const int ox = m_out[j] % W;
+    edge[j] = (ox == 0 ? 1 : 0) | (ox == W - 1 ? 2 : 0);
+  }
+  // T1 / T2 row of the pixel operand: `off` relative to the lane's own row; the two x-border taps (bad) read the zero row
+  auto row_bases = [&](int off, int kc, int bad, int (&rb)[MT2]) {
+#pragma unroll
+    for (int j = 0; j < MT2; ++j) {
+      const int row = m_out[j] + off;
+      const int v = row * ROWB + (((row & 15) ^ lq) << 4);
+      rb[j] = ((edge[j] & bad) ? ZROW + (lq << 4) : v) ^ (kc << 7);
+    }
+  };
+  uint4_t fb[2][MT2];
+  auto ldb = [&](auto setc, int ks, const int (&rb)[MT2]) {
+    constexpr int S = decltype(setc)::value;
+#pragma unroll
+    for (int j = 0; j < MT2; ++j) fb[S][j] = *reinterpret_cast<const uint4_t*>(smem + (rb[j] ^ (ks << 6)));
+  };
+  auto mma2 = [&](auto setc, auto slotc, auto ksc) {
+    constexpr int S = decltype(setc)::value, SL = decltype(slotc)::value, ks = decltype(ksc)::value;
+#pragma unroll
+    for (int j = 0; j < MT2; ++j)
+#pragma unroll
+      for (int t = 0; t < CT; ++t)
+        acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, areg[SL][ks][t]),
+                                                           __builtin_bit_cast(half8_t, fb[S][j]), acc[t][j], 0, 0, 0);
+  };
+  // one weight step g (ring slot SL): slice 0 of the pixel operand already sits in register set 0; `rbn` = row bases of the next step.
+  // Issue order: an LDS read, three MFMAs, a weight load — eight times (a buffer_load_b128 holds the wave's issue port for ~40 cycles;
+  // clustered as hipcc places them, the matrix pipe drains behind them)
+  auto dstep = [&](auto slotc, int g, const int (&rb)[MT2], bool has_next, const int (&rbn)[MT2]) {
+    constexpr int SL = decltype(slotc)::value;
+    using slot = std::integral_constant<int, SL>;
+    load_a(std::integral_constant<int, (SL + D) % NS>{}, g + D);
+    ldb(c1{}, 1, rb);
+    mma2(c0{}, slot{}, c0{});
+    if (has_next) ldb(c0{}, 0, rbn);
+    mma2(c1{}, slot{}, c1{});
+    bns_unroll<8>([&](auto ic) {
+      constexpr int i = decltype(ic)::value;
+      __builtin_amdgcn_sched_group_barrier(0x100, (i & 3) < MT2 ? 1 : 0, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, CT * MT2 / 4, 0);
+      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+    });
+  };
+
+  // ---- phase 2: nine taps x KC chunks, three taps per loop trip (12 steps: a multiple of the register ring period) -------
+  {
+    static_assert((3 * KC) % NS == 0, "ring phase of the unrolled body");
+    int rb[MT2], rbn[MT2];
+    row_bases(-1, 0, 1, rb);
+    ldb(c0{}, 0, rb);
+    for (int ky = 0; ky < 3; ++ky) {
+      bns_unroll<3 * KC>([&](auto sc) {
+        constexpr int s = decltype(sc)::value;
+        constexpr int kx = s / KC, kc = s % KC;
+        constexpr int nkc = (kc + 1) % KC, nkx = kc + 1 == KC ? (kx + 1) % 3 : kx;
+        const int nky = (kc + 1 == KC && kx == 2) ? ky + 1 : ky;
+        row_bases(nky * W + nkx - 1, nkc, nkx == 0 ? 1 : (nkx == 2 ? 2 : 0), rbn);
+        // (the last step's look-ahead read lands inside LDS and is never multiplied: no branch in the step)
+        dstep(std::integral_constant<int, (G2 + s) % NS>{}, G2 + 3 * KC * ky + s, rb, true, rbn);
+#pragma unroll
+        for (int j = 0; j < MT2; ++j) rb[j] = rbn[j];
+      });
+    }
+  }
+  BNSD_TS(3);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  BNS_BARRIER();          // every wave is past its last T1 read: T2 overwrites T1
+  {
+    add_shift(1, acc, std::integral_constant<int, MT2>{});
+#pragma unroll
+    for (int j = 0; j < MT2; ++j) {
+      const int m = m_out[j];
+      half8_t h8[2];
+      pieces(acc, j, h8);
+      char* rowp = smem + m * ROWB;
+      const int cb = wave * 8 + 2 * lq;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) *reinterpret_cast<half8_t*>(rowp + (((cb + h) ^ (m & 15)) << 4)) = h8[h];
+    }
+  }
+  zero_acc();
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  BNS_BARRIER();          // T2 complete
+  BNSD_TS(4);
+
+  // ---- phase 3: four quarters of P output channels; a quarter leaves through one of the wave's two private staging tiles ----------
+  {
+    // the wave's own [NOUT pixels][128 bytes = its 64 channels of the quarter] tile, 16-byte piece c of pixel m at piece c ^ (m & 7);
+    // read-out: lane -> pixel lane / 8 + 8 k, piece lane % 8 (whole 128-byte lines per pixel)
+    constexpr int NSTG = NOUT / 8;
+    unsigned s_voff[NSTG];
+    int s_off[NSTG];
+#pragma unroll
+    for (int k = 0; k < NSTG; ++k) {
+      const int m = (lane >> 3) + 8 * k, ch = lane & 7;
+      s_voff[k] = m < npix_out ? (unsigned)((((n * p.H + y0) * W + m) * p.y_cstride + p.y_coff + wave * 64 + ch * 8) * 2) : kOOB;
+      s_off[k] = wave * (NOUT * 128) + m * 128 + ((ch ^ (m & 7)) << 4);
+    }
+    int rb[MT2], rbn[MT2];
+    row_bases(0, 0, 0, rb);
+    ldb(c0{}, 0, rb);
+    bns_unroll<4>([&](auto qc) {
+      constexpr int q = decltype(qc)::value;
+      bns_unroll<KC>([&](auto kcc) {
+        constexpr int kc = decltype(kcc)::value;
+        constexpr int g = G3 + q * KC + kc;
+        row_bases(0, (kc + 1) % KC, 0, rbn);
+        dstep(std::integral_constant<int, g % NS>{}, g, rb, g + 1 < GEND, rbn);
+#pragma unroll
+        for (int j = 0; j < MT2; ++j) rb[j] = rbn[j];
+      });
+      // shift3 of the quarter and the residual join every tile's accumulator as two MFMAs
+      add_shift(2 + q, acc, std::integral_constant<int, MT2>{});
+#pragma unroll
+      for (int t = 0; t < CT; ++t)
+#pragma unroll
+        for (int j = 0; j < MT2; ++j)
+          acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, permA[t & 1]),
+                                                             __builtin_bit_cast(half8_t, res[q][j][t >> 1]), acc[t][j], 0, 0, 0);
+      char* stg = smem + STG + (q & 1) * STGB + wave * (NOUT * 128);
+#pragma unroll
+      for (int j = 0; j < MT2; ++j) {
+        const int m = m_out[j];
+        half8_t h8[2];
+        pieces(acc, j, h8);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) *reinterpret_cast<half8_t*>(stg + m * 128 + (((2 * lq + h) ^ (m & 7)) << 4)) = h8[h];
+      }
+      zero_acc();
+      // wave-private pieces: a wave reads back only what it wrote itself, its LDS operations execute in order: no barrier, only a
+      // compiler fence (the read-out must stay behind the tile's writes in program order)
+      asm volatile("" ::: "memory");
+#pragma unroll
+      for (int k = 0; k < NSTG; ++k) {
+        const uint4_t v = *reinterpret_cast<const uint4_t*>(smem + STG + (q & 1) * STGB + s_off[k]);
+        if (!(p.dbg & 4)) __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_y, s_voff[k] + (unsigned)(q * P * 2), 0, FT_YSTORE_BUF_AUX);
+      }
+    });
+  }
+  if (p.dbg & 32) {
+    ts[5] = __builtin_amdgcn_s_memtime();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    ts[6] = __builtin_amdgcn_s_memtime();
+    if (tid == 0) {
+      unsigned long long* o = reinterpret_cast<unsigned long long*>(p.y + ((size_t)((n * p.H + y0) * W) * p.y_cstride + p.y_coff) * 2);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[i] = ts[i];
+    }
+  }
+#endif
+}
+
 // ---- weight stream packing -------------------------------------------------------------------------------------------
 // w1 [P][C], w2 [P][9P] (k = tap * P + ci), w3 [C][P]: the K-major layouts of ft_conv_pack_geometry.  One thread per
 // 16-byte piece of the stream: step g, slice kk, channel tile i, lane -> 8 consecutive k of one output channel.
@@ -1323,6 +1782,34 @@ __global__ __launch_bounds__(256) void bns_pack_kernel(const half_t* __restrict_
   const int l31 = lane & 31, lhi = lane >> 5;
   const int co_t = 32 * i + bns_sigma(l31);
   const int k_t = 16 * kk + 8 * lhi;
+  const half_t* src;
+  if (g < G::G2) {
+    src = w1 + (size_t)co_t * G::C + 64 * g + k_t;
+  } else if (g < G::G3) {
+    const int s = g - G::G2, tap = s / G::KC, kc = s - tap * G::KC;
+    src = w2 + (size_t)co_t * (9 * P) + tap * P + 64 * kc + k_t;
+  } else {
+    const int s = g - G::G3, q = s / G::KC, kc = s - q * G::KC;
+    src = w3 + (size_t)(q * P + co_t) * P + 64 * kc + k_t;
+  }
+  out[idx] = *reinterpret_cast<const uint4_t*>(src);
+}
+
+// The stream of bottleneck_stream_tile16_kernel (P = 256, layout 1): same steps of 64 k, a step = two K32 slices x sixteen 16-channel
+// tiles x 1 KiB; lane l of a fragment holds row l & 15, k = 8 (l >> 4) .. + 7 of the slice, row r of tile t = channel
+// 64 (t >> 2) + 16 (r >> 2) + 4 (t & 3) + (r & 3).  A wave's four tiles of a slice are 4 contiguous KiB.
+__global__ __launch_bounds__(256) void bns_pack16_kernel(const half_t* __restrict__ w1, const half_t* __restrict__ w2,
+                                                         const half_t* __restrict__ w3, uint4_t* __restrict__ out) {
+  using G = BnsGeom<256>;
+  constexpr int P = 256;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= G::GEND * G::WSTEP / 16) return;
+  const int lane = idx & 63, frag = idx >> 6;
+  const int g = frag >> 5, f = frag & 31;
+  const int ks = f >> 4, t = f & 15;
+  const int r = lane & 15;
+  const int co_t = 64 * (t >> 2) + 16 * (r >> 2) + 4 * (t & 3) + (r & 3);
+  const int k_t = 32 * ks + 8 * (lane >> 4);
   const half_t* src;
   if (g < G::G2) {
     src = w1 + (size_t)co_t * G::C + 64 * g + k_t;
@@ -1362,6 +1849,7 @@ __global__ __launch_bounds__(256) void bns_pack_head_kernel(const half_t* __rest
 
 struct BnsPlan {
   int variant;   // 0: <128,4,3>  1: <256,4,3>  2: <256,3,2>  3: <256,2,1> column-split (direct kernel only)  4: stride-2 head <4,1>
+                 // 5: <128,3,2>  6: 256 planes on 16-pixel tiles (bottleneck_stream_tile16_kernel; its own stream layout)
   int TH, ppi;
   int TWc, csplit;
 };
@@ -1399,7 +1887,7 @@ static int bns_plan(const ft_bottleneck_desc* d, BnsPlan* out) {
     th = th < d->H ? th : d->H;
     return ceil_div(d->H, ceil_div(d->H, th));     // same strip count, balanced rows
   };
-  const int force = dev_env_int("FT_BNS_VARIANT", -1);   // dev / tests: 1, 2 or 3 (read per call)
+  const int force = dev_env_int("FT_BNS_VARIANT", -1);   // dev / tests: 1, 2, 3 or 6 (read per call)
   if (d->P == 128) {
     // strips of <= 192 output pixels on <= 256 halo pixels (<128, 4, 3>), or of <= 128 on <= 192 (<128, 3, 2>, round 4) where the
     // large strips leave CUs idle: ResNet-101 at 384 x 288 with 16 crops per GPU has 160 large strips for 256 CUs (48 x 36 maps,
@@ -1432,8 +1920,10 @@ static int bns_plan(const ft_bottleneck_desc* d, BnsPlan* out) {
     xs = cs; x_tw = tw; x_th = ceil_div(d->H, ceil_div(d->H, th));
   }
   if (th_big < 1 && th_small < 1 && !xs) return FT_ERR_UNSUPPORTED;
+  // 16-pixel tiles: <= 48 output pixels on <= 80 halo pixels; folded operands and four waves only
+  const int th_16 = d->folded ? rows(48, 80) : 0;
   int pick;
-  if (force == 1 || force == 2 || (force == 3 && xs)) pick = force;
+  if (force == 1 || force == 2 || (force == 3 && xs) || (force == 6 && th_16 >= 1)) pick = force;
   else {
     // Both variants run one workgroup per CU at the matrix pipe's pace (the FT_BNS_DBG=64/128 ablation: same phase times
     // with every load out of range), so the cost of a launch is rounds of 256 workgroups x MFMAs per workgroup:
@@ -1447,13 +1937,25 @@ static int bns_plan(const ft_bottleneck_desc* d, BnsPlan* out) {
     else pick = cost(th_big, 4, 3) <= cost(th_small, 3, 2) ? 1 : 2;
     if (pick == 1 && th_big < 1) pick = 2;
     if (pick == 2 && th_small < 1) pick = th_big >= 1 ? 1 : 3;
+    long long cf = pick == 1 ? cost(th_big, 4, 3) : (pick == 2 ? cost(th_small, 3, 2) : -1);
+    // the 16-pixel tiles in the same unit (one 32-pixel tile of a pair of channel tiles for a K16 step = 64 MFMA cycles = two 16-pixel
+    // tiles of four channel tiles for half a K32 step): 5 halo and 3 output tiles count as 2.5 and 1.5.  Not under FT_BNS_WAVES=8
+    // (the eight-wave forms are 32-pixel kernels).
+    if (th_16 >= 1 && dev_env_int("FT_BNS_WAVES", 4) != 8) {
+      const long long wg = (long long)d->N * ceil_div(d->H, th_16);
+      const long long c16 = ((wg + 255) / 256) * (long long)(32 * 5 + 104 * 3);
+      if (cf < 0 || c16 < cf) { pick = 6; cf = c16; }
+    }
     if (xs && pick != 3) {
       // the column-split form only where it needs no more rounds of 256 workgroups than it saves in work per workgroup
       const long long wgx = (long long)d->N * ceil_div(d->H, x_th) * xs;
       const long long cx = ((wgx + 255) / 256) * (long long)(64 * 2 + 208 * 1);
-      const long long cf = pick == 1 ? cost(th_big, 4, 3) : cost(th_small, 3, 2);
       if (cx < cf) pick = 3;
     }
+  }
+  if (pick == 6) {
+    *out = BnsPlan{6, th_16, ceil_div(d->H, th_16), d->W, 1};
+    return FT_OK;
   }
   if (pick == 1 && th_big < 1) pick = 2;
   if (pick == 2 && th_small < 1) pick = th_big >= 1 ? 1 : 3;
@@ -1503,6 +2005,15 @@ static int bns_launch_direct(const BnsParams& p, hipStream_t s) {
   return FT_OK;
 }
 
+static int bns_launch_tile16(const BnsParams& p, hipStream_t s) {
+  auto k = bottleneck_stream_tile16_kernel<FT_BNS_SLOTS>;
+  constexpr int lds = 81920 + 2 * 4 * 48 * 128;
+  FT_RAISE_LDS(k, lds);
+  hipLaunchKernelGGL(k, dim3(p.total), dim3(256), lds, s, p);
+  FT_LAUNCH_CHECK("bottleneck_stream_tile16_kernel");
+  return FT_OK;
+}
+
 }  // namespace
 }  // namespace ft
 
@@ -1515,6 +2026,12 @@ extern "C" int ft_bottleneck_stream_folds(const ft_bottleneck_desc* d) {
   ft::BnsPlan pl;
   if (ft::bns_plan(d, &pl) != FT_OK) return 0;
   return pl.variant != 4;
+}
+
+extern "C" int ft_bottleneck_stream_layout(const ft_bottleneck_desc* d) {
+  ft::BnsPlan pl;
+  if (ft::bns_plan(d, &pl) != FT_OK) return -1;
+  return pl.variant == 6 ? 1 : 0;
 }
 
 extern "C" long long ft_bottleneck_stream_weight_bytes(const ft_bottleneck_desc* d) {
@@ -1542,6 +2059,9 @@ extern "C" int ft_bottleneck_stream_pack(const ft_bottleneck_desc* d, const void
   if (d->P == 128) {
     const int n16 = BnsGeom<128>::GEND * BnsGeom<128>::WSTEP / 16;
     hipLaunchKernelGGL(bns_pack_kernel<128>, dim3(ceil_div(n16, 256)), dim3(256), 0, s, a, b, c, static_cast<uint4_t*>(wstream));
+  } else if (pl.variant == 6) {
+    const int n16 = BnsGeom<256>::GEND * BnsGeom<256>::WSTEP / 16;
+    hipLaunchKernelGGL(bns_pack16_kernel, dim3(ceil_div(n16, 256)), dim3(256), 0, s, a, b, c, static_cast<uint4_t*>(wstream));
   } else {
     const int n16 = BnsGeom<256>::GEND * BnsGeom<256>::WSTEP / 16;
     hipLaunchKernelGGL(bns_pack_kernel<256>, dim3(ceil_div(n16, 256)), dim3(256), 0, s, a, b, c, static_cast<uint4_t*>(wstream));
@@ -1587,6 +2107,7 @@ extern "C" int ft_bottleneck_stream_fwd(const ft_bottleneck_desc* d, const void*
       case 0: return bns_launch<128, 4, 3, true>(p, s);
       case 5: return bns_launch<128, 3, 2, true>(p, s);
       case 1: return bns_launch<256, 4, 3, true>(p, s);
+      case 6: return bns_launch_tile16(p, s);
       case 3: return waves8 ? bns_launch_direct<2, 1, true, 0, 8, true>(p, s) : bns_launch_direct<2, 1, true, 0, 4, true>(p, s);
       default: return waves8 ? bns_launch_direct<3, 2, false, 0, 8, true>(p, s) : bns_launch_direct<3, 2, false, 0, 4, true>(p, s);
     }

@@ -120,6 +120,19 @@ __device__ __forceinline__ void relu_acc16(const float16_t& acc, half8_t (&h8)[2
   }
 }
 
+// the same for two 16 x 16 accumulator blocks of one lane (4 + 4 registers) as one 16-byte piece
+__device__ __forceinline__ half8_t relu_acc4x2(const float4_t& a, const float4_t& b) {
+  half8_t o;
+#pragma unroll
+  for (int r = 0; r < 4; r += 2) {
+    const half2_t u = __builtin_elementwise_max(__builtin_convertvector(float2_t{a[r], a[r + 1]}, half2_t), half2_t{(half_t)0.f, (half_t)0.f});
+    const half2_t v = __builtin_elementwise_max(__builtin_convertvector(float2_t{b[r], b[r + 1]}, half2_t), half2_t{(half_t)0.f, (half_t)0.f});
+    o[r] = u[0]; o[r + 1] = u[1];
+    o[4 + r] = v[0]; o[4 + r + 1] = v[1];
+  }
+  return o;
+}
+
 // Activation-output stores.  FT_YSTORE_AUX = 16 (sc1) makes them write-through: nothing is left dirty in the XCD L2s for
 // the end-of-kernel release to write back (the line is dropped from L2; the next launch reads it from the memory side).
 #ifndef FT_YSTORE_AUX

@@ -1224,7 +1224,9 @@ def _bottleneck_stream_operands(c1: "FusedConv", d, x: ActView, planes: int, p1,
     lib = _lib.load()
     (w1, s1, b1), (w2, s2, b2), (w3, s3, b3) = p1, p2, p3
     folded = convs is not None
-    key = ("bns_stream_folded" if folded else "bns_stream", x.N, x.H, x.W)
+    # the fragment order follows the kernel form the library plans for this descriptor (FT_BNS_VARIANT is read per call): part of the key
+    layout = int(lib.ft_bottleneck_stream_layout(ctypes.byref(d)))
+    key = ("bns_stream_folded" if folded else "bns_stream", x.N, x.H, x.W, layout)
     cached = c1._packed.get(key) if hasattr(c1, "_packed") else None
     if cached is None:
         P = planes

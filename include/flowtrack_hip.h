@@ -286,6 +286,11 @@ int ft_bottleneck_stream_supported(const ft_bottleneck_desc* d);
 /* 1 when ft_bottleneck_stream_fwd takes the FOLDED operands for this block (d->folded = 1; every stride-1 identity block), 0 when only
  * the table form exists (the stride-2 head); the value of d->folded itself is ignored. */
 int ft_bottleneck_stream_folds(const ft_bottleneck_desc* d);
+/* Fragment order of the weight stream that ft_bottleneck_stream_pack writes and ft_bottleneck_stream_fwd reads for this descriptor
+ * (d->folded counts) under the current developer switches: 0 = 32-channel tiles in K16 slices (every 32-pixel kernel), 1 = 16-channel
+ * tiles in K32 slices (the 256-plane kernel on 16-pixel MFMA tiles), -1 = unsupported.  Same byte count either way.  A stream packed
+ * for one order must not be fed to a launch that plans the other: callers that cache streams key them by this value. */
+int ft_bottleneck_stream_layout(const ft_bottleneck_desc* d);
 long long ft_bottleneck_stream_weight_bytes(const ft_bottleneck_desc* d);
 int ft_bottleneck_stream_pack(const ft_bottleneck_desc* d, const void* w1, const void* w2, const void* w3, void* wstream,
                               ft_stream_t stream);

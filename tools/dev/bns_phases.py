@@ -1,5 +1,5 @@
 """Phase timeline of the streamed fused bottleneck (FT_BNS_DBG=32 stamps s_memtime at phase boundaries of wave 0).
-usage: bns_phases.py [P=128|256] [B] ; FT_BNS_VARIANT applies."""
+usage: bns_phases.py [P=128|256] [B] ; FT_BNS_VARIANT (1, 2, 6) applies."""
 import os, sys
 os.environ["FT_BNS_DBG"] = str(32 | int(os.environ.get("FT_BNS_DBG", "0")))
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -26,7 +26,8 @@ for _ in range(3):
     y.t.zero_()
     prog.run_eager(); prog.stream.synchronize()
 var = os.environ.get("FT_BNS_VARIANT", "")
-TH = 8 if P == 128 or var == "1" or (var != "2" and B * 2 >= 224) else 4     # rows per strip of the variant bns_plan picks
+# rows per strip of the variant bns_plan picks (6 = the 16-pixel tiles, the default for folded operands below 112 crops)
+TH = 8 if P == 128 or var == "1" or (var not in ("2", "6") and B * 2 >= 224) else 4
 raw = y.t[:, ::TH, 0, :32].contiguous().view(torch.int64).reshape(-1, 8).cpu()
 t = raw.double()                          # the first pixel of every strip carries the stamps
 t0 = t[:, 0].min()

@@ -1,5 +1,6 @@
 """Static instruction mix of one kernel of a hipcc -S listing, split at its s_memtime stamps (the kernels' phase markers).
-usage: isa_phases.py <file.s> <substring of the kernel's mangled name> [--dump N]   (dev tool; no GPU)"""
+usage: isa_phases.py <file.s> <substring of the kernel's mangled name> [--ops]   (dev tool; no GPU)
+e.g. the 256-plane block: "direct_kernelILi3ELi2ELb0ELi4ELi0ELi4ELb1" (32-pixel tiles, FT_BNS_VARIANT=2), "tile16" (16-pixel tiles, =6)"""
 import collections
 import re
 import sys
