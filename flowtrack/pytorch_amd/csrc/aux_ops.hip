@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const T* __restrict__
         float v[8];
         load8<T>(x + (((n * Hi + iy) * Wi + ix) * (size_t)C8 + c8) * 8, v);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) m[e] = fmaxf(m[e], v[e]);
+        for (int e = 0; e < 8; ++e) m[e] = (v[e] > m[e] || v[e] != v[e]) ? v[e] : m[e];   // a NaN in the window stays (nn.MaxPool2d); fmaxf drops it
       }
     }
     store8<T>(y + i * 8, m);

@@ -308,7 +308,7 @@ int ft_pack_nchw_to_nhwc(const float* x, void* y, int N, int C, int H, int W,
 int ft_unpack_nhwc_to_nchw(const void* x, float* y, int N, int C, int H, int W,
                            int x_cstride, int x_coff, int dtype,
                            ft_stream_t stream);
-/* nn.MaxPool2d(3, 2, 1) on NHWC (resnet.py:23); C multiple of 8 */
+/* nn.MaxPool2d(3, 2, 1) on NHWC (resnet.py:23); C multiple of 8; padding is -inf, a NaN in the window gives NaN */
 int ft_maxpool3x3s2_fwd(const void* x, void* y, int N, int Hi, int Wi, int C,
                         int dtype, ft_stream_t stream);
 
