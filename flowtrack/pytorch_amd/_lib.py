@@ -21,6 +21,7 @@ FT_F16, FT_F32 = 0, 1
 FT_ACT_NONE, FT_ACT_RELU, FT_ACT_LEAKY = 0, 1, 2
 FT_LAYOUT_NHWC, FT_LAYOUT_NCHW_F32 = 0, 1
 FT_RGB_MEAN_SPLITS = 64
+FT_BNK_Y_FULL, FT_BNK_Y_EVEN, FT_BNK_Y_NONE = 0, 1, 2   # ft_bottleneck_exit_fwd: what is written of the block's own output
 
 
 class FlowtrackHipError(RuntimeError):
@@ -95,6 +96,11 @@ _PROTOTYPES = {
     "ft_bottleneck_supported": (c_int, [POINTER(BottleneckDesc)]),
     "ft_bottleneck_fwd": (c_int, [POINTER(BottleneckDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ft_bottleneck_flops": (c_double, [POINTER(BottleneckDesc)]),
+    "ft_bottleneck_exit_supported": (c_int, [POINTER(BottleneckDesc), c_int, c_int, c_int, c_int]),
+    "ft_bottleneck_exit_weight_bytes": (ctypes.c_longlong, [POINTER(BottleneckDesc), c_int]),
+    "ft_bottleneck_exit_pack": (c_int, [POINTER(BottleneckDesc), c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ft_bottleneck_exit_fwd": (c_int, [POINTER(BottleneckDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ft_bottleneck_rstat_supported": (c_int, [POINTER(BottleneckDesc)]),
     "ft_bottleneck_rstat_weight_bytes": (ctypes.c_longlong, []),
     "ft_bottleneck_rstat_fwd": (c_int, [POINTER(BottleneckDesc), c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -52,6 +52,16 @@ struct BnkParams {
   int w3_pitch;    // bytes per output-channel row of w3: 128 (W3 [256][64]); 256 at a projection block ([256][W3' 64 | Wd' 64])
   int dbg;         // FT_BNK_DBG (dev): 1 no x loads, 4 no stores, 16 x loads from images 0..7 only (L2-resident), 32 phase timestamps
 };
+// the exit form's extra arguments (a type of its own: the kernel argument block of the other forms stays what it was)
+struct BnkExitParams : BnkParams {
+  const char* tw;      // tail weights [128][256] in fragment order (bnk_tail_pack_kernel)
+  const float* tscale; // folded BN of the tail conv, 128 + 128 floats
+  const float* tshift;
+  char* t1;            // tail output [N,H,W,128] view
+  int t1_cstride, t1_coff;
+  int y_mode;          // FT_BNK_Y_FULL / _EVEN / _NONE
+  unsigned y_bytes, t1_bytes;   // extents of the two outputs (buffer stores: a lane with nothing to store points out of range)
+};
 
 template <int N, int I = 0, typename F>
 __device__ __forceinline__ void unroll_for(F&& f) {
@@ -94,12 +104,23 @@ __device__ __forceinline__ constexpr int ring_slot(int i) { return i == 0 ? 6553
 // over K = [t2 | x] of FusedShortcutConv (both BatchNorms folded into the weights, the shifts added): W3' quarters come through
 // the ring as before, the x fragments of the patch's own pixels are picked out of the phase-1 stage in the B-operand layout
 // and the shortcut weights Wd' (32 KiB per workgroup, L2-resident) go straight to registers at kernel start.
-template <int TW, int NCH, bool FULL, bool PROJ = false>
-__global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const BnkParams p) {
+// EXIT = the stage's LAST identity block together with the 1x1 conv that opens the next stage (layer2.0.conv1, 256 -> 128 + bn + relu,
+// resnet.py:37-43): nothing but that conv and the stride-2 shortcut reads the block's output, so a fourth phase multiplies every
+// activated quarter of y, as it sits in its staging buffer ([128 px][64 ch] = the pixel-operand layout T2 is read in), by the
+// K-slice [128 co][64 ci] of the tail weights into a persistent 128 x 128 fp32 accumulator (wave: ONE 32-channel tile x all four pixel
+// tiles = 64 registers: no two waves fetch the same weights, 64 KiB per patch from L2; 2 x 2 tiles per wave fetch 128 KiB and read
+// half the pixel fragments from LDS: measured alone the two layouts take the same time, profiles/HISTORY.md).  The tail weights come
+// straight from L2 to registers in fragment order, a quarter's 4 KiB per wave one quarter ahead (two register sets); the outputs go
+// through buffer stores, which the compiler counts: no wait on a weight fragment also waits for stores.  t1 leaves from the
+// accumulator layout (a lane owns 16 consecutive channels, as in conv1x1_stream_kernel) and y is written whole, at its even pixels
+// only (compact [N, H/2, W/2, 256]: what the stride-2 shortcut reads) or not at all.  250 registers, 76 800 B of LDS, no scratch.
+template <int TW, int NCH, bool FULL, bool PROJ = false, bool EXIT = false>
+__global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const std::conditional_t<EXIT, BnkExitParams, BnkParams> p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int TH = 128 / TW, PW = TW + 2, PH = TH + 2, NPIX = PW * PH;
   static_assert(NPIX <= 192, "halo patch");
   static_assert(!PROJ || (FULL && NCH == 1), "projection form: 64-channel input, whole block");
+  static_assert(!EXIT || (FULL && NCH == 4 && !PROJ), "exit form: the 256-wide identity block");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef __attribute__((address_space(3))) void* lds_ptr;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -370,6 +391,19 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const BnkParam
                                                            __builtin_bit_cast(half8_t, fb[sl][kk][j]), acc2[j], 0, 0, 0);
   });
 
+  // exit form: the tail weights of quarter 0 (this wave's one 32-channel tile x four K16 slices).  Issued behind the last
+  // counted wait of the ring; the vmcnt(0) in front of phase 3 covers them.
+  uint4_t fw4[EXIT ? 2 : 1][4];        // [quarter & 1][K16 slice] of channel tile `wave`
+  float16_t acc4[EXIT ? 4 : 1];        // [pixel tile]
+  [[maybe_unused]] auto load_tail = [&](int q) {
+    if constexpr (EXIT) {
+      const __amdgpu_buffer_rsrc_t rsrc_tw = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.tw), 0, 128 * kC * 2, 0x00020000);
+#pragma unroll
+      for (int k16 = 0; k16 < 4; ++k16)
+        fw4[q & 1][k16] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_tw, (unsigned)(lane * 16), ((q * 4 + wave) * 4 + k16) * 1024, 0);
+    }
+  };
+  if constexpr (EXIT) load_tail(0);
   BNK_TS(3);
   {
     char* t2 = smem + kOffT2;            // the T2 region held only a phase-1 stage, dead since the barrier after phase 1
@@ -417,26 +451,34 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const BnkParam
   load_item(12);
 
   // ================= phase 3: y = relu(bn3(W3 . t2) + x), four quarters of 64 output channels ====================
+  // exit form: 64 more accumulator registers live through phase 3, so T2's fragments are read again in every quarter instead of
+  // held (32 registers); staging B then cannot reuse the T2 region and lies at 16 .. 32 Ki (8 KiB that T1 left + ring slot 1,
+  // whose W3 quarter 0 every wave is done with at quarter 0's barrier, before quarter 1 writes B for the first time)
+  constexpr int kOutB = EXIT ? 16384 : kOffOutB;
   uint4_t fb3[2][2][2];
-  {
-    const char* t2 = smem + kOffT2;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int m = wp2 * 64 + j * 32 + l31;
-      const int lsw = lhi ^ BNK_KEY(m);
-#pragma unroll
-      for (int sl = 0; sl < 2; ++sl)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-          fb3[sl][kk][j] = *reinterpret_cast<const uint4_t*>(t2 + m * 128 + ((lsw ^ (sl * 4 + kk * 2)) << 4));
-    }
+#define BNK_LOAD_FB3()                                                                                                       \
+  {                                                                                                                          \
+    const char* t2 = smem + kOffT2;                                                                                          \
+    _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                                          \
+      const int m = wp2 * 64 + j * 32 + l31;                                                                                 \
+      const int lsw = lhi ^ BNK_KEY(m);                                                                                      \
+      _Pragma("unroll") for (int sl = 0; sl < 2; ++sl)                                                                       \
+        _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                                                     \
+          fb3[sl][kk][j] = *reinterpret_cast<const uint4_t*>(t2 + m * 128 + ((lsw ^ (sl * 4 + kk * 2)) << 4));               \
+    }                                                                                                                        \
   }
+  if constexpr (!EXIT) BNK_LOAD_FB3();
   long long spix[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int m = (tid + 256 * i) >> 3;
     const int oy = qy0 + m / TW, ox = qx0 + m % TW;
     spix[i] = (oy < p.H && ox < p.W) ? ((long long)n * p.H + oy) * p.W + ox : -1;
+    if constexpr (EXIT) {    // patch origins are even: parity is local.  H and W are even here (supported())
+      if (p.y_mode == FT_BNK_Y_EVEN)
+        spix[i] = (oy < p.H && ox < p.W && !((oy | ox) & 1)) ? ((long long)n * (p.H >> 1) + (oy >> 1)) * (p.W >> 1) + (ox >> 1) : -1;
+      else if (p.y_mode == FT_BNK_Y_NONE) spix[i] = -1;
+    }
   }
   // every W3 quarter and the residuals have landed; every wave holds its T2 fragments (staging B reuses the T2 region)
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -451,6 +493,10 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const BnkParam
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc3[j][r] = 0.f;
+    if constexpr (EXIT) {
+      if constexpr (q < 3) load_tail(q + 1);
+      BNK_LOAD_FB3();
+    }
 #pragma unroll
     for (int sl = 0; sl < 2; ++sl)
 #pragma unroll
@@ -471,7 +517,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const BnkParam
             acc3[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, fad[q][sl * 2 + kk]),
                                                              __builtin_bit_cast(half8_t, fbx[sl][kk][j]), acc3[j], 0, 0, 0);
     }
-    char* so = smem + ((q & 1) ? kOffOutB : kOffOutA);
+    char* so = smem + ((q & 1) ? kOutB : kOffOutA);
     float4_t sc[4], sh[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -501,20 +547,85 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const BnkParam
     // one barrier per quarter: the two staging buffers alternate, a buffer's previous readers are two barriers behind
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     BNK_BARRIER();
+    if constexpr (!EXIT) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int idx = tid + 256 * i, m = idx >> 3, ch = idx & 7;
-      const uint4_t v = *reinterpret_cast<const uint4_t*>(so + m * 128 + ((ch ^ BNK_KEY(m)) << 4));
-      if (spix[i] >= 0 && !(p.dbg & 4))
-        store_out16(p.y + (spix[i] * p.y_cstride + p.y_coff + q * 64 + ch * 8) * 2, v);
+      for (int i = 0; i < 4; ++i) {
+        const int idx = tid + 256 * i, m = idx >> 3, ch = idx & 7;
+        const uint4_t v = *reinterpret_cast<const uint4_t*>(so + m * 128 + ((ch ^ BNK_KEY(m)) << 4));
+        if (spix[i] >= 0 && !(p.dbg & 4))
+          store_out16(p.y + (spix[i] * p.y_cstride + p.y_coff + q * 64 + ch * 8) * 2, v);
+      }
+    } else {
+      const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (p.dbg & 4) ? 0 : p.y_bytes, 0x00020000);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int idx = tid + 256 * i, m = idx >> 3, ch = idx & 7;
+        const uint4_t v = *reinterpret_cast<const uint4_t*>(so + m * 128 + ((ch ^ BNK_KEY(m)) << 4));
+        const unsigned vo = spix[i] >= 0 ? (unsigned)((spix[i] * p.y_cstride + p.y_coff + q * 64 + ch * 8) * 2) : kOOB;
+        __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_y, vo, 0, FT_YSTORE_BUF_AUX);
+      }
+      // ---- phase 4, step q: tail accumulator += Wt[:, 64q .. 64q+63] . y quarter (the fp16 values just staged) ------------
+      if constexpr (q == 0) {    // the accumulator starts its life here, not in front of phase 3 (registers)
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc4[pt][r] = 0.f;
+      }
+#pragma unroll
+      for (int k16 = 0; k16 < 4; ++k16) {
+        uint4_t fb4[4];
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt) {
+          const int m = pt * 32 + l31;
+          fb4[pt] = *reinterpret_cast<const uint4_t*>(so + m * 128 + (((lhi ^ BNK_KEY(m)) ^ (k16 * 2)) << 4));
+        }
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt)
+          acc4[pt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, fw4[q & 1][k16]),
+                                                            __builtin_bit_cast(half8_t, fb4[pt]), acc4[pt], 0, 0, 0);
+      }
     }
   });
+  if constexpr (EXIT) {
+    // tail epilogue = conv1x1_stream_kernel's: fp32 scale * acc + shift, ReLU, fp16; register r of the tile = channel 16 lhi + r
+    // (the pack kernel permuted the rows), 32 bytes per lane and pixel tile
+    const __amdgpu_buffer_rsrc_t rsrc_t1 = __builtin_amdgcn_make_buffer_rsrc(p.t1, 0, (p.dbg & 4) ? 0 : p.t1_bytes, 0x00020000);
+    const int ch = wave * 32 + 16 * lhi;
+    float4_t sc[4], sh[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      sc[g] = *reinterpret_cast<const float4_t*>(p.tscale + ch + 4 * g);
+      sh[g] = *reinterpret_cast<const float4_t*>(p.tshift + ch + 4 * g);
+    }
+#pragma unroll
+    for (int pt = 0; pt < 4; ++pt) {
+      const int m = pt * 32 + l31;
+      const int oy = qy0 + m / TW, ox = qx0 + m % TW;
+      const unsigned vo = (oy < p.H && ox < p.W) ? (unsigned)(((((long long)n * p.H + oy) * p.W + ox) * p.t1_cstride + p.t1_coff + ch) * 2) : kOOB;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        half8_t o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const int r = h * 8 + e;
+          const float v = acc4[pt][r] * sc[r >> 2][r & 3] + sh[r >> 2][r & 3];
+          o[e] = (half_t)act_mul(v, 0.f);
+        }
+        // plain, not write-through (as conv1x1_stream_kernel): a 128-byte line of t1 gets its four 32-byte pieces from four lanes of
+        // two waves at different times and the L2 merges them; written through, every piece went to memory as a 64-byte write
+        // (WRITE_SIZE 125.8 MB per launch at batch 64 where t1 + the even y are 75.5)
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_t, o), rsrc_t1, vo, h * 16, 0);
+      }
+    }
+  }
   if (p.dbg & 32) {       // dev: phase timestamps of wave 0 over the tile's first output pixel (output is garbage then)
     ts[6] = __builtin_amdgcn_s_memtime();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     ts[7] = __builtin_amdgcn_s_memtime();
     if (tid == 0) {
       unsigned long long* o = reinterpret_cast<unsigned long long*>(p.y + ((((long long)n * p.H + qy0) * p.W + qx0) * p.y_cstride + p.y_coff) * 2);
+      if constexpr (EXIT)    // the exit form may have no full y map: the stamps go to t1's first pixel of the tile (128 channels = 256 bytes)
+        o = reinterpret_cast<unsigned long long*>(p.t1 + ((((long long)n * p.H + qy0) * p.W + qx0) * p.t1_cstride + p.t1_coff) * 2);
 #pragma unroll
       for (int i = 0; i < 8; ++i) o[i] = ts[i];
     }
@@ -535,6 +646,39 @@ static int supported(const ft_bottleneck_desc* d) {
   return FT_OK;
 }
 
+// fragment-ordered tail weights of the exit form: [quarter 4][channel tile 4][K16 slice 4][lane 64] x 16 bytes from the packed
+// [128][256] layout; row r of a tile holds channel cd_sigma(r), so accumulator register r of lane half lhi = channel 16 lhi + r
+__global__ __launch_bounds__(256) void bnk_tail_pack_kernel(const half_t* __restrict__ w, uint4_t* __restrict__ out, int kpad) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;      // 4096 = 16 blocks exactly
+  const int lane = idx & 63, f = idx >> 6;
+  const int k16 = f & 3, tl = (f >> 2) & 3, q = f >> 4;
+  const int r = lane & 31;
+  const int co = tl * 32 + 16 * ((r >> 2) & 1) + 4 * (r >> 3) + (r & 3), k = q * 64 + k16 * 16 + 8 * (lane >> 5);
+  out[idx] = *reinterpret_cast<const uint4_t*>(w + (size_t)co * kpad + k);
+}
+
+static int exit_supported(const ft_bottleneck_desc* d, int tail_cout, int t1_cstride, int t1_coff, int y_mode) {
+  const int st = supported(d);
+  if (st != FT_OK) return st;
+  if (y_mode != FT_BNK_Y_FULL && y_mode != FT_BNK_Y_EVEN && y_mode != FT_BNK_Y_NONE) return FT_ERR_INVALID_ARG;
+  if (d->head_only || d->projection || d->C != kC || tail_cout != 128) return FT_ERR_UNSUPPORTED;
+  if ((d->H | d->W) & 1) return FT_ERR_UNSUPPORTED;
+  if (t1_coff < 0 || t1_coff % 8 || t1_cstride % 8) return FT_ERR_UNSUPPORTED;
+  if (t1_cstride < t1_coff + tail_cout) return FT_ERR_INVALID_ARG;
+  if ((long long)d->N * d->H * d->W * t1_cstride * 2 >= (1LL << 31) || (long long)d->N * d->H * d->W * d->y_cstride * 2 >= (1LL << 31))
+    return FT_ERR_UNSUPPORTED;      // 32-bit offsets of the buffer stores
+  return FT_OK;
+}
+
+template <int TW>
+static int launch_exit(const BnkExitParams& p, hipStream_t s) {
+  auto k = bottleneck_fused_kernel<TW, 4, true, false, true>;
+  FT_RAISE_LDS(k, kLdsBytes);
+  hipLaunchKernelGGL(k, dim3(p.total), dim3(256), kLdsBytes, s, p);
+  FT_LAUNCH_CHECK("bottleneck_fused_kernel(exit)");
+  return FT_OK;
+}
+
 template <int TW, int NCH, bool FULL, bool PROJ = false>
 static int launch(const BnkParams& p, hipStream_t s) {
   auto k = bottleneck_fused_kernel<TW, NCH, FULL, PROJ>;
@@ -542,6 +686,28 @@ static int launch(const BnkParams& p, hipStream_t s) {
   hipLaunchKernelGGL(k, dim3(p.total), dim3(256), kLdsBytes, s, p);
   FT_LAUNCH_CHECK("bottleneck_fused_kernel");
   return FT_OK;
+}
+
+static void fill_params(BnkParams& p, const ft_bottleneck_desc* d, const void* x, const void* w1, const void* w2, const void* w3,
+                        const float* scale_shift, void* y) {
+  p.x = static_cast<const char*>(x);
+  p.y = static_cast<char*>(y);
+  p.w1 = static_cast<const char*>(w1);
+  p.w2 = static_cast<const char*>(w2);
+  p.w3 = static_cast<const char*>(w3);
+  p.tab = reinterpret_cast<const char*>(scale_shift);
+  p.N = d->N; p.H = d->H; p.W = d->W;
+  p.x_cstride = d->x_cstride; p.x_coff = d->x_coff; p.y_cstride = d->y_cstride; p.y_coff = d->y_coff;
+  p.x_bytes = (unsigned)((size_t)d->N * d->H * d->W * d->x_cstride * 2);
+  p.w3_pitch = d->projection ? 256 : 128;
+  // 8 rows x 16 columns unless the width only divides by 8 (R101 at 384x288: 96x72 maps -> 16 rows x 8 columns)
+  const bool tall = d->W % 16 != 0 && d->W % 8 == 0;
+  const int tw = tall ? 8 : 16, th = 128 / tw;
+  p.tx = ceil_div(d->W, tw);
+  p.ty = ceil_div(d->H, th);
+  p.total = d->N * p.tx * p.ty;
+  static const int dbg = dev_env_int("FT_BNK_DBG", 0);
+  p.dbg = dbg;
 }
 
 }  // namespace
@@ -565,27 +731,54 @@ extern "C" int ft_bottleneck_fwd(const ft_bottleneck_desc* d, const void* x, con
   if (st != FT_OK) return st;
   if (!x || !w1 || !w2 || (!w3 && !d->head_only) || !scale_shift || !y) return FT_ERR_INVALID_ARG;
   BnkParams p{};
-  p.x = static_cast<const char*>(x);
-  p.y = static_cast<char*>(y);
-  p.w1 = static_cast<const char*>(w1);
-  p.w2 = static_cast<const char*>(w2);
-  p.w3 = static_cast<const char*>(w3);
-  p.tab = reinterpret_cast<const char*>(scale_shift);
-  p.N = d->N; p.H = d->H; p.W = d->W;
-  p.x_cstride = d->x_cstride; p.x_coff = d->x_coff; p.y_cstride = d->y_cstride; p.y_coff = d->y_coff;
-  p.x_bytes = (unsigned)((size_t)d->N * d->H * d->W * d->x_cstride * 2);
-  p.w3_pitch = d->projection ? 256 : 128;
-  // 8 rows x 16 columns unless the width only divides by 8 (R101 at 384x288: 96x72 maps -> 16 rows x 8 columns)
-  const bool tall = d->W % 16 != 0 && d->W % 8 == 0;
-  const int tw = tall ? 8 : 16, th = 128 / tw;
-  p.tx = ceil_div(d->W, tw);
-  p.ty = ceil_div(d->H, th);
-  p.total = d->N * p.tx * p.ty;
-  static const int dbg = dev_env_int("FT_BNK_DBG", 0);
-  p.dbg = dbg;
+  fill_params(p, d, x, w1, w2, w3, scale_shift, y);
   hipStream_t s = as_stream(stream);
+  const bool tall = d->W % 16 != 0 && d->W % 8 == 0;
   if (d->head_only) return tall ? launch<8, 1, false>(p, s) : launch<16, 1, false>(p, s);
   if (d->projection) return tall ? launch<8, 1, true, true>(p, s) : launch<16, 1, true, true>(p, s);
   return tall ? launch<8, 4, true>(p, s) : launch<16, 4, true>(p, s);
 }
 
+extern "C" int ft_bottleneck_exit_supported(const ft_bottleneck_desc* d, int tail_cout, int t1_cstride, int t1_coff, int y_mode) {
+  return ft::exit_supported(d, tail_cout, t1_cstride, t1_coff, y_mode);
+}
+
+extern "C" long long ft_bottleneck_exit_weight_bytes(const ft_bottleneck_desc* d, int tail_cout) {
+  return ft::exit_supported(d, tail_cout, tail_cout, 0, FT_BNK_Y_FULL) == FT_OK ? 128LL * ft::kC * 2 : 0;
+}
+
+extern "C" int ft_bottleneck_exit_pack(const ft_bottleneck_desc* d, int tail_cout, const void* wt_packed, int kpad, int cout_pad, void* wstream,
+                                       ft_stream_t stream) {
+  using namespace ft;
+  const int st = exit_supported(d, tail_cout, tail_cout, 0, FT_BNK_Y_FULL);
+  if (st != FT_OK) return st;
+  if (!wt_packed || !wstream || kpad < kC || kpad % 8 || cout_pad < tail_cout) return FT_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(bnk_tail_pack_kernel, dim3(16), dim3(256), 0, as_stream(stream), static_cast<const half_t*>(wt_packed),
+                     static_cast<uint4_t*>(wstream), kpad);
+  FT_LAUNCH_CHECK("bnk_tail_pack_kernel");
+  return FT_OK;
+}
+
+extern "C" int ft_bottleneck_exit_fwd(const ft_bottleneck_desc* d, const void* x, const void* w1, const void* w2, const void* w3,
+                                      const float* scale_shift, void* y, int y_mode, int tail_cout, const void* tail_wstream,
+                                      const float* tail_scale, const float* tail_shift, void* t1, int t1_cstride, int t1_coff,
+                                      ft_stream_t stream) {
+  using namespace ft;
+  const int st = exit_supported(d, tail_cout, t1_cstride, t1_coff, y_mode);
+  if (st != FT_OK) return st;
+  if (!x || !w1 || !w2 || !w3 || !scale_shift || (!y && y_mode != FT_BNK_Y_NONE) || !tail_wstream || !tail_scale || !tail_shift || !t1)
+    return FT_ERR_INVALID_ARG;
+  BnkExitParams p{};
+  fill_params(p, d, x, w1, w2, w3, scale_shift, y);
+  p.tw = static_cast<const char*>(tail_wstream);
+  p.tscale = tail_scale;
+  p.tshift = tail_shift;
+  p.t1 = static_cast<char*>(t1);
+  p.t1_cstride = t1_cstride; p.t1_coff = t1_coff;
+  p.y_mode = y_mode;
+  const size_t ypix = y_mode == FT_BNK_Y_FULL ? (size_t)d->N * d->H * d->W : y_mode == FT_BNK_Y_EVEN ? (size_t)d->N * (d->H / 2) * (d->W / 2) : 0;
+  p.y_bytes = (unsigned)(ypix * d->y_cstride * 2);
+  p.t1_bytes = (unsigned)((size_t)d->N * d->H * d->W * t1_cstride * 2);
+  const bool tall = d->W % 16 != 0 && d->W % 8 == 0;
+  return tall ? launch_exit<8>(p, as_stream(stream)) : launch_exit<16>(p, as_stream(stream));
+}

@@ -94,7 +94,7 @@ def new_act(N: int, H: int, W: int, C: int, dtype, device, cstride: Optional[int
 # --------------------------------------------------------------------------------------------
 def is_conv_call(name: str) -> bool:
     """Launches whose work is convolution MACs (the roofline's kernels): ft_conv2d_fwd[_ws] and ft_bottleneck_fwd."""
-    return name.startswith("ft_conv2d_fwd") or name in ("ft_bottleneck_fwd", "ft_bottleneck_rstat_fwd", "ft_bottleneck_stream_fwd", "ft_bottleneck_cluster_fwd", "ft_conv_direct_fwd")
+    return name.startswith("ft_conv2d_fwd") or name in ("ft_bottleneck_fwd", "ft_bottleneck_exit_fwd", "ft_bottleneck_rstat_fwd", "ft_bottleneck_stream_fwd", "ft_bottleneck_cluster_fwd", "ft_conv_direct_fwd")
 
 
 def _on_plan_device(fn):
@@ -1363,6 +1363,84 @@ def record_bottleneck(prog: Program, c1: "FusedConv", c2: "FusedConv", c3: "Fuse
     table = torch.cat([t.flatten()[:n] for t, n in ((s1, planes), (b1, planes), (s2, planes), (b2, planes), (s3, x.C), (b3, x.C))]).contiguous()
     prog.add("ft_bottleneck_fwd", ctypes.byref(d), x.t.data_ptr(), w1.data_ptr(), w2.data_ptr(), w3.data_ptr(), table.data_ptr(),
              y.t.data_ptr(), keep=(d, x.t, y.t, w1, w2, w3, table))
+
+
+#: y modes of ft_bottleneck_exit_fwd by name
+BNK_Y_MODES = {"full": _lib.FT_BNK_Y_FULL, "even": _lib.FT_BNK_Y_EVEN, "none": _lib.FT_BNK_Y_NONE}
+
+
+def _bottleneck_exit_args(x: ActView, y: Optional[ActView], t1: ActView, planes: int, y_mode: str):
+    """(descriptor, y mode code) of ft_bottleneck_exit_*; None when the views do not have the mode's shapes."""
+    if y_mode not in BNK_Y_MODES or (y is None) != (y_mode == "none"):
+        return None
+    want = {"full": (x.N, x.H, x.W), "even": (x.N, x.H // 2, x.W // 2), "none": None}[y_mode]
+    if y is not None and ((y.N, y.H, y.W) != want or y.C != x.C or y.t.dtype != x.t.dtype or y.rowpacked):
+        return None
+    if (t1.N, t1.H, t1.W) != (x.N, x.H, x.W) or t1.t.dtype != x.t.dtype or t1.rowpacked or x.rowpacked:
+        return None
+    d = _lib.BottleneckDesc()
+    d.dtype = _lib.dtype_code(x.t.dtype)
+    d.N, d.H, d.W, d.C, d.P = x.N, x.H, x.W, x.C, planes
+    d.x_cstride, d.x_coff = x.cstride, x.coff
+    d.y_cstride, d.y_coff = (y.cstride, y.coff) if y is not None else (act_stride(x.C), 0)
+    return d, BNK_Y_MODES[y_mode]
+
+
+def bottleneck_exit_fusable(c1: "FusedConv", c2: "FusedConv", c3: "FusedConv", tail: "FusedConv", x: ActView, y: Optional[ActView],
+                            t1: ActView, y_mode: str = "even") -> bool:
+    """True when ft_bottleneck_exit_fwd covers this identity block together with `tail`, the 1x1 conv + bn + relu that opens the next
+    stage (fp16, 256 -> 64 -> 64 -> 256 then 256 -> 128, even map sizes)."""
+    full = ActView(x.t, x.C, x.coff)      # the block itself must be one ft_bottleneck_fwd covers (its output view: any of x's shape)
+    if x.t.dtype != torch.float16 or not bottleneck_fusable(c1, c2, c3, x, full):
+        return False
+    if (tail.k, tail.stride, tail.pad, tail.cin, tail.cout) != (1, 1, 0, x.C, t1.C) or tail.transposed or tail.tail_cout \
+            or tail.act != ACT_CODES["relu"] or tail._bn is None:
+        return False
+    args = _bottleneck_exit_args(x, y, t1, c2.cin, y_mode)
+    if args is None:
+        return False
+    d, mode = args
+    return _lib.load().ft_bottleneck_exit_supported(ctypes.byref(d), tail.cout, t1.cstride, t1.coff, mode) == 0
+
+
+def record_bottleneck_exit(prog: Program, c1: "FusedConv", c2: "FusedConv", c3: "FusedConv", tail: "FusedConv", x: ActView,
+                           y: Optional[ActView], t1: ActView, label: str, y_mode: str = "even") -> None:
+    """A stage's last identity block AND the next stage's opening 1x1 conv (`tail`: conv + bn + relu, 256 -> 128) as ONE launch
+    (ft_bottleneck_exit_fwd): t1 = tail(block(x)) [N,H,W,128]; of the block's own output `y` the launch writes all ("full"), the
+    even pixels as a compact [N, H/2, W/2, C] map ("even": what the stride-2 projection shortcut reads) or nothing ("none", y = None)."""
+    lib = _lib.load()
+    args = _bottleneck_exit_args(x, y, t1, c2.cin, y_mode)
+    if args is None:
+        raise FlowtrackHipError(f"{label}: views do not fit y mode {y_mode!r}")
+    d, mode = args
+    def overlap(a, b):      # the buffers behind two views share bytes
+        a0, b0 = a.t.data_ptr(), b.t.data_ptr()
+        return a0 < b0 + b.t.numel() * b.t.element_size() and b0 < a0 + a.t.numel() * a.t.element_size()
+    if overlap(t1, x) or (y is not None and (overlap(y, x) or overlap(t1, y))):
+        raise FlowtrackHipError(f"{label}: x, y and t1 of the exit form must be three separate buffers")
+    planes = c2.cin
+    check(lib.ft_bottleneck_exit_supported(ctypes.byref(d), tail.cout, t1.cstride, t1.coff, mode), "ft_bottleneck_exit_supported")
+    w1, s1, b1 = _bottleneck_packed(c1, x, (planes, x.C, 1), label)
+    w2, s2, b2 = _bottleneck_packed(c2, x, (planes, 9 * planes, 1), label)
+    w3, s3, b3 = _bottleneck_packed(c3, x, (x.C, planes, 1), label)
+    wt, st, bt = _bottleneck_packed(tail, x, (tail.cout, x.C, 1), label)
+    key = ("bnk_exit", wt.data_ptr())
+    wstream = tail._packed.get(key)
+    if wstream is None:       # fragment-ordered tail weights: once per packed weight set
+        wstream = torch.empty(int(lib.ft_bottleneck_exit_weight_bytes(ctypes.byref(d), tail.cout)), dtype=torch.uint8, device=x.t.device)
+        check(lib.ft_bottleneck_exit_pack(ctypes.byref(d), tail.cout, wt.data_ptr(), int(wt.shape[-1]), int(wt.shape[-2]), wstream.data_ptr(),
+                                          current_stream_handle(x.t.device)), "ft_bottleneck_exit_pack")
+        torch.cuda.current_stream(x.t.device).synchronize()
+        tail._packed[key] = wstream
+    table = torch.cat([t.flatten()[:n] for t, n in ((s1, planes), (b1, planes), (s2, planes), (b2, planes), (s3, x.C), (b3, x.C))]).contiguous()
+    tscale, tshift = st.flatten()[:tail.cout].contiguous(), bt.flatten()[:tail.cout].contiguous()
+    # the roofline's FLOPs of this launch = the block + the conv it absorbed (2 * MACs each)
+    flops = float(lib.ft_bottleneck_flops(ctypes.byref(d))) + 2.0 * x.N * x.H * x.W * x.C * tail.cout
+    prog.flops += flops
+    prog.fused_records.append((label, len(prog.calls), flops))
+    prog.add("ft_bottleneck_exit_fwd", ctypes.byref(d), x.t.data_ptr(), w1.data_ptr(), w2.data_ptr(), w3.data_ptr(), table.data_ptr(),
+             y.t.data_ptr() if y is not None else None, mode, tail.cout, wstream.data_ptr(), tscale.data_ptr(), tshift.data_ptr(),
+             t1.t.data_ptr(), t1.cstride, t1.coff, keep=(d, x.t, y.t if y is not None else None, t1.t, w1, w2, w3, table, wstream, tscale, tshift))
 
 
 # --------------------------------------------------------------------------------------------

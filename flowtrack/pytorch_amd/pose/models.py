@@ -24,9 +24,9 @@ import torch
 import torch.nn as nn
 
 from ..engine import HipModule
-from ..hip_ops import (ActView, FlowtrackHipError, FusedConv, FusedShortcutConv, Program, bottleneck_fusable,
+from ..hip_ops import (ActView, FlowtrackHipError, FusedConv, FusedShortcutConv, Program, bottleneck_exit_fusable, bottleneck_fusable,
                        bottleneck_entry_fusable, bottleneck_head_fusable, bottleneck_cluster_supported, bottleneck_strips_supported, bottleneck_head_stream_fusable, bottleneck_prefers_fused, new_act, new_rowpacked_act, record_bottleneck, record_bottleneck_entry, record_bottleneck_head, record_bottleneck_head_stream,
-                       record_maxpool, record_pack_input)
+                       record_bottleneck_exit, record_maxpool, record_pack_input)
 from ..params import ActMarker, BatchNormParams, ConvParams, ConvTransposeParams
 
 # depth -> blocks per stage; only Bottleneck nets are valid because the head hard-codes 2048
@@ -61,11 +61,29 @@ class _PosePlan:
         self.runs = 0
 
 
+class _Stages(dict):
+    """plan.stages: the activation view behind each stage.  A stage whose last block was recorded in the exit form
+    (DeconvResnet.fuse_stage_exit) may never write its full map: it has no entry, and asking for it says why."""
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.absent = {}
+
+    def __missing__(self, key):
+        if key in self.absent:
+            raise FlowtrackHipError(f"plan.stages[{key!r}]: {self.absent[key]}")
+        raise KeyError(key)
+
+
 class DeconvResnet(HipModule):
     #: fold each block-0 projection shortcut into its conv3 launch (FusedShortcutConv); FT_FUSE_SHORTCUT=0 keeps them apart
     fuse_shortcut: bool = os.environ.get("FT_FUSE_SHORTCUT", "1") != "0"
     #: identity-shortcut blocks of the 256-wide stage as one launch (ft_bottleneck_fwd); FT_FUSE_BOTTLENECK=0 keeps 3 convs
     fuse_bottleneck: bool = os.environ.get("FT_FUSE_BOTTLENECK", "1") != "0"
+    #: a stage's last identity block together with the next stage's conv1 as one launch that writes t1 and only the even pixels of
+    #: the block's output (ft_bottleneck_exit_fwd; layer1.2 + layer2.0.conv1): recorded as an alternative to today's launches, the
+    #: first-call benchmark keeps one.  FT_FUSE_STAGE_EXIT=0 / False records today's launches only, 2 / "force" the exit form only (dev, tests)
+    fuse_stage_exit = {"0": False, "2": "force"}.get(os.environ.get("FT_FUSE_STAGE_EXIT", "1"), True)
     #: the stem's max-pool inside the stem conv launch (ft_conv_desc.pool); FT_FUSE_STEM_POOL=0 keeps the two launches
     fuse_stem_pool: bool = os.environ.get("FT_FUSE_STEM_POOL", "1") != "0"
     #: the fused stem reads the NCHW fp32 input itself (ft_conv_desc.x_nchw_f32): no pack launch, no packed copy, bit-identical
@@ -179,10 +197,16 @@ class DeconvResnet(HipModule):
         # FT_SPLIT_LANES=1 (dev, measured in profiles/README.md): layer1 + layer2 as TWO half-batch lanes (parallel graph branches).
         # Their fused blocks are phase-locked across the chip — every workgroup reads its input, then multiplies, then writes, at
         # the same time, so HBM idles while the matrix pipe runs and vice versa; two lanes half a block apart overlap them.
-        stages = {"stem": cur}         # activation views behind each stage (diagnostics: tests/error_budget.py)
-        for li, layer in enumerate((self.layer1, self.layer2, self.layer3, self.layer4), start=1):
-            if li > 1:
+        stages = _Stages({"stem": cur})         # activation views behind each stage (diagnostics: tests/error_budget.py)
+        trunk = (self.layer1, self.layer2, self.layer3, self.layer4)
+        seam = None                    # output view of this stage's entry block when the previous stage's exit form recorded it
+        for li, layer in enumerate(trunk, start=1):
+            if li > 1 and seam is None:
                 stages[f"layer{li - 1}"] = cur
+            elif li > 1:
+                stages.absent[f"layer{li - 1}"] = ("this plan records the stage's last block in the exit form, which writes only the even pixels of "
+                                                   "its output (the full map exists only if the first-call benchmark kept today's launches): for the "
+                                                   "map, build the model with fuse_stage_exit = False (FT_FUSE_STAGE_EXIT=0)")
             if split and li == 1:
                 chain = []
                 hh, ww = cur.H, cur.W
@@ -239,8 +263,15 @@ class DeconvResnet(HipModule):
                 cur = chain[-1][2]
                 continue
             for bi, blk in enumerate(layer):
+                if bi == 0 and seam is not None:
+                    cur, seam = seam, None
+                    continue
                 name = f"layer{li}.{bi}"
                 out = new_act(B, cur.H // blk.stride, cur.W // blk.stride, blk.conv1.cout * 4, dtype, device)
+                if bi == len(layer) - 1 and bi > 0 and li < 4 and not split:
+                    seam = self._record_stage_exit(prog, name, blk, f"layer{li + 1}.0", trunk[li][0], cur, out, dtype, device)
+                    if seam is not None:
+                        continue
                 self._record_block(prog, name, blk, cur, out, dtype, device)
                 cur = out
 
@@ -294,6 +325,59 @@ class DeconvResnet(HipModule):
                 prog.add("ft_memcpy_async", ex["header_host"].data_ptr(), ex["header"].data_ptr(), ctypes.c_size_t((1 + B) * 4), keep=(ex["header_host"],))
                 plan.exact = ex
         return plan
+
+    def _record_stage_exit(self, prog, name: str, blk, nname: str, nblk, cur, out, dtype, device):
+        """The seam between two stages: `blk` = the stage's last identity block (from `cur` into `out`), `nblk` = the stride-2 entry
+        block of the next stage.  Nothing but nblk.conv1 and nblk's stride-2 shortcut reads `out`, so where ft_bottleneck_exit_fwd
+        covers the pair (fp16, 256 -> 64 -> 64 -> 256 then 256 -> 128: layer1 -> layer2) two forms of BOTH blocks are recorded and
+        the first-call benchmark keeps one:
+          "fused"  blk + nblk.conv1 as one launch that writes t1 and the even pixels of blk's output as a compact half-size map,
+                   then nblk.conv2 and the K-concatenated conv3 + shortcut, which reads the compact map at stride 1;
+          "convs"  the launches _record_block gives the two blocks (nblk.conv1 a launch of its own).
+        Returns nblk's output view, or None when the exit form does not apply (nothing recorded then)."""
+        if not (self.fuse_stage_exit and self.fuse_bottleneck and self.fuse_shortcut) or dtype != torch.float16:
+            return None
+        if len(blk.downsample) or blk.stride != 1 or nblk.stride != 2 or not len(nblk.downsample) or cur.H % 2 or cur.W % 2:
+            return None
+        B, mk = cur.N, dict(dtype=dtype, device=device)
+        nplanes = nblk.conv1.cout
+        c1 = self.fused(name + ".conv1", blk.conv1.weight, bn=blk.bn1.as_dict(), act="relu", **mk)
+        c2 = self.fused(name + ".conv2", blk.conv2.weight, stride=1, pad=1, bn=blk.bn2.as_dict(), act="relu", **mk)
+        c3 = self.fused(name + ".conv3", blk.conv3.weight, bn=blk.bn3.as_dict(), act="relu", **mk)
+        n1 = self.fused(nname + ".conv1", nblk.conv1.weight, bn=nblk.bn1.as_dict(), act="relu", **mk)
+        n2 = self.fused(nname + ".conv2", nblk.conv2.weight, stride=2, pad=1, bn=nblk.bn2.as_dict(), act="relu", **mk)
+        t1 = new_act(B, cur.H, cur.W, nplanes, dtype, device)
+        y_even = new_act(B, cur.H // 2, cur.W // 2, cur.C, dtype, device)
+        if not bottleneck_exit_fusable(c1, c2, c3, n1, cur, y_even, t1, "even"):
+            return None
+        t2 = new_act(B, cur.H // 2, cur.W // 2, nplanes, dtype, device)
+        nout = new_act(B, cur.H // 2, cur.W // 2, nplanes * 4, dtype, device)
+        key = (nname + ".conv3+downsample@even", dtype, str(device))
+        sc = self._layers.get(key)
+        if sc is None:      # the same GEMM as _record_block's, its shortcut operand read at stride 1 from the compact map
+            sc = self._layers[key] = FusedShortcutConv(nblk.conv3.weight, nblk.bn3.as_dict(), nblk.downsample[0].weight,
+                                                       nblk.downsample[1].as_dict(), 1, dtype=dtype, device=device, act="relu",
+                                                       label=nname + ".conv3+downsample")
+
+        def exit_form():
+            record_bottleneck_exit(prog, c1, c2, c3, n1, cur, y_even, t1, f"{name}.fused+{nname}.conv1", "even")
+            n2.record(prog, t1, t2)
+            sc.record(prog, t2, y_even, nout)
+
+        def block_form():
+            self._record_block(prog, name, blk, cur, out, dtype, device)
+            self._record_block(prog, nname, nblk, out, nout, dtype, device)
+        if self.fuse_stage_exit == "force":
+            exit_form()
+            return nout
+        # a choice of the "bottleneck" family, with that family's option names: "fused" = the block fused with the conv behind it
+        # (the exit form), "convs" = that conv stays a launch of its own (today's launches of the two blocks)
+        prog.begin_choice(f"bottleneck|exit,{B},{cur.H},{cur.W},{cur.C},{nplanes},{cur.cstride}")
+        for form_name, form in (("fused", exit_form), ("convs", block_form)):
+            prog.option(form_name)
+            form()
+        prog.end_choice()
+        return nout
 
     def _record_block(self, prog, name: str, blk, cur, out, dtype, device) -> None:
         """One Bottleneck (blocks.py:83-120) from view `cur` into view `out` (both may be batch slices of larger buffers): the

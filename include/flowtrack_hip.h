@@ -273,6 +273,30 @@ int ft_bottleneck_fwd(const ft_bottleneck_desc* d, const void* x,
 /* algorithmic FLOPs of the three convs (2*MACs, no halo recompute) */
 double ft_bottleneck_flops(const ft_bottleneck_desc* d);
 
+/* Exit form of ft_bottleneck_fwd for a stage's LAST identity block (fp16, C = 256, P = 64, even H and W): the same block plus the
+ * 1x1 conv + bn + relu that opens the next stage (layer2.0.conv1 of the ResNets, 256 -> tail_cout = 128, resnet.py:37-43) in one
+ * launch.  Every 64-channel quarter of y is multiplied by its K-slice of the tail weights while it sits in LDS; t1 [N,H,W,128]
+ * (view t1_cstride / t1_coff, element units, multiples of 8) holds the same roundings as ft_bottleneck_fwd followed by the conv on y:
+ * only the fp32 summation order differs.  y_mode says what is written of y itself:
+ *   FT_BNK_Y_FULL  [N,H,W,C] as ft_bottleneck_fwd
+ *   FT_BNK_Y_EVEN  the even-row, even-column pixels only, compact: y = [N, H/2, W/2, C] with d->y_cstride / y_coff (what a
+ *                  stride-2 1x1 shortcut reads)
+ *   FT_BNK_Y_NONE  nothing (y may be NULL)
+ *   ft_bottleneck_exit_weight_bytes  size of the packed tail stream (0 when unsupported)
+ *   ft_bottleneck_exit_pack          builds it from the tail conv's ft_conv_pack_geometry layout ([cout_pad][kpad] fp16); once per
+ *                                    weight set
+ *   ft_bottleneck_exit_fwd           w1 / w2 / w3 / scale_shift as ft_bottleneck_fwd; tail_scale / tail_shift = the tail's folded
+ *                                    BatchNorm, float[tail_cout] each; t1 must alias neither x nor y. */
+enum { FT_BNK_Y_FULL = 0, FT_BNK_Y_EVEN = 1, FT_BNK_Y_NONE = 2 };
+int ft_bottleneck_exit_supported(const ft_bottleneck_desc* d, int tail_cout, int t1_cstride, int t1_coff, int y_mode);
+long long ft_bottleneck_exit_weight_bytes(const ft_bottleneck_desc* d, int tail_cout);
+int ft_bottleneck_exit_pack(const ft_bottleneck_desc* d, int tail_cout, const void* wt_packed, int kpad, int cout_pad, void* wstream,
+                            ft_stream_t stream);
+int ft_bottleneck_exit_fwd(const ft_bottleneck_desc* d, const void* x, const void* w1, const void* w2, const void* w3,
+                           const float* scale_shift, void* y, int y_mode, int tail_cout, const void* tail_wstream,
+                           const float* tail_scale, const float* tail_shift, void* t1, int t1_cstride, int t1_coff,
+                           ft_stream_t stream);
+
 /* Streamed-weights form of the same fusion for the 128- and 256-plane stages (fp16, C = 4P, P = 128 or 256, stride 1,
  * head_only = 0; ResNet layer2.1+ / layer3.1+): a workgroup owns a full-width strip of output rows of one image, keeps
  * t1 / t2 in LDS and streams the block's weights once through an LDS ring (csrc/bottleneck_stream.hip).
