@@ -350,7 +350,9 @@ int ft_bn_batch_stats(const void* x, int N, int H, int W, int C, int x_cstride, 
  * (first occurrence on ties), x = idx % W, y = idx / W (integer floor, torch
  * 0.4 semantics), coords zeroed where score <= 0, optional +/-0.25 px nudge.
  * heatmaps: NCHW fp32 [N,K,H,W]; idx int32 [N*K]; score fp32 [N*K];
- * coords fp32 [N*K*2] (x,y in heatmap pixels, before transform_preds). */
+ * coords fp32 [N*K*2] (x,y in heatmap pixels, before transform_preds).
+ * NaN is outside what the reference defines; the kernel promises only this: a NaN
+ * is never the arg-max, and a map of nothing but NaN gives idx 0 and coords (0, 0). */
 int ft_heatmap_max_preds(const float* heatmaps, int N, int K, int H, int W,
                          int adjust_coords, int32_t* idx, float* score,
                          float* coords, ft_stream_t stream);
