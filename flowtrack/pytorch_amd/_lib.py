@@ -20,6 +20,7 @@ FT_ERR_UNSUPPORTED = 2   # ft_status: valid but not implemented for this combina
 FT_F16, FT_F32 = 0, 1
 FT_ACT_NONE, FT_ACT_RELU, FT_ACT_LEAKY = 0, 1, 2
 FT_LAYOUT_NHWC, FT_LAYOUT_NCHW_F32 = 0, 1
+FT_CORR_FORM_VALU, FT_CORR_FORM_MFMA, FT_CORR_FORM_ROWS, FT_CORR_FORM_ROWS64 = 0, 1, 2, 3   # ft_correlation_nhwc_form
 FT_RGB_MEAN_SPLITS = 64
 FT_BNK_Y_FULL, FT_BNK_Y_EVEN, FT_BNK_Y_NONE = 0, 1, 2   # ft_bottleneck_exit_fwd: what is written of the block's own output
 
@@ -133,6 +134,7 @@ _PROTOTYPES = {
     "ft_upsample_bilinear4x": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "ft_correlation_out_shape": (c_int, [c_int] * 8 + [POINTER(c_int)] * 3),
     "ft_correlation_fwd": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 10 + [c_void_p]),
+    "ft_correlation_nhwc_form": (c_int, [c_int] * 10 + [c_float, c_int]),
     "ft_correlation_nhwc_fwd": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 10 + [c_float, c_int, c_void_p]),
     "ft_resample2d_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "ft_channelnorm_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),

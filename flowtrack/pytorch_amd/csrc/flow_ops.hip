@@ -64,6 +64,13 @@ __global__ __launch_bounds__(256) void correlation_nchw_kernel(const float* __re
 // for every displacement with one 32-thread block per pixel, correlation_cuda_kernel.cu:69-101).
 // Thread = (pixel x, group of GX horizontal displacements): the f1 chunk is loaded once per GX dots.
 // Results collect in an LDS tile and leave as contiguous D*D-channel runs per pixel.
+// act(v) = v > 0 ? v : k * v with torch's value for EVERY input and every slope: the negated ordered compare keeps a NaN and +inf,
+// ReLU takes a literal 0 (ReLU(-inf) = 0), leaky the IEEE product (slope 0 and -inf give NaN, as torch's x * negative_slope does;
+// act_mul's legacy multiply would return 0 there).  k = slope for FT_ACT_LEAKY, 1 for FT_ACT_NONE.
+__device__ __forceinline__ float corr_act(float v, int act, float k) {
+  return !(v <= 0.f) ? v : (act == FT_ACT_RELU ? 0.f : v * k);
+}
+
 template <typename T, int TX, int GX, int NT>
 __global__ __launch_bounds__(NT) void correlation_nhwc_kernel(const T* __restrict__ f1, const T* __restrict__ f2,
                                                                T* __restrict__ y, int C, int H, int W, int max_disp,
@@ -98,6 +105,7 @@ __global__ __launch_bounds__(NT) void correlation_nhwc_kernel(const T* __restric
   const int ngx = (D + GX - 1) / GX;  // displacement groups per pixel
   const int nwork = TX * ngx;
   const float inv_c = 1.0f / (float)C;
+  const float act_k = act == FT_ACT_LEAKY ? slope : 1.f;   // corr_act
 
   for (int dyi = 0; dyi < D; ++dyi) {
     const int y2 = yrow + (dyi - drad) * s2;
@@ -146,10 +154,7 @@ __global__ __launch_bounds__(NT) void correlation_nhwc_kernel(const T* __restric
       for (int e = 0; e < GX; ++e) {
         const int dxi = g * GX + e;
         if (dxi < D) {
-          float v = acc[e] * inv_c;
-          if (act == FT_ACT_RELU) v = v > 0.f ? v : 0.f;
-          else if (act == FT_ACT_LEAKY) v = v > 0.f ? v : v * slope;
-          s_out[px * DD + dyi * D + dxi] = v;
+          s_out[px * DD + dyi * D + dxi] = corr_act(acc[e] * inv_c, act, act_k);
         }
       }
     }
@@ -194,6 +199,7 @@ __global__ __launch_bounds__(256) void correlation_mfma_kernel(const half_t* __r
   const int wrows = 64 + 4 * drad;          // f2 window: pixels x0 - 2*drad ... x0 + 63 + 2*drad
   const int stage = ((wrows * ROWB + 1023) / 1024) * 1024;
   const float inv_c = 1.0f / (float)C;
+  const float act_k = act == FT_ACT_LEAKY ? slope : 1.f;   // corr_act
 
   // f1 fragments (operand A: row = f1 pixel of this parity, k = channel)
   uint4_t a[KS];
@@ -253,9 +259,7 @@ __global__ __launch_bounds__(256) void correlation_mfma_kernel(const half_t* __r
       const int x = x0 + 2 * r + par;
       const int dxi = c + 32 * jt - r;
       if (x < W && (unsigned)dxi < (unsigned)D) {
-        float v = acc[g] * inv_c;
-        if (act == FT_ACT_RELU) v = v > 0.f ? v : 0.f;
-        else if (act == FT_ACT_LEAKY) v = v > 0.f ? v : v * slope;
+        const float v = corr_act(acc[g] * inv_c, act, act_k);
         y[((size_t)(n * H + yrow) * W + x) * y_cstride + y_coff + dyi * D + dxi] = (half_t)v;
       }
     }
@@ -1520,22 +1524,67 @@ extern "C" int ft_correlation_fwd(const float* in1, const float* in2, float* out
   return FT_OK;
 }
 
+// The one place that decides which kernel a call of ft_correlation_nhwc_fwd runs, and with which sizes (pure host code:
+// ft_correlation_nhwc_form reports the form, the launch path takes everything from here).
+// The two rows kernels fold the activation into max(v * k_pos, v * k_neg), which is act(v) only for a slope in [0, 1] and is
+// not torch's value for a -inf sum when the slope is 0 (max(-inf, -inf * 0 = NaN) = -inf; torch: ReLU 0, leaky NaN): ReLU
+// and leaky slopes outside (0, 1] take the one-row kernel, whose corr_act is right for every slope and every input.
+struct CorrPlan {
+  int form;                          // FT_CORR_FORM_*
+  int D;                             // displacements per axis
+  unsigned long long f_bytes, y_bytes;
+  size_t lds;                        // dynamic LDS of the VALU form
+};
+
+static int correlation_nhwc_plan(int B, int C, int H, int W, int max_displacement, int stride2, int f_cstride, int y_cstride,
+                                 int y_coff, int act, float slope, int dtype, CorrPlan* p) {
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || max_displacement < 0 || stride2 <= 0) return FT_ERR_INVALID_ARG;
+  if (dtype != FT_F16 && dtype != FT_F32) return FT_ERR_INVALID_ARG;
+  if (C % 8 || f_cstride % 8 || f_cstride < C) return FT_ERR_INVALID_ARG;
+  p->D = (max_displacement / stride2) * 2 + 1;
+  if (y_coff < 0 || y_cstride < y_coff + p->D * p->D) return FT_ERR_INVALID_ARG;
+  const size_t esz = dtype_size(dtype);
+  p->f_bytes = (unsigned long long)B * H * W * f_cstride * esz;
+  p->y_bytes = (unsigned long long)B * H * W * y_cstride * esz;
+  p->lds = 0;
+  if (dtype == FT_F16 && stride2 == 2 && max_displacement % 2 == 0 && max_displacement <= 32 && C == 256 &&
+      p->f_bytes < (1ull << 31)) {
+    const bool rows_act_ok = act != FT_ACT_RELU && !(act == FT_ACT_LEAKY && !(slope > 0.f && slope <= 1.f));
+    if (max_displacement == 20 && p->y_bytes < (1ull << 31) && rows_act_ok)
+      p->form = W <= 64 && y_coff % 8 == 0 && y_cstride % 8 == 0 ? FT_CORR_FORM_ROWS64 : FT_CORR_FORM_ROWS;
+    else
+      p->form = FT_CORR_FORM_MFMA;
+    return FT_OK;
+  }
+  // fp16: 32-pixel tiles / 256 threads; fp32 (parity mode): 16-pixel tiles / 128 threads (LDS budget)
+  const size_t pstride = C * esz + 16;
+  const int tx = dtype == FT_F16 ? 32 : 16;
+  p->lds = (size_t)(tx + tx + 2 * max_displacement) * pstride + (size_t)tx * p->D * p->D * 4;
+  if (p->lds > 160 * 1024) return FT_ERR_UNSUPPORTED;
+  p->form = FT_CORR_FORM_VALU;
+  return FT_OK;
+}
+
+extern "C" int ft_correlation_nhwc_form(int B, int C, int H, int W, int max_displacement, int stride2, int f_cstride,
+                                        int y_cstride, int y_coff, int act, float slope, int dtype) {
+  CorrPlan p;
+  return correlation_nhwc_plan(B, C, H, W, max_displacement, stride2, f_cstride, y_cstride, y_coff, act, slope, dtype, &p) ==
+                 FT_OK ? p.form : -1;
+}
+
 extern "C" int ft_correlation_nhwc_fwd(const void* f1, const void* f2, void* y, int B, int C, int H, int W,
                                        int max_displacement, int stride2, int f_cstride, int y_cstride, int y_coff,
                                        int act, float slope, int dtype, ft_stream_t stream) {
-  if (!f1 || !f2 || !y || B <= 0 || C <= 0 || H <= 0 || W <= 0 || max_displacement < 0 || stride2 <= 0)
-    return FT_ERR_INVALID_ARG;
-  if (dtype != FT_F16 && dtype != FT_F32) return FT_ERR_INVALID_ARG;
-  if (C % 8 || f_cstride % 8 || f_cstride < C) return FT_ERR_INVALID_ARG;
-  const int D = (max_displacement / stride2) * 2 + 1;
-  if (y_coff < 0 || y_cstride < y_coff + D * D) return FT_ERR_INVALID_ARG;
-  const size_t esz = dtype_size(dtype);
-  const unsigned long long f_bytes = (unsigned long long)B * H * W * f_cstride * esz;
-  if (dtype == FT_F16 && stride2 == 2 && max_displacement % 2 == 0 && max_displacement <= 32 && C == 256 &&
-      f_bytes < (1ull << 31)) {
+  if (!f1 || !f2 || !y) return FT_ERR_INVALID_ARG;
+  CorrPlan plan;
+  const int st = correlation_nhwc_plan(B, C, H, W, max_displacement, stride2, f_cstride, y_cstride, y_coff, act, slope, dtype,
+                                       &plan);
+  if (st != FT_OK) return st;
+  const int form = plan.form;
+  const unsigned long long f_bytes = plan.f_bytes, y_bytes = plan.y_bytes;
+  if (form != FT_CORR_FORM_VALU) {
     const int drad = max_displacement / 2;
-    const unsigned long long y_bytes = (unsigned long long)B * H * W * y_cstride * 2;
-    if (drad == 10 && y_bytes < (1ull << 31) && W <= 64 && y_coff % 8 == 0 && y_cstride % 8 == 0) {
+    if (form == FT_CORR_FORM_ROWS64) {
       // FlowNetC's shape on maps up to 64 wide: 64-column ring slots, six waves, 3 output rows per workgroup
       static const int cdbg = ft::dev_env_int("FT_CORR_DBG", 0);   // dev ablation, timing only: see the kernel
       constexpr int R = 3;
@@ -1555,7 +1604,7 @@ extern "C" int ft_correlation_nhwc_fwd(const void* f1, const void* f2, void* y, 
       FT_LAUNCH_CHECK("correlation_mfma_rows64_kernel");
       return FT_OK;
     }
-    if (drad == 10 && y_bytes < (1ull << 31)) {     // FlowNetC's shape: 3 output rows per workgroup
+    if (form == FT_CORR_FORM_ROWS) {     // FlowNetC's shape: 3 output rows per workgroup
       constexpr int R = 3;
       auto k = correlation_mfma_rows_kernel<16, R, 10>;
       constexpr size_t lds3 = 3 * (((size_t)(64 + 40) * 512 + 1023) / 1024 * 1024);
@@ -1584,12 +1633,8 @@ extern "C" int ft_correlation_nhwc_fwd(const void* f1, const void* f2, void* y, 
     FT_LAUNCH_CHECK("correlation_mfma_kernel");
     return FT_OK;
   }
-  const size_t pstride = C * esz + 16;
-  // fp16: 32-pixel tiles / 256 threads; fp32 (parity mode): 16-pixel tiles / 128 threads (LDS budget)
-  const int tx = dtype == FT_F16 ? 32 : 16;
-  const size_t lds = (size_t)(tx + tx + 2 * max_displacement) * pstride + (size_t)tx * D * D * 4;
-  if (lds > 160 * 1024) return FT_ERR_UNSUPPORTED;
-  dim3 grid(ceil_div(W, tx) * H, B);
+  const size_t lds = plan.lds;
+  dim3 grid(ceil_div(W, dtype == FT_F16 ? 32 : 16) * H, B);
   if (dtype == FT_F16) {
     auto k = correlation_nhwc_kernel<half_t, 32, kCorrGX, 256>;
     if (lds > 64 * 1024) FT_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

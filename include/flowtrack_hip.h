@@ -455,7 +455,32 @@ int ft_correlation_fwd(const float* in1, const float* in2, float* out, int B,
                        int corr_type_multiply, ft_stream_t stream);
 /* Fused in-network form (FlowNetC.py:86-92): NHWC `dtype` features in, the
  * LeakyReLU'd cost volume written into channels [y_coff, y_coff+D*D) of an
- * NHWC concat buffer.  kernel_size=1, stride1=1, pad=max_displacement. */
+ * NHWC concat buffer.  kernel_size=1, stride1=1, pad=max_displacement.
+ *   y[pix, y_coff + (dy+r)*D + (dx+r)] = act(1/C * sum_c f1[pix, c] * f2[pix + stride2*(dy, dx), c]),
+ *   act(v) = v > 0 ? v : k * v with k = 0 (FT_ACT_RELU), slope (FT_ACT_LEAKY, any finite slope) or 1 (FT_ACT_NONE), and
+ *   torch's value for a NaN / +inf / -inf sum (NaN, +inf, the IEEE product k * -inf — NaN at slope 0; ReLU(-inf) = 0).
+ * One of four kernels runs (csrc/flow_ops.hip); ft_correlation_nhwc_form tells which without touching a device:
+ *
+ *   id                    kernel                                  chosen when
+ *   FT_CORR_FORM_ROWS64   correlation_mfma_rows64_kernel<16,3,10> fp16, C = 256, stride2 = 2, max_displacement = 20, features and
+ *                         (3 rows per workgroup, W <= 64)         output below 2 GiB, act none or leaky with slope in (0, 1],
+ *                                                                 W <= 64, y_coff % 8 == 0 and y_cstride % 8 == 0
+ *   FT_CORR_FORM_ROWS     correlation_mfma_rows_kernel<16,3,10>   as above with W > 64, or y_coff % 8, or y_cstride % 8
+ *                         (3 rows, 104-column window)
+ *   FT_CORR_FORM_MFMA     correlation_mfma_kernel<16>             fp16, C = 256, stride2 = 2, even max_displacement <= 32, features
+ *                         (one row per workgroup)                 below 2 GiB, and not a rows form: max_displacement != 20, or
+ *                                                                 ReLU, or a leaky slope outside (0, 1], or an output >= 2 GiB
+ *   FT_CORR_FORM_VALU     correlation_nhwc_kernel<half,32,..>     everything else: fp32 always; fp16 when C != 256, stride2 != 2,
+ *                         / <float,16,..>                         an odd or > 32 max_displacement, or features >= 2 GiB
+ *
+ * ft_correlation_nhwc_form returns the id, or -1 where ft_correlation_nhwc_fwd refuses the call: FT_ERR_INVALID_ARG (sizes
+ * <= 0, C % 8, f_cstride % 8, f_cstride < C, a slice [y_coff, y_coff + D*D) outside y_cstride, an unknown dtype) and the
+ * FT_ERR_UNSUPPORTED of the VALU form when (2*tile + 2*max_displacement) * (C * elem + 16) + tile * D*D * 4 bytes of LDS
+ * (tile = 32 pixels fp16, 16 fp32) exceed 160 KiB. */
+enum { FT_CORR_FORM_VALU = 0, FT_CORR_FORM_MFMA = 1, FT_CORR_FORM_ROWS = 2, FT_CORR_FORM_ROWS64 = 3 };
+int ft_correlation_nhwc_form(int B, int C, int H, int W, int max_displacement,
+                             int stride2, int f_cstride, int y_cstride,
+                             int y_coff, int act, float slope, int dtype);
 int ft_correlation_nhwc_fwd(const void* f1, const void* f2, void* y, int B,
                             int C, int H, int W, int max_displacement,
                             int stride2, int f_cstride, int y_cstride,
