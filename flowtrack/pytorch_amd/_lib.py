@@ -108,6 +108,7 @@ _PROTOTYPES = {
     "ft_bottleneck_stream_supported": (c_int, [POINTER(BottleneckDesc)]),
     "ft_bottleneck_stream_folds": (c_int, [POINTER(BottleneckDesc)]),
     "ft_bottleneck_stream_layout": (c_int, [POINTER(BottleneckDesc)]),
+    "ft_bottleneck_stream_variant": (c_int, [POINTER(BottleneckDesc)]),
     "ft_bottleneck_stream_weight_bytes": (ctypes.c_longlong, [POINTER(BottleneckDesc)]),
     "ft_bottleneck_stream_pack": (c_int, [POINTER(BottleneckDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ft_bottleneck_stream_fwd": (c_int, [POINTER(BottleneckDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

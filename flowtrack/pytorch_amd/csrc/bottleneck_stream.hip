@@ -1766,6 +1766,494 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
 #endif
 }
 
+// ---- 128 planes, weights straight to registers (folded operands, four waves) ---------------------------------------------------
+// bottleneck_stream_kernel<128, MT1, MT2, true> with the weight path of bottleneck_stream_direct_kernel.  At 128 planes the waves are
+// WCOLS 2 x WPG 2: the two pixel groups of a wave column multiply the SAME weight fragments, which is why the ring kernel shares them
+// through LDS — and pays for it with (2 A + 3 B) ds_read_b128 per 6 MFMAs at one wave per SIMD and a workgroup barrier at every 16-KiB
+// weight step (34 per strip).  Here every wave loads its own 8 x 1 KiB of a step (kk, tile 2 wcol + i at g * WSTEP + (kk * NCT + 2 wcol
+// + i) KiB of the unchanged bns_pack_kernel<128> stream) straight into VGPRs NS - 1 steps ahead: the stream reaches a CU twice (32 KiB
+// per step, half of what the 256-plane direct kernels pull through the same path per MFMA cycle), the A operand never crosses LDS, the
+// ring barriers are gone (phases 2 and 3 meet only at the phase transitions and at the output tile of a quarter) and the 48 KiB of the
+// ring hold a second output staging tile, so that the write of quarter q + 1 never waits behind the stores of quarter q.
+// Everything else is the ring kernel's plan: x-chunk ring -> T1 -> T2, zero row, x-border lane masks, residual picked out of the x
+// chunks, shift and residual MFMAs, relu_acc16 epilogues, whole-line stores.  Every accumulator sees the same MFMAs on the same fp16
+// operands in the same order as in the ring kernel: the two forms are bit-identical.
+// LDS (160 KiB): [0, 96 K) x-chunk buffers / [0, 64 K) T1 / [0, 48 K) T2, staging tile 0 at 48 K (phase 3), zero row at 97 K, scratch
+// of the L2 touch at 100 K, staging tile 1 at 112 K.
+// Registers decide the shape (residual 64 MT2, phase 1's accumulators 32 MT1, 32 per weight slot, 8 MT1 for the x fragments):
+//   <4, 3, NS = 2>  504 registers, 160 KiB of LDS, scratch 0.  NS = 3 spills (512 registers + 180 B of scratch; 132 B with the shift pairs
+//                   of epilogues 1 .. 5 loaded behind phase 1 as they are now; the same 132 B with phase 1's x fragments single-buffered),
+//                   so the large strips prefetch ONE step ahead: a step is 768-1024 MFMA cycles, an L2 hit ~500.
+//   <3, 2, NS = 3>  422 registers, 160 KiB of LDS, scratch 0.
+template <int MT1, int MT2, int NS>
+__global__ __launch_bounds__(256, 1) void bottleneck_stream_direct128_kernel(const BnsParams p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  constexpr int P = 128;
+  using G = BnsGeom<P>;
+  constexpr int NCT = G::NCT, WCOLS = G::WCOLS, WPG = G::WPG, NC1 = G::NC1, KC = G::KC, WSTEP = G::WSTEP, ROWB = G::ROWB;
+  constexpr int G2 = G::G2, G3 = G::G3, GEND = G::GEND;
+  constexpr int XROWS = WPG * MT1 * 32, LX = WPG * MT1;     // rows of an x chunk buffer; 1-KiB x loads per wave per chunk
+  constexpr int NOUT = WPG * MT2 * 32;                       // output pixels of the strip (padded)
+  constexpr int STG0 = G::STG, STG1 = G::WBASE, STGB = NOUT * ROWB, SCR = 102400;
+  static_assert(XROWS * 128 <= G::XSTRIDE && XROWS * ROWB <= G::TAB && STGB <= STG0 && STG0 + STGB <= G::TAB, "LDS map: T1, T2, staging tile 0");
+  static_assert(SCR >= G::ZROW + ROWB && SCR + 1024 <= STG1 && STG1 + STGB <= G::LDS_BYTES, "LDS map: scratch, staging tile 1");
+  static_assert(NS >= 2 && (3 * KC) % NS == 0, "ring phase of the unrolled phase-2 body");
+  constexpr int D = NS - 1;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  typedef __attribute__((address_space(3))) void* lds_ptr;
+  using c0 = std::integral_constant<int, 0>;
+  using c1 = std::integral_constant<int, 1>;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wcol = wave % WCOLS, pg = wave / WCOLS;
+  const int l31 = lane & 31, lhi = lane >> 5;
+
+  int logical;
+  {
+    const int b = blockIdx.x;
+    const int q = p.total >> 3, r = p.total & 7, xcd = b & 7, loc = b >> 3;
+    logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+  }
+  const int n = logical / p.ppi;
+  const int y0 = (logical - n * p.ppi) * p.TH;
+  const int W = p.W;
+  const int rows_out = p.H - y0 < p.TH ? p.H - y0 : p.TH;
+  const int npix_out = rows_out * W;
+  const int npix_halo = (p.TH + 2) * W;
+
+  const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.x), 0, p.x_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.ws), 0, p.ws_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.tab), 0, (2 * P + G::C) * 4, 0x00020000);
+  constexpr unsigned kOOB = 0x80000000u;
+
+  // x chunk: row = halo pixel, 128 bytes (64 channels); see the ring kernel
+  unsigned x_voff[LX];
+#pragma unroll
+  for (int t = 0; t < LX; ++t) {
+    const int hp = (t * 4 + wave) * 8 + (lane >> 3);
+    const int hr = hp / W, hc = hp - hr * W;
+    const int iy = y0 - 1 + hr;
+    unsigned v = kOOB;
+    if (hp < npix_halo && (unsigned)iy < (unsigned)p.H)
+      v = (unsigned)((((n * p.H + iy) * W + hc) * p.x_cstride + p.x_coff) * 2 + (((lane & 7) ^ BNS_XKEY(hp)) << 4));
+    x_voff[t] = v;
+  }
+  const unsigned lane16 = (unsigned)lane * 16u;
+  auto issue_x = [&](int c, int buf) {
+    char* dst = smem + buf * G::XSTRIDE;
+#pragma unroll
+    for (int t = 0; t < LX; ++t)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (lds_ptr)(dst + (t * 4 + wave) * 1024), 16, x_voff[t], c * 128, 0, 0);
+  };
+  // the weight fragments of step g for this wave: (kk, tile 2*wcol + i) at g * WSTEP + (kk * NCT + 2*wcol + i) KiB; both pixel groups of a
+  // wave column load the same ones.  Steps past the end of the stream: out of range by the lane offset, zeros, never multiplied.
+  uint4_t areg[NS][4][2];
+  auto load_a_half = [&](auto slotc, int g, auto halfc) {   // K16 slices {0, 1} or {2, 3} of the step
+    constexpr int SL = decltype(slotc)::value, HF = decltype(halfc)::value;
+    const unsigned vo = g < GEND ? lane16 : kOOB;
+#pragma unroll
+    for (int kk = 2 * HF; kk < 2 * HF + 2; ++kk)
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        areg[SL][kk][i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_w, vo, g * WSTEP + (kk * NCT + 2 * wcol + i) * 1024, 0);
+  };
+  auto load_a = [&](auto slotc, int g) {
+    load_a_half(slotc, g, c0{});
+    load_a_half(slotc, g, c1{});
+  };
+  unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  BNSD_TS(0);
+  // the first round of workgroups on an XCD pulls the block's weight stream into that XCD's L2 (see the direct kernel): EXACTLY kTouch
+  // loads per thread, issued behind x chunk 0 and the weights of step 0 and counted by the first hand-counted wait
+  constexpr int kTouch = 6;
+  auto issue_touch = [&]() {
+    const bool on = blockIdx.x < 256 && !(p.dbg & 512);
+    const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
+    const int first = p.total < 256 ? p.total : 256;
+    const int nloc = (first - xcd + 7) >> 3;
+    const unsigned lines = (p.ws_bytes + 127u) >> 7;
+    const unsigned per = (lines + nloc - 1) / nloc;
+    const unsigned lo = loc * per, hi = lo + per < lines ? lo + per : lines;
+#pragma unroll
+    for (int k = 0; k < kTouch; ++k) {
+      const unsigned l = lo + tid + 256u * k;
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (lds_ptr)(smem + SCR + wave * 256), 4, (on && l < hi) ? l << 7 : kOOB, 0, 0, 0);
+    }
+  };
+  // folded operands: the shift pair of MFMA row l31 of every (epilogue, channel tile) of this wave and the residual's 0/1 matrix (see
+  // the direct kernel)
+  unsigned shp[6][2];
+  uint4_t permA[2];
+  const uint4_t onesB = uint4_t{0x3C003C00u, 0u, 0u, 0u};
+  {
+    const int sg = bns_sigma(l31);
+    const bool on = lhi == (sg >> 4);
+    const int ph = (sg >> 3) & 1, pe = sg & 7;
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      unsigned w[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) w[k] = (on && ph == hh && (pe >> 1) == k) ? (0x3C00u << (16 * (pe & 1))) : 0u;
+      permA[hh] = uint4_t{w[0], w[1], w[2], w[3]};
+    }
+  }
+  // (the pairs of epilogue 0 in the prologue, those of epilogues 1 .. 5 behind phase 1's loop, where the registers are free again)
+  constexpr int kTabLoads = 2;
+  auto load_shp = [&](int e0, int e1) {
+    const unsigned so = lhi == 0 ? 4u * (unsigned)bns_sigma(l31) : kOOB;
+#pragma unroll
+    for (int e = e0; e < e1; ++e)
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        shp[e][i] = __builtin_amdgcn_raw_buffer_load_b32(rsrc_t, so, 4 * (e * P + (2 * wcol + i) * 32), 0);
+  };
+  auto add_shift = [&](int e, auto& A, auto mtc) {      // A[i][j] += shift of epilogue e (one MFMA per tile)
+    constexpr int MT = decltype(mtc)::value;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const uint4_t sa = uint4_t{shp[e][i], 0u, 0u, 0u};
+#pragma unroll
+      for (int j = 0; j < MT; ++j)
+        A[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, sa), __builtin_bit_cast(half8_t, onesB), A[i][j], 0, 0, 0);
+    }
+  };
+  // order of every wave's (in-order) load queue: x chunk 0, the weights of step 0, the L2 touch, the shift pairs, x chunk 1, the weights
+  // of steps 1 .. D-1, x chunk 2 (the order of the steady state: weights of step c+1 between x chunks c+1 and c+2).  The first wait
+  // counts them: compiler fences on both sides of the touch / shift group.
+  issue_x(0, 0);
+  load_a(c0{}, 0);
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  issue_touch();
+  load_shp(0, 1);
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  issue_x(1, 1);
+  bns_unroll<D - 1>([&](auto sc) { load_a(std::integral_constant<int, decltype(sc)::value + 1>{}, decltype(sc)::value + 1); });
+  issue_x(2, 2);
+  if (tid < ROWB / 16) *reinterpret_cast<uint4_t*>(smem + G::ZROW + tid * 16) = uint4_t{0u, 0u, 0u, 0u};
+
+  // residual = the block input at the strip's own pixels, in phase 3's accumulator layout: [quarter][tile i][pixel tile j][half]
+  uint4_t res[4][2][MT2][2];
+  int m_out[MT2];       // output pixel (strip-relative, row-major at width W) of this lane per pixel tile
+#pragma unroll
+  for (int j = 0; j < MT2; ++j) m_out[j] = (pg * MT2 + j) * 32 + l31;
+
+  // ================= phase 1: t1 = relu(W1' . x + shift1) on the halo strip ===========================================================
+  float16_t acc1[2][MT1];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < MT1; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc1[i][j][r] = 0.f;
+  int b1_off[MT1];
+#pragma unroll
+  for (int j = 0; j < MT1; ++j) {
+    const int hp = (pg * MT1 + j) * 32 + l31;
+    b1_off[j] = hp * 128 + ((lhi ^ BNS_XKEY(hp)) << 4);
+  }
+  {
+    uint4_t fx[2][MT1];
+    auto ldx = [&](auto setc, int buf, int kk) {
+      constexpr int S = decltype(setc)::value;
+      const char* xb = smem + buf * G::XSTRIDE;
+#pragma unroll
+      for (int j = 0; j < MT1; ++j) fx[S][j] = *reinterpret_cast<const uint4_t*>(xb + (b1_off[j] ^ (kk << 5)));
+    };
+    auto mma1 = [&](auto setc, auto slotc, auto kkc) {
+      constexpr int S = decltype(setc)::value, SL = decltype(slotc)::value, kk = decltype(kkc)::value;
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < MT1; ++j)
+          acc1[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, areg[SL][kk][i]),
+                                                              __builtin_bit_cast(half8_t, fx[S][j]), acc1[i][j], 0, 0, 0);
+    };
+    // x chunk 0 has landed (this wave's share): behind it the weights of steps 0 .. D-1 (8 loads each), the touch, the shift pairs and
+    // x chunks 1 and 2 may fly
+    static_assert(2 * LX + 8 * D + kTouch + kTabLoads <= 63, "vmcnt immediate");
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * LX + 8 * D + kTouch + kTabLoads) : "memory");
+    BNS_BARRIER();
+    BNSD_TS(7);             // start-up: x chunk 0 of every wave has landed
+    ldx(c0{}, 0, 0);
+    bns_unroll<NC1>([&](auto cc) {
+      constexpr int c = decltype(cc)::value;
+      constexpr int buf = c % 3;
+      using slot = std::integral_constant<int, c % NS>;
+      // two scheduling regions per chunk (the wave-uniform branch of the residual pick-up splits it), each with half of the step's
+      // weight loads and the direct kernel's pinned issue order: one vector-memory load and the LDS reads behind every two MFMAs
+      load_a_half(std::integral_constant<int, (c + D) % NS>{}, c + D, c0{});
+      ldx(c1{}, buf, 1);
+      mma1(c0{}, slot{}, std::integral_constant<int, 0>{});
+      ldx(c0{}, buf, 2);
+      __builtin_amdgcn_sched_group_barrier(0x020, LX, 0);
+      bns_unroll<3>([&](auto) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, (2 * MT1 + 2) / 3, 0);
+        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+      });
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, (MT1 + 2) / 3, 0);
+      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+      bns_unroll<MT1 - 1>([&](auto) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, (MT1 + 2) / 3, 0);
+      });
+      if (c % WCOLS == wcol) {       // this chunk holds the channels of this wave column for quarter c / WCOLS
+        constexpr int q = c / WCOLS;
+        const char* xb = smem + buf * G::XSTRIDE;
+#pragma unroll
+        for (int j = 0; j < MT2; ++j) {
+          const int hp = m_out[j] + W;
+          const char* rowp = xb + hp * 128;
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+              res[q][i][j][h] = *reinterpret_cast<const uint4_t*>(rowp + (((4 * i + 2 * lhi + h) ^ BNS_XKEY(hp)) << 4));
+        }
+      }
+      mma1(c1{}, slot{}, std::integral_constant<int, 1>{});
+      load_a_half(std::integral_constant<int, (c + D) % NS>{}, c + D, c1{});
+      ldx(c1{}, buf, 3);
+      mma1(c0{}, slot{}, std::integral_constant<int, 2>{});
+      bns_unroll<MT1>([&](auto) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      });
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x020, 4 - MT1 > 0 ? 4 - MT1 : 0, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 4 * MT1 - 2 * MT1 - 2, 0);
+      if constexpr (c + 1 < NC1) {
+        // x chunk c+1 has landed and every read of chunk c's buffer is complete: refill it with chunk c+3.  Younger than x chunk c+1 are the weights of step c+1 (D = 2: needed next anyway, waited for), x
+        // chunk c+2 and the weights of step c+D (8 loads); with D = 3 the weights of step c+2 sit in between and stay in flight too.
+        if constexpr (c + 2 < NC1) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(LX + (D <= 2 ? 8 : 16)) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(D <= 2 ? 8 : 16) : "memory");
+        BNS_BARRIER();
+        if constexpr (c + 3 < NC1) issue_x(c + 3, buf);
+        ldx(c0{}, (c + 1) % 3, 0);
+      }
+      mma1(c1{}, slot{}, std::integral_constant<int, 3>{});
+    });
+  }
+  BNSD_TS(1);
+  load_shp(1, 6);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  BNS_BARRIER();          // every wave is past its last x-chunk read: the x buffers become T1
+  {
+    add_shift(0, acc1, std::integral_constant<int, MT1>{});
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+      for (int j = 0; j < MT1; ++j) {
+        const int hp = (pg * MT1 + j) * 32 + l31;
+        const int hr = hp / W;
+        const int iy = y0 - 1 + hr;
+        const bool inside = (unsigned)iy < (unsigned)p.H;     // out-of-image halo rows are conv2's zero padding
+        half8_t h8[2];
+        relu_acc16(acc1[i][j], h8);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          uint4_t u = __builtin_bit_cast(uint4_t, h8[h]);
+          u.x = inside ? u.x : 0u; u.y = inside ? u.y : 0u; u.z = inside ? u.z : 0u; u.w = inside ? u.w : 0u;
+          h8[h] = __builtin_bit_cast(half8_t, u);
+        }
+        if (hp < npix_halo) {
+          char* rowp = smem + hp * ROWB;
+          const int cb = (2 * wcol + i) * 4 + 2 * lhi;
+#pragma unroll
+          for (int h = 0; h < 2; ++h)
+            *reinterpret_cast<half8_t*>(rowp + (((cb + h) ^ (hp & 15)) << 4)) = h8[h];
+        }
+      }
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  BNS_BARRIER();          // T1 complete
+  BNSD_TS(2);
+
+  // ================= phases 2 + 3: weight steps G2 .. GEND-1, pixel operand from T1 / T2 ==============================================
+  float16_t acc[2][MT2];
+  auto zero_acc = [&]() {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < MT2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  };
+  zero_acc();
+  // x-border flags of this lane's output pixels: bit 0 = first column (tap kx = 0 is padding), bit 1 = last column
+  int edge[MT2];
+#pragma unroll
+  for (int j = 0; j < MT2; ++j) {
+    const int ox = m_out[j] % W;
+    edge[j] = (ox == 0 ? 1 : 0) | (ox == W - 1 ? 2 : 0);
+  }
+  auto row_bases = [&](int off, int kc, int bad, int (&rb)[MT2]) {
+#pragma unroll
+    for (int j = 0; j < MT2; ++j) {
+      const int row = m_out[j] + off;
+      const int v = row * ROWB + (((row & 15) ^ lhi) << 4);
+      rb[j] = ((edge[j] & bad) ? G::ZROW + (lhi << 4) : v) ^ (kc << 7);
+    }
+  };
+  uint4_t fb[2][MT2];
+  auto ldb = [&](auto setc, int kk, const int (&rb)[MT2]) {
+    constexpr int S = decltype(setc)::value;
+#pragma unroll
+    for (int j = 0; j < MT2; ++j) fb[S][j] = *reinterpret_cast<const uint4_t*>(smem + (rb[j] ^ (kk << 5)));
+  };
+  auto mma2 = [&](auto setc, auto slotc, auto kkc) {
+    constexpr int S = decltype(setc)::value, SL = decltype(slotc)::value, kk = decltype(kkc)::value;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < MT2; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, areg[SL][kk][i]),
+                                                           __builtin_bit_cast(half8_t, fb[S][j]), acc[i][j], 0, 0, 0);
+  };
+  // one weight step g (register slot SL = g % NS): slice 0 of the pixel operand already sits in register set 0; `rbn` = row bases of
+  // the next step.  Issue order as in the direct kernel: one weight load and the pixel-operand reads after every MT2 MFMAs.
+  auto dstep = [&](auto slotc, int g, const int (&rb)[MT2], bool has_next, const int (&rbn)[MT2]) {
+    constexpr int SL = decltype(slotc)::value;
+    using slot = std::integral_constant<int, SL>;
+    load_a(std::integral_constant<int, (SL + D) % NS>{}, g + D);
+    ldb(c1{}, 1, rb);
+    mma2(c0{}, slot{}, std::integral_constant<int, 0>{});
+    ldb(c0{}, 2, rb);
+    mma2(c1{}, slot{}, std::integral_constant<int, 1>{});
+    ldb(c1{}, 3, rb);
+    mma2(c0{}, slot{}, std::integral_constant<int, 2>{});
+    if (has_next) ldb(c0{}, 0, rbn);
+    mma2(c1{}, slot{}, std::integral_constant<int, 3>{});
+    bns_unroll<8>([&](auto ic) {
+      constexpr int i = decltype(ic)::value;
+      __builtin_amdgcn_sched_group_barrier(0x008, MT2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, (i & 1) ? (MT2 + 1) / 2 : MT2 / 2, 0);
+    });
+  };
+
+  // ---- phase 2: nine taps x KC chunks, three taps per loop trip (6 steps: a multiple of the register ring period) --------------------
+  {
+    int rb[MT2], rbn[MT2];
+    row_bases(-1, 0, 1, rb);                         // tap (0, 0), chunk 0
+    ldb(c0{}, 0, rb);
+    for (int ky = 0; ky < 3; ++ky) {
+      bns_unroll<3 * KC>([&](auto sc) {
+        constexpr int s = decltype(sc)::value;
+        constexpr int kx = s / KC, kc = s % KC;
+        constexpr int nkc = (kc + 1) % KC, nkx = kc + 1 == KC ? (kx + 1) % 3 : kx;
+        const int nky = (kc + 1 == KC && kx == 2) ? ky + 1 : ky;
+        row_bases(nky * W + nkx - 1, nkc, nkx == 0 ? 1 : (nkx == 2 ? 2 : 0), rbn);
+        dstep(std::integral_constant<int, (G2 + s) % NS>{}, G2 + 3 * KC * ky + s, rb, !(ky == 2 && s == 3 * KC - 1), rbn);
+#pragma unroll
+        for (int j = 0; j < MT2; ++j) rb[j] = rbn[j];
+      });
+    }
+  }
+  BNSD_TS(3);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  BNS_BARRIER();          // every wave is past its last T1 read: T2 overwrites T1
+  {
+    add_shift(1, acc, std::integral_constant<int, MT2>{});
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+      for (int j = 0; j < MT2; ++j) {
+        const int m = m_out[j];
+        half8_t h8[2];
+        relu_acc16(acc[i][j], h8);
+        char* rowp = smem + m * ROWB;
+        const int cb = (2 * wcol + i) * 4 + 2 * lhi;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) *reinterpret_cast<half8_t*>(rowp + (((cb + h) ^ (m & 15)) << 4)) = h8[h];
+      }
+    }
+  }
+  zero_acc();
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  BNS_BARRIER();          // T2 complete
+  BNSD_TS(4);
+
+  // ---- phase 3: four quarters of P output channels, K = P; the tile of a quarter leaves through one of two LDS staging tiles ---------
+  {
+    // read-out: thread -> 16-byte chunk tid % 16 of the whole 256-byte lines of pixels tid / 16 + 16 k (the row key m & 15 is the same
+    // for every k, so the LDS offsets and the output offsets are one base each plus a constant / wave-uniform step)
+    constexpr int CPR = ROWB / 16, NSTG = NOUT * CPR / 256;
+    static_assert(CPR == 16, "read-out map");
+    const int m0 = tid >> 4, sch = tid & 15;
+    const unsigned y_base = (unsigned)((((n * p.H + y0) * W + m0) * p.y_cstride + p.y_coff + sch * 8) * 2);
+    const unsigned y_step = (unsigned)(16 * p.y_cstride * 2);
+    const int s_off0 = m0 * ROWB + ((sch ^ (m0 & 15)) << 4);
+    int rb[MT2], rbn[MT2];
+    row_bases(0, 0, 0, rb);
+    ldb(c0{}, 0, rb);
+    bns_unroll<4>([&](auto qc) {
+      constexpr int q = decltype(qc)::value;
+      bns_unroll<KC>([&](auto kcc) {
+        constexpr int kc = decltype(kcc)::value;
+        constexpr int g = G3 + q * KC + kc;
+        row_bases(0, (kc + 1) % KC, 0, rbn);
+        dstep(std::integral_constant<int, g % NS>{}, g, rb, g + 1 < GEND, rbn);
+#pragma unroll
+        for (int j = 0; j < MT2; ++j) rb[j] = rbn[j];
+      });
+      char* stg = smem + ((q & 1) ? STG1 : STG0);
+      // shift3 of the quarter and the residual join the accumulators as three MFMAs per tile
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const uint4_t sa = uint4_t{shp[2 + q][i], 0u, 0u, 0u};
+#pragma unroll
+        for (int j = 0; j < MT2; ++j) {
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, sa), __builtin_bit_cast(half8_t, onesB), acc[i][j], 0, 0, 0);
+#pragma unroll
+          for (int h = 0; h < 2; ++h)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, permA[h]), __builtin_bit_cast(half8_t, res[q][i][j][h]),
+                                                               acc[i][j], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < MT2; ++j) {
+          half8_t o8[2];
+          relu_acc16(acc[i][j], o8);
+          const int m = m_out[j];
+#pragma unroll
+          for (int h = 0; h < 2; ++h)
+            *reinterpret_cast<half8_t*>(stg + m * ROWB + ((((2 * wcol + i) * 4 + 2 * lhi + h) ^ (m & 15)) << 4)) = o8[h];
+        }
+      zero_acc();
+      // the two staging tiles alternate: the readers of this tile's previous content (quarter q-2) passed the barrier of quarter q-1
+      // with their LDS reads complete, so ONE barrier per quarter (tile complete) is all the hand-over needs
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      BNS_BARRIER();
+#pragma unroll
+      for (int k = 0; k < NSTG; ++k) {
+        const uint4_t v = *reinterpret_cast<const uint4_t*>(stg + s_off0 + k * 16 * ROWB);
+        const unsigned vo = m0 + 16 * k < npix_out ? y_base + (unsigned)k * y_step + (unsigned)(q * P * 2) : kOOB;
+        if (!(p.dbg & 4)) __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_y, vo, 0, FT_YSTORE_BUF_AUX);
+      }
+    });
+  }
+  if (p.dbg & 32) {       // dev: phase timestamps of wave 0 over the strip's first output pixel (the output is garbage then)
+    ts[5] = __builtin_amdgcn_s_memtime();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    ts[6] = __builtin_amdgcn_s_memtime();
+    if (tid == 0) {
+      unsigned long long* o = reinterpret_cast<unsigned long long*>(p.y + ((size_t)((n * p.H + y0) * W) * p.y_cstride + p.y_coff) * 2);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o[i] = ts[i];
+    }
+  }
+#endif
+}
+
 // ---- weight stream packing -------------------------------------------------------------------------------------------
 // w1 [P][C], w2 [P][9P] (k = tap * P + ci), w3 [C][P]: the K-major layouts of ft_conv_pack_geometry.  One thread per
 // 16-byte piece of the stream: step g, slice kk, channel tile i, lane -> 8 consecutive k of one output channel.
@@ -1850,9 +2338,20 @@ __global__ __launch_bounds__(256) void bns_pack_head_kernel(const half_t* __rest
 struct BnsPlan {
   int variant;   // 0: <128,4,3>  1: <256,4,3>  2: <256,3,2>  3: <256,2,1> column-split (direct kernel only)  4: stride-2 head <4,1>
                  // 5: <128,3,2>  6: 256 planes on 16-pixel tiles (bottleneck_stream_tile16_kernel; its own stream layout)
+                 // 7: <128,4,3> weights straight to registers (bottleneck_stream_direct128_kernel)  8: <128,3,2> likewise
   int TH, ppi;
   int TWc, csplit;
 };
+
+// the rule's choice at 128 planes, per strip size: 1 = bottleneck_stream_direct128_kernel for folded descriptors.  Measured in situ
+// (profiles/HISTORY.md): large strips, R50 batch 64: 42.2 -> 38.0 us per block, +1.35 % on the step; small strips, R101 384x288 at 16
+// crops: +0.4 % on the step
+#ifndef FT_BNS_DIRECT128_LARGE
+#define FT_BNS_DIRECT128_LARGE 1
+#endif
+#ifndef FT_BNS_DIRECT128_SMALL
+#define FT_BNS_DIRECT128_SMALL 1
+#endif
 
 static int bns_plan(const ft_bottleneck_desc* d, BnsPlan* out) {
   if (!d) return FT_ERR_INVALID_ARG;
@@ -1895,16 +2394,21 @@ static int bns_plan(const ft_bottleneck_desc* d, BnsPlan* out) {
     // on MT1 halo tiles + (72 + 32) steps on MT2 output tiles, per pair of channel tiles.
     const int th_b = rows(192, 256), th_s = rows(128, 192);
     if (th_b < 1 && th_s < 1) return FT_ERR_UNSUPPORTED;
-    const int force128 = dev_env_int("FT_BNS_VARIANT128", 0);   // dev / tests: 1 large, 2 small (read per call)
+    // dev / tests (read per call): 1 ring kernel on large strips, 2 ring on small, 3 direct kernel on large, 4 direct on small
+    const int force128 = dev_env_int("FT_BNS_VARIANT128", 0);
     auto cost = [&](int th, int mt1, int mt2) {
       const long long wg = (long long)d->N * ceil_div(d->H, th);
       return ((wg + 255) / 256) * (long long)(32 * mt1 + 104 * mt2);
     };
     bool small = th_b < 1 || (th_s >= 1 && cost(th_s, 3, 2) < cost(th_b, 4, 3));
-    if (force128 == 1 && th_b >= 1) small = false;
-    if (force128 == 2 && th_s >= 1) small = true;
+    if ((force128 == 1 || force128 == 3) && th_b >= 1) small = false;
+    if ((force128 == 2 || force128 == 4) && th_s >= 1) small = true;
+    // the direct form (folded fp16 operands only; table-form descriptors keep the ring kernels) where it was measured faster in situ
+    bool direct = d->folded && (small ? FT_BNS_DIRECT128_SMALL : FT_BNS_DIRECT128_LARGE);
+    if (force128 == 1 || force128 == 2) direct = false;
+    if (force128 == 3 || force128 == 4) direct = d->folded != 0;
     const int th = small ? th_s : th_b;
-    *out = BnsPlan{small ? 5 : 0, th, ceil_div(d->H, th), d->W, 1};
+    *out = BnsPlan{direct ? (small ? 8 : 7) : (small ? 5 : 0), th, ceil_div(d->H, th), d->W, 1};
     return FT_OK;
   }
   const int th_big = rows(96, 120), th_small = rows(64, 96);
@@ -2005,6 +2509,19 @@ static int bns_launch_direct(const BnsParams& p, hipStream_t s) {
   return FT_OK;
 }
 
+#ifndef FT_BNS_SLOTS128
+#define FT_BNS_SLOTS128 2     // weight-step register slots of the 128-plane direct kernel on large strips: 3 spills (132 B of scratch)
+#endif
+template <int MT1, int MT2>
+static int bns_launch_direct128(const BnsParams& p, hipStream_t s) {
+  auto k = bottleneck_stream_direct128_kernel<MT1, MT2, MT1 == 4 ? FT_BNS_SLOTS128 : 3>;
+  constexpr int lds = BnsGeom<128>::LDS_BYTES;
+  FT_RAISE_LDS(k, lds);
+  hipLaunchKernelGGL(k, dim3(p.total), dim3(256), lds, s, p);
+  FT_LAUNCH_CHECK("bottleneck_stream_direct128_kernel");
+  return FT_OK;
+}
+
 static int bns_launch_tile16(const BnsParams& p, hipStream_t s) {
   auto k = bottleneck_stream_tile16_kernel<FT_BNS_SLOTS>;
   constexpr int lds = 81920 + 2 * 4 * 48 * 128;
@@ -2032,6 +2549,12 @@ extern "C" int ft_bottleneck_stream_layout(const ft_bottleneck_desc* d) {
   ft::BnsPlan pl;
   if (ft::bns_plan(d, &pl) != FT_OK) return -1;
   return pl.variant == 6 ? 1 : 0;
+}
+
+extern "C" int ft_bottleneck_stream_variant(const ft_bottleneck_desc* d) {
+  ft::BnsPlan pl;
+  if (ft::bns_plan(d, &pl) != FT_OK) return -1;
+  return pl.variant;
 }
 
 extern "C" long long ft_bottleneck_stream_weight_bytes(const ft_bottleneck_desc* d) {
@@ -2106,6 +2629,8 @@ extern "C" int ft_bottleneck_stream_fwd(const ft_bottleneck_desc* d, const void*
     switch (pl.variant) {
       case 0: return bns_launch<128, 4, 3, true>(p, s);
       case 5: return bns_launch<128, 3, 2, true>(p, s);
+      case 7: return bns_launch_direct128<4, 3>(p, s);
+      case 8: return bns_launch_direct128<3, 2>(p, s);
       case 1: return bns_launch<256, 4, 3, true>(p, s);
       case 6: return bns_launch_tile16(p, s);
       case 3: return waves8 ? bns_launch_direct<2, 1, true, 0, 8, true>(p, s) : bns_launch_direct<2, 1, true, 0, 4, true>(p, s);

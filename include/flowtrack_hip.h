@@ -315,6 +315,12 @@ int ft_bottleneck_stream_folds(const ft_bottleneck_desc* d);
  * tiles in K32 slices (the 256-plane kernel on 16-pixel MFMA tiles), -1 = unsupported.  Same byte count either way.  A stream packed
  * for one order must not be fed to a launch that plans the other: callers that cache streams key them by this value. */
 int ft_bottleneck_stream_layout(const ft_bottleneck_desc* d);
+/* Kernel form that ft_bottleneck_stream_fwd launches for this descriptor (d->folded counts) under the current developer switches, -1 =
+ * unsupported: 0 / 5 = the 128-plane ring kernel on large (<= 192 output pixels) / small (<= 128) strips, 7 / 8 = the 128-plane kernel
+ * with the weights straight to registers on the same strips (folded operands only; reads the same stream as 0 / 5), 1 / 2 / 3 = the
+ * 256-plane 32-pixel kernels (96- / 64-pixel strips, column split), 6 = the 256-plane kernel on 16-pixel tiles, 4 = the stride-2 head.
+ * For tests and tools: ft_bottleneck_stream_layout cannot tell forms apart that share a stream. */
+int ft_bottleneck_stream_variant(const ft_bottleneck_desc* d);
 long long ft_bottleneck_stream_weight_bytes(const ft_bottleneck_desc* d);
 int ft_bottleneck_stream_pack(const ft_bottleneck_desc* d, const void* w1, const void* w2, const void* w3, void* wstream,
                               ft_stream_t stream);

@@ -1,4 +1,4 @@
-"""Times ft_bottleneck_stream_fwd alone: usage bns_bench.py [P] [B] [H] [W]; FT_BNS_VARIANT / FT_BNS_DBG apply."""
+"""Times ft_bottleneck_stream_fwd alone: usage bns_bench.py [P] [B] [H] [W]; FT_BNS_VARIANT / FT_BNS_VARIANT128 / FT_BNS_DBG apply."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -28,4 +28,4 @@ prog.run_eager(); prog.stream.synchronize()
 t = prog.time_calls(iters=10)
 us = sum(ms for _, ms in t) / len(t) * 1e3
 fl = 2.0 * B * H * W * (C * P + 9 * P * P + P * C)
-print(f"FT_BNS_DBG={os.environ.get('FT_BNS_DBG', '0'):>3s} VARIANT={os.environ.get('FT_BNS_VARIANT', '-')}  P={P} B={B} {H}x{W}: {us:7.1f} us per block   {fl / us * 1e-6:7.1f} TFLOP/s", flush=True)
+print(f"FT_BNS_DBG={os.environ.get('FT_BNS_DBG', '0'):>3s} VARIANT={os.environ.get('FT_BNS_VARIANT128' if P == 128 else 'FT_BNS_VARIANT', '-')}  P={P} B={B} {H}x{W}: {us:7.1f} us per block   {fl / us * 1e-6:7.1f} TFLOP/s", flush=True)

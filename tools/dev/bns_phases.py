@@ -1,5 +1,5 @@
 """Phase timeline of the streamed fused bottleneck (FT_BNS_DBG=32 stamps s_memtime at phase boundaries of wave 0).
-usage: bns_phases.py [P=128|256] [B] ; FT_BNS_VARIANT (1, 2, 6) applies."""
+usage: bns_phases.py [P=128|256] [B] ; FT_BNS_VARIANT (1, 2, 6) applies at 256 planes, FT_BNS_VARIANT128 (1 ring, 3 direct: large strips) at 128."""
 import os, sys
 os.environ["FT_BNS_DBG"] = str(32 | int(os.environ.get("FT_BNS_DBG", "0")))
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
