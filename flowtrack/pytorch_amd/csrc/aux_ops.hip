@@ -185,6 +185,98 @@ __global__ __launch_bounds__(256) void heatmap_max_preds_kernel(const float* __r
   }
 }
 
+// ---- flip test: mirrored input, and merge + max_preds of the two passes' heat maps ---------------------------------------------
+// y[n,c,h,w] = x[n,c,h,W-1-w] as a grid-stride copy.  The 16-byte form moves groups of 4 pixels: group g of a row is read whole,
+// reversed in registers and stored as group W/4 - 1 - g, so both the loads and the stores of a wave stay contiguous.
+__global__ __launch_bounds__(256) void hflip_rows4_kernel(const float4_t* __restrict__ x, float4_t* __restrict__ y, int W4, size_t total) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = i / W4;
+    const int g = (int)(i - row * W4);
+    const float4_t v = x[i];
+    y[row * W4 + (W4 - 1 - g)] = float4_t{v[3], v[2], v[1], v[0]};
+  }
+}
+
+__global__ __launch_bounds__(256) void hflip_scalar_kernel(const float* __restrict__ x, float* __restrict__ y, int W, size_t total) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = i / W;
+    const int xx = (int)(i - row * W);
+    y[row * W + (W - 1 - xx)] = x[i];
+  }
+}
+
+// (a + b) * 0.5f as exactly two fp32 roundings: nothing around a call may contract with either of them
+__device__ __forceinline__ float flip_avg(float a, float b) {
+#pragma clang fp contract(off)
+  const float s = a + b;
+  return s * 0.5f;
+}
+
+// heatmap_max_preds_kernel over merged[n,k,y,x] = (hm[n,k,y,x] + hm_flip[n,perm[k],y,W-1-x]) * 0.5f: one workgroup per merged map,
+// the same element-to-thread assignment and the same tie rule.  The merged map is stored when `merged` is given; thread 0 RECOMPUTES
+// the nudge's four neighbours from the two inputs (no read-back of other threads' stores, and it works without `merged`).
+__global__ __launch_bounds__(256) void heatmap_flip_merge_kernel(const float* __restrict__ hm, const float* __restrict__ hm_flip,
+                                                                 const int32_t* __restrict__ perm, int K, int H, int W, int adjust,
+                                                                 float* __restrict__ merged, int32_t* __restrict__ idx_out,
+                                                                 float* __restrict__ rows) {
+#pragma clang fp contract(off)
+  const int map = blockIdx.x;
+  const int n = map / K, k = map - n * K;
+  int ks = k;
+  if (perm) {
+    const int pk = perm[k];
+    if ((unsigned)pk < (unsigned)K) ks = pk;   // an entry outside [0, K) reads as k itself
+  }
+  const int HW = H * W;
+  const float* p = hm + (size_t)map * HW;
+  const float* q = hm_flip + ((size_t)n * K + ks) * HW;
+  float* m = merged ? merged + (size_t)map * HW : nullptr;
+  float best = -INFINITY;
+  int bidx = 0x7fffffff;
+  for (int i = threadIdx.x; i < HW; i += 256) {
+    const int y = i / W, x = i - y * W;
+    const float v = flip_avg(p[i], q[y * W + (W - 1 - x)]);
+    if (m) m[i] = v;
+    if (v > best) { best = v; bidx = i; }  // strided ascending i: keeps the first occurrence per thread
+  }
+  if (!idx_out) return;                    // (idx and rows come together: merged only)
+  // wave64 butterfly: larger value wins, ties go to the smaller index (first occurrence, row-major)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(best, off);
+    const int oi = __shfl_xor(bidx, off);
+    if (ov > best || (ov == best && oi < bidx)) { best = ov; bidx = oi; }
+  }
+  __shared__ float s_v[4];
+  __shared__ int s_i[4];
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { s_v[wave] = best; s_i[wave] = bidx; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w)
+      if (s_v[w] > best || (s_v[w] == best && s_i[w] < bidx)) { best = s_v[w]; bidx = s_i[w]; }
+    if (bidx == 0x7fffffff) bidx = 0;  // all-NaN / empty map
+    idx_out[map] = bidx;
+    float cx = 0.f, cy = 0.f;
+    if (best > 0.f) {  // coords.mul(mask), evaluation.py:17-19
+      const int x = bidx % W, y = bidx / W;
+      cx = (float)x;
+      cy = (float)y;
+      if (adjust && x > 0 && x < W - 1 && y > 0 && y < H - 1) {  // evaluation.py:31-33, on merged values
+        const int xf = W - 1 - x;          // mirrored column: x + 1 -> xf - 1, x - 1 -> xf + 1
+        const float right = flip_avg(p[y * W + x + 1], q[y * W + xf - 1]), left = flip_avg(p[y * W + x - 1], q[y * W + xf + 1]);
+        const float down = flip_avg(p[(y + 1) * W + x], q[(y + 1) * W + xf]), up = flip_avg(p[(y - 1) * W + x], q[(y - 1) * W + xf]);
+        const float dx = right - left, dy = down - up;
+        cx += dx > 0.f ? 0.25f : (dx < 0.f ? -0.25f : 0.f);
+        cy += dy > 0.f ? 0.25f : (dy < 0.f ? -0.25f : 0.f);
+      }
+    }
+    rows[(size_t)map * 3] = cx;
+    rows[(size_t)map * 3 + 1] = cy;
+    rows[(size_t)map * 3 + 2] = best;
+  }
+}
+
 // ---- arg-max margin screen: per crop, the smallest (top-1 - top-2) over its K maps ------------------------------------
 // One workgroup per crop walks its K maps; a thread keeps the two largest values it has seen (at different pixels), waves
 // and workgroup merge pairs: best = max(b1, b2), second = max(min(b1, b2), s1, s2).  Equal maxima at two pixels -> margin 0.
@@ -925,6 +1017,31 @@ extern "C" int ft_heatmap_keypoint_rows(const float* heatmaps, int N, int K, int
   hipLaunchKernelGGL(heatmap_max_preds_kernel, dim3(N * K), dim3(256), 0, as_stream(stream), heatmaps, H, W,
                      adjust_coords, idx, rows + 2, rows, 3, 3);
   FT_LAUNCH_CHECK("heatmap_max_preds_kernel");
+  return FT_OK;
+}
+
+extern "C" int ft_hflip_nchw_f32(const float* x, float* y, int N, int C, int H, int W, ft_stream_t stream) {
+  if (!x || !y || N <= 0 || C <= 0 || H <= 0 || W <= 0) return FT_ERR_INVALID_ARG;
+  const size_t total = (size_t)N * C * H * W;
+  if (W % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0) {
+    hipLaunchKernelGGL(hflip_rows4_kernel, dim3(grid_for(total / 4)), dim3(256), 0, as_stream(stream), reinterpret_cast<const float4_t*>(x),
+                       reinterpret_cast<float4_t*>(y), W / 4, total / 4);
+    FT_LAUNCH_CHECK("hflip_rows4_kernel");
+    return FT_OK;
+  }
+  hipLaunchKernelGGL(hflip_scalar_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), x, y, W, total);
+  FT_LAUNCH_CHECK("hflip_scalar_kernel");
+  return FT_OK;
+}
+
+extern "C" int ft_heatmap_flip_merge(const float* hm, const float* hm_flip, const int32_t* perm, int N, int K, int H, int W,
+                                     int adjust_coords, float* merged, int32_t* idx, float* rows, ft_stream_t stream) {
+  if (!hm || !hm_flip || N <= 0 || K <= 0 || H <= 0 || W <= 0) return FT_ERR_INVALID_ARG;
+  if ((!merged && !idx && !rows) || (idx == nullptr) != (rows == nullptr)) return FT_ERR_INVALID_ARG;
+  if ((long long)N * K > 0x7fffffffLL || (long long)H * W > 0x7fffffffLL) return FT_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(heatmap_flip_merge_kernel, dim3(N * K), dim3(256), 0, as_stream(stream), hm, hm_flip, perm, K, H, W, adjust_coords,
+                     merged, idx, rows);
+  FT_LAUNCH_CHECK("heatmap_flip_merge_kernel");
   return FT_OK;
 }
 

@@ -96,6 +96,11 @@ class DeconvResnet(HipModule):
     keypoints_in_plan = None
     #: record the exact-arg-max mode's screen + flagged-crop gather inside fp16 plans (needs keypoints_in_plan); see exact_submit_plan
     exact_in_plan: bool = False
+    #: None: no flip test.  A sequence of (a, b) left/right joint pairs (tools/pose/main.get_flip_pairs; () = mirror and average, no swap):
+    #: forward_flip(), plan_for() and, with keypoints_in_plan set, forward_keypoints() / forward_keypoint_rows() use the FLIP PLAN of a
+    #: shape: the ordinary launch list at batch 2B between ft_hflip_nchw_f32 (x[:B] mirrored into x[B:]) and ft_heatmap_flip_merge
+    #: (the two halves averaged, left/right joints swapped back, and the key points of the merged maps).  forward() never reads it
+    flip_pairs = None
     #: dev: layer1 + layer2 as two half-batch lanes (parallel graph branches); FT_SPLIT_LANES=1
     split_lanes4: bool = os.environ.get("FT_SPLIT_LANES4", "0") == "1"       # dev: layer4 as two half-batch lanes
     split_lanes: int = int(os.environ.get("FT_SPLIT_LANES", "0") or 0)     # 1: lanes start together; 2: the second lane starts with its half of the stem
@@ -165,12 +170,43 @@ class DeconvResnet(HipModule):
         self._invalidate()
 
     # -- plan construction ----------------------------------------------------------------------
-    def _build_plan(self, B: int, H: int, W: int, device, dtype) -> _PosePlan:
+    def _flip_perm(self):
+        """flip_pairs as the channel permutation of ft_heatmap_flip_merge (merged map k reads map perm[k] of the mirrored pass), validated
+        as tools/pose/main._flip_back validates its pairs; None when flip_pairs is None."""
+        if self.flip_pairs is None:
+            return None
+        if self.exact_in_plan:
+            raise FlowtrackHipError("flip_pairs is set: the exact-arg-max mode (exact_in_plan) does not combine with the flip test")
+        perm, seen = list(range(self.num_classes)), set()
+        try:
+            pairs = [(int(a), int(b)) for a, b in self.flip_pairs]
+        except (TypeError, ValueError):
+            raise FlowtrackHipError(f"flip_pairs must be None or a sequence of (a, b) joint pairs, got {self.flip_pairs!r}")
+        for a, b in pairs:
+            if not (0 <= a < self.num_classes and 0 <= b < self.num_classes):
+                raise FlowtrackHipError(f"flip pair ({a}, {b}) does not fit {self.num_classes} heatmap channels: wrong dataset table?")
+            if a in seen or b in seen:
+                raise FlowtrackHipError(f"flip pair ({a}, {b}): a joint may appear in one pair only")
+            seen.update((a, b))
+            perm[a], perm[b] = b, a
+        return tuple(perm)
+
+    def _no_flip(self, what: str) -> None:
+        if self.flip_pairs is not None:
+            raise FlowtrackHipError(f"{what}: flip_pairs is set, and the exact-arg-max mode does not combine with the flip test")
+
+    def _build_plan(self, B: int, H: int, W: int, device, dtype, perm=None) -> _PosePlan:
         if H % 32 or W % 32:
             raise FlowtrackHipError(f"input {H}x{W}: height and width must be multiples of 32")
         prog = Program(self._side_stream(device))
         mk = dict(dtype=dtype, device=device)
+        B0 = B
+        if perm is not None:
+            # flip plan: everything below is the ordinary launch list at batch 2B; crops [B0, 2 B0) are the mirrored copies of [0, B0)
+            B = 2 * B0
         x_static = torch.empty((B, 3, H, W), dtype=torch.float32, device=device)
+        if perm is not None:
+            prog.add("ft_hflip_nchw_f32", x_static.data_ptr(), x_static[B0:].data_ptr(), B0, 3, H, W)
         # 7x7/s2/p3 stem: one kernel row = one K-run.  fp16: conv1 + bn1 + relu + maxpool (resnet.py:19-23) are ONE launch
         # (ft_conv_desc.pool; its patch starts one stem column further left: 5 physical pad columns instead of 3) and the
         # [B, H/2, W/2, 64] stem map never exists
@@ -297,6 +333,25 @@ class DeconvResnet(HipModule):
             hm = self.fused("heatmap", self.heatmap.weight, bias=self.heatmap.bias, act=None, **mk)
             heatmaps = torch.empty((B, self.num_classes, cur.H, cur.W), dtype=torch.float32, device=device)
             hm.record(prog, cur, heatmaps)
+        if perm is not None:
+            # last launch: average the two halves (mirror + left/right swap of the second) and, with keypoints_in_plan, the key points
+            # of the merged maps — in place of the separate ft_heatmap_keypoint_rows launch
+            K, hh, hw = self.num_classes, heatmaps.shape[2], heatmaps.shape[3]
+            merged = torch.empty((B0, K, hh, hw), dtype=torch.float32, device=device)
+            plan = _PosePlan(prog, x_static[:B0], merged)
+            plan.stages, plan.heatmaps_raw, plan.x_full = stages, heatmaps, x_static
+            plan.flip_perm = torch.tensor(perm, dtype=torch.int32, device=device)
+            plan.kp_idx = plan.kp_rows = None
+            keep = [merged, heatmaps, plan.flip_perm]
+            if self.keypoints_in_plan is not None:
+                plan.kp_idx = torch.empty((B0, K), dtype=torch.int32, device=device)
+                plan.kp_rows = torch.empty((B0, K, 3), dtype=torch.float32, device=device)
+                plan.kp_score, plan.kp_coords = plan.kp_rows[:, :, 2:], plan.kp_rows[:, :, :2]
+                keep += [plan.kp_idx, plan.kp_rows]
+            prog.add("ft_heatmap_flip_merge", heatmaps.data_ptr(), heatmaps[B0:].data_ptr(), plan.flip_perm.data_ptr(), B0, K, hh, hw,
+                     int(bool(self.keypoints_in_plan)), merged.data_ptr(), plan.kp_idx.data_ptr() if plan.kp_idx is not None else None,
+                     plan.kp_rows.data_ptr() if plan.kp_rows is not None else None, keep=tuple(keep))
+            return plan
         plan = _PosePlan(prog, x_static, heatmaps)
         plan.stages = stages
         if self.keypoints_in_plan is not None:
@@ -484,13 +539,17 @@ class DeconvResnet(HipModule):
         """The plan (launch list + activation buffers + graph) of one input shape.  `replica` > 0 gives an independent copy
         with its own buffers — same packed weights, same tile picks — for callers that keep several batches of one shape
         in flight on different streams (tracking.PoseRunner per clip, tools/tracking/demo.run_clips)."""
+        return self._plan_for(B, H, W, replica, self._flip_perm())
+
+    def _plan_for(self, B: int, H: int, W: int, replica: int = 0, perm=None) -> _PosePlan:
+        """plan_for() with the flip test stated by the caller: perm = None is the plain plan of the shape whatever flip_pairs says."""
         device, dtype = self._resolve()
         key = (B, H, W, device, dtype, self.keypoints_in_plan) + (("exact", float(self.exact_argmax_rel_bound)) if self.exact_in_plan else ()) + \
-            ((replica,) if replica else ())
+            ((replica,) if replica else ()) + ((("flip",) + tuple(perm),) if perm is not None else ())
         plan = self._plans.get(key)
         if plan is None:
             with torch.no_grad():
-                plan = self._build_plan(B, H, W, device, dtype)
+                plan = self._build_plan(B, H, W, device, dtype, perm)
             self._plans[key] = plan
         return plan
 
@@ -502,11 +561,24 @@ class DeconvResnet(HipModule):
     @torch.no_grad()
     def forward(self, x: torch.Tensor, copy_output: bool = True) -> torch.Tensor:
         """x: [B,3,H,W] on the model's GPU -> heatmaps [B,K,H/4,W/4] fp32 (pose_deconv.py:32-46)."""
+        return self._forward(x, copy_output, None)
+
+    @torch.no_grad()
+    def forward_flip(self, x: torch.Tensor, copy_output: bool = True) -> torch.Tensor:
+        """The flip test of the reference (tools/pose/main.py:289-299) as ONE plan: x and its mirror image through the net as a batch
+        of 2B, then (heatmaps(x) + heatmaps(mirrored x) mirrored back with the `flip_pairs` channels swapped) * 0.5 -> [B,K,H/4,W/4]
+        fp32.  flip_pairs must be set; () mirrors and averages without a swap."""
+        perm = self._flip_perm()
+        if perm is None:
+            raise FlowtrackHipError("set model.flip_pairs (tools/pose/main.get_flip_pairs; () = no left/right swap) before forward_flip()")
+        return self._forward(x, copy_output, perm)
+
+    def _forward(self, x: torch.Tensor, copy_output: bool, perm) -> torch.Tensor:
         self._check_eval()
         if x.dim() != 4 or x.shape[1] != 3:
             raise FlowtrackHipError(f"expected [B,3,H,W], got {tuple(x.shape)}")
         B, _, H, W = x.shape
-        plan = self.plan_for(B, H, W)
+        plan = self._plan_for(B, H, W, 0, perm)
         if x.device != plan.x_static.device:
             raise FlowtrackHipError("input and model are on different devices")
         if x.data_ptr() != plan.x_static.data_ptr():   # zero-copy when the caller filled static_input() in place
@@ -532,7 +604,7 @@ class DeconvResnet(HipModule):
         (heatmaps [B,K,h,w], idx int32 [B,K], scores [B,K,1], coords [B,K,2] in heatmap pixels), valid until the next call."""
         if self.keypoints_in_plan is None:
             raise FlowtrackHipError("set model.keypoints_in_plan = True / False (adjust_coords) before forward_keypoints()")
-        hm = self.forward(x, copy_output=False)
+        hm = self._forward(x, False, self._flip_perm())      # (with flip_pairs set: the merged maps and their key points)
         plan = self._last_plan
         return hm, plan.kp_idx, plan.kp_score, plan.kp_coords
 
@@ -602,6 +674,7 @@ class DeconvResnet(HipModule):
         """First half of the exact-arg-max step (see above): everything is queued on the current stream, nothing is waited for."""
         if self.keypoints_in_plan is None:
             raise FlowtrackHipError("set model.keypoints_in_plan = True / False (adjust_coords) before exact_submit()")
+        self._no_flip("exact_submit")
         import ctypes
         from .. import _lib
         from ..hip_ops import check, current_stream_handle
@@ -641,6 +714,7 @@ class DeconvResnet(HipModule):
         place): ONE graph replay — network, key-point rows, screen, gather, header copy — and an event.  The plan's buffers are the
         step's state, so a plan must be finished (exact_finish_plan) before it is submitted again: callers that keep several steps
         in flight rotate plan replicas."""
+        self._no_flip("exact_submit_plan")
         ex = getattr(plan, "exact", None)
         if ex is None:
             raise FlowtrackHipError("exact_submit_plan: the plan was built without exact_in_plan (fp16, keypoints_in_plan, B <= 1024)")
@@ -737,6 +811,7 @@ class DeconvResnet(HipModule):
         per call sits between 2 and 3."""
         if self.keypoints_in_plan is None:
             raise FlowtrackHipError("set model.keypoints_in_plan = True / False (adjust_coords) before forward_keypoint_rows_exact()")
+        self._no_flip("forward_keypoint_rows_exact")
         want = self.compute_dtype
         if want not in (None, torch.float16) and next(self.parameters()).dtype != torch.float16:
             raise FlowtrackHipError("forward_keypoint_rows_exact() is the fp16 mode's exact-arg-max path: compute_dtype must be fp16")

@@ -168,11 +168,13 @@ class PoseRunner:
     plan look-up per call (tools/dev/clip_profile.py: 0.21 -> ~0.1 ms per frame)."""
     BUCKETS = (4, 8, 16, 32, 64, 128, 256)
 
-    def __init__(self, net, inp_res=(256, 192), normalize=True, replica: int = 0, stream=None, cv2_exact: bool = False):
+    def __init__(self, net, inp_res=(256, 192), normalize=True, replica: int = 0, stream=None, cv2_exact: bool = False, flip_pairs=None):
         """replica / stream: a runner of its own plan copies (DeconvResnet.plan_for(..., replica)) whose launches go to
         `stream` — several runners on one net then overlap on the GPU (one per clip, tools/tracking/demo.run_clips).
         cv2_exact: crops in cv2.warpAffine's fixed-point arithmetic (bit-exact to the restated classic OpenCV path, unpinned against a
-        real cv2 build: ft_crop_affine_cv2_fwd) instead of the fp32 bilinear."""
+        real cv2 build: ft_crop_affine_cv2_fwd) instead of the fp32 bilinear.
+        flip_pairs: left/right joint pairs (tools/pose/main.get_flip_pairs) -> net.flip_pairs: the runner's plans become flip plans (the
+        crops and their mirror images through the net, rows of the merged heat maps); None leaves the net as it is."""
         self.net, self.inp_res = net, inp_res
         self.replica, self.stream = int(replica), stream
         self.cv2_exact = bool(cv2_exact)
@@ -181,6 +183,8 @@ class PoseRunner:
         require_gpu(self.dev)
         self.lib = _lib.load()
         net.keypoints_in_plan = True                      # rows with the adjust_coords nudge, inside the plan's graph
+        if flip_pairs is not None:
+            net.flip_pairs = tuple((int(a), int(b)) for a, b in flip_pairs)
         self.mean = self.inv_std = None
         self.pre = 1.0
         if normalize:
@@ -369,8 +373,8 @@ class GroupPoseRunner(PoseRunner):
     Protocol per round: member submits (any subset of the members, each at most once) -> flush() -> ... -> results.  A
     result() of a round that was not flushed yet flushes it (a member alone behaves like a plain runner)."""
 
-    def __init__(self, net, inp_res=(256, 192), normalize=True, replica: int = 0, stream=None, cv2_exact: bool = False):
-        super().__init__(net, inp_res, normalize, replica, stream, cv2_exact)
+    def __init__(self, net, inp_res=(256, 192), normalize=True, replica: int = 0, stream=None, cv2_exact: bool = False, flip_pairs=None):
+        super().__init__(net, inp_res, normalize, replica, stream, cv2_exact, flip_pairs)
         self._pending = []                                 # [frame_dev, boxes [n,4]] of the round being collected
         self._round = {"handle": None, "cuts": None}       # the collecting round; replaced at flush
 

@@ -370,6 +370,22 @@ int ft_heatmap_keypoint_rows(const float* heatmaps, int N, int K, int H, int W,
                              int adjust_coords, int32_t* idx, float* rows,
                              ft_stream_t stream);
 
+/* ---- flip test (reference tools/pose/main.py:289-299): the mirrored input, and the merge of the two passes ----
+ * y[n,c,h,w] = x[n,c,h,W-1-w]; NCHW fp32; x and y must not overlap.  The mirrored input of the flip test
+ * (tools/pose/main.py:289-291 of the reference).  16-byte loads and reversed 16-byte stores when W % 4 == 0 and both
+ * pointers are 16-byte aligned, scalar otherwise. */
+int ft_hflip_nchw_f32(const float* x, float* y, int N, int C, int H, int W, ft_stream_t stream);
+
+/* Flip-test merge + max_preds in one launch (reference tools/pose/main.py:289-299, evaluation.py:11-35).
+ *   merged[n,k,y,x] = (hm[n,k,y,x] + hm_flip[n,perm[k],y,W-1-x]) * 0.5f     -- exactly these two fp32 roundings
+ * hm, hm_flip: NCHW fp32 [N,K,H,W] (plain pass / pass on the mirrored input).
+ * perm: DEVICE int32[K], NULL = identity; an entry outside [0,K) is read as k itself (never an out-of-range read).
+ * merged (fp32 [N,K,H,W]), idx (int32 [N*K]) and rows (fp32 [N*K*3] = x, y, score) may each be NULL, but not all
+ * three, and idx and rows only together.  idx / rows are ft_heatmap_keypoint_rows of `merged`, including
+ * adjust_coords and the NaN promise.  merged must not alias hm or hm_flip. */
+int ft_heatmap_flip_merge(const float* hm, const float* hm_flip, const int32_t* perm, int N, int K, int H, int W,
+                          int adjust_coords, float* merged, int32_t* idx, float* rows, ft_stream_t stream);
+
 /* Arg-max margin screen of the fast (fp16) mode: min_margin[n] = min over the K maps of crop n of (largest - second largest
  * value, at different pixels; 0 for a tie).  A crop whose min_margin exceeds twice the heat-map error bound of the fp16
  * arithmetic has the same arg-max in every map as the fp32 parity mode (max_preds, evaluation.py:11-20); the others are the

@@ -80,11 +80,25 @@ def validate(model, batches, flip_test=False, adjust_coords=True, flip_pairs=COC
     (parallel.all_gather_rows: one collective per batch), so every rank returns the full arrays in dataset order — what the
     reference gets from nn.DataParallel's scatter / gather (tools/flownet/main.py:133-134,186).  `preds_fn(heatmaps, center,
     scale, adjust_coords)` defaults to the device path (evaluation.final_preds); `device` / `preds_fn` exist for the gloo test."""
-    from flowtrack.pytorch_amd import parallel
     if hasattr(model, 'eval'):
         model.eval()
     preds_fn = preds_fn or evaluation.final_preds
     on_gpu = torch.device(device).type == 'cuda'
+    # the flip test inside the model's plan (DeconvResnet.forward_flip: mirror, 2B pass and merge as one graph) where the model has it;
+    # any other model, and the CPU stand-ins, take the generic two-pass form below
+    fused_flip = bool(flip_test) and on_gpu and hasattr(model, 'forward_flip')
+    if fused_flip:
+        saved_pairs = getattr(model, 'flip_pairs', None)
+        model.flip_pairs = tuple((int(a), int(b)) for a, b in flip_pairs)
+    try:
+        return _validate_loop(model, batches, flip_test, fused_flip, adjust_coords, flip_pairs, rank, world, device, on_gpu, preds_fn)
+    finally:
+        if fused_flip:
+            model.flip_pairs = saved_pairs
+
+
+def _validate_loop(model, batches, flip_test, fused_flip, adjust_coords, flip_pairs, rank, world, device, on_gpu, preds_fn):
+    from flowtrack.pytorch_amd import parallel
     all_preds, all_scores, all_idx = [], [], []
     n, t0 = 0, time.time()
     for inputs, meta in batches:
@@ -93,8 +107,11 @@ def validate(model, batches, flip_test=False, adjust_coords=True, flip_pairs=COC
         center, scale = np.asarray(meta['center'])[lo:hi], np.asarray(meta['scale'])[lo:hi]
         if hi > lo:
             x = inputs[lo:hi].to(device, non_blocking=True)
-            output = model(x)
-            if flip_test:
+            if fused_flip:
+                output = model.forward_flip(x)
+            else:
+                output = model(x)
+            if flip_test and not fused_flip:
                 flipped = _flip_back(model(torch.flip(x, dims=[3])), flip_pairs)
                 output = (output + flipped) * 0.5
             preds, scores = preds_fn(output, center, scale, adjust_coords)

@@ -401,6 +401,9 @@ def main(argv=None):
     ap.add_argument("--groups", type=int, default=2, help="clip groups of run_clips (each group's per-frame crops share one plan replay)")
     ap.add_argument("--waves", type=int, default=1, help="waves of run_clips (the next wave's batched phases run under the current wave's passes)")
     ap.add_argument("--pose_classes", type=int, default=17, help="key points per person: 17 (COCO) or 16 (MPII)")
+    ap.add_argument("--flip_test", action="store_true",
+                    help="pose with the flip test: every crop and its mirror image through the net, heat maps averaged with the COCO "
+                         "left/right joints swapped back, inside the runners' plans (DeconvResnet.flip_pairs); needs --pose_classes 17")
     ap.add_argument("--max_boxes", type=str, default="auto",
                     help="boxes kept per frame after NMS: 'none' (the reference: every survivor), an integer, '2x' = twice the "
                          "detector boxes; 'auto' = 'none' with --pose_model, '2x' with the synthetic (untrained) weights")
@@ -412,6 +415,11 @@ def main(argv=None):
     device = torch.device("cuda", local_rank)
     torch.cuda.set_device(device)
     pose_net, flow_net = build_nets(args, device)
+    if args.flip_test:
+        from tools.pose.main import COCO_FLIP_PAIRS
+        if args.pose_classes != 17:
+            raise SystemExit("--flip_test swaps the COCO left/right joints: it needs --pose_classes 17")
+        pose_net.flip_pairs = tuple(COCO_FLIP_PAIRS)       # every PoseRunner / GroupPoseRunner plan of this net becomes a flip plan
     if args.clips > 1:
         if world != 1:
             raise SystemExit("--clips is the per-GPU throughput mode: run one process per GPU, each with its own clips")
