@@ -127,14 +127,9 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const std::con
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, lhi = lane >> 5;
 
-  // XCD-aware order: block b runs on XCD b % 8; give each XCD one contiguous range of patches (neighbouring patches
-  // share their halo rows through that XCD's L2)
-  int logical;
-  {
-    const int b = blockIdx.x;
-    const int q = p.total >> 3, r = p.total & 7, xcd = b & 7, loc = b >> 3;
-    logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  // XCD-aware order: each XCD gets one contiguous range of patches (neighbouring patches share their halo rows through that
+  // XCD's L2)
+  const int logical = xcd_logical_wg(p.total);
   const int tiles_per_img = p.tx * p.ty;
   const int n = logical / tiles_per_img;
   const int trem = logical - n * tiles_per_img;

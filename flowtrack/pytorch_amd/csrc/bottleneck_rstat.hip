@@ -134,14 +134,9 @@ __global__ __launch_bounds__(512, 1) void bottleneck_rstat_kernel(const BnrParam
   const int l31 = lane & 31, lhi = lane >> 5;
   const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr)smem;
 
-  // XCD-aware order: block b runs on XCD b % 8; each XCD gets one contiguous range of strips (neighbouring strips share their
-  // halo rows through that XCD's L2)
-  int logical;
-  {
-    const int b = blockIdx.x;
-    const int q = p.total >> 3, r = p.total & 7, xcd = b & 7, loc = b >> 3;
-    logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  // XCD-aware order: each XCD gets one contiguous range of strips (neighbouring strips share their halo rows through that
+  // XCD's L2)
+  const int logical = xcd_logical_wg(p.total);
   const int n = logical / p.S, si = logical - n * p.S;
   const int W = p.W, HW = p.H * W;
   const int r0 = si * p.SR;

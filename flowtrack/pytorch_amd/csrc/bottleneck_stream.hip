@@ -94,6 +94,98 @@ struct BnsGeom {
   static_assert(ZROW % ROWB == 0 && ZROW + ROWB <= WBASE && WBASE + 3 * WSTEP == LDS_BYTES, "LDS map");
 };
 
+// ---- device code shared by the four kernels --------------------------------------------------------------------------------------
+// hipcc's output for these kernels (422-512 VGPRs, hand-counted waits) depends on how the source is phrased: every helper below was
+// checked to leave all kernels of the unit instruction-identical (tools/dev/isa_diff.py; profiles/HISTORY.md lists what was tried and
+// withdrawn).  What came through: scalars by value, results by value where there is one, arrays by reference, the call where the
+// block stood.  Still one copy per kernel, because a function (or even a namespace-scope constant) changed the code: kOOB, x_voff[],
+// issue_touch, permA, the residual pick-up, the swizzled T1 / T2 row stores, zero_acc, row_bases.
+typedef __attribute__((address_space(3))) void* lds_ptr;
+constexpr unsigned kBnsOOB = 0x80000000u;   // = the kernels' own kOOB: a buffer offset out of range for every descriptor (zeros, no traffic)
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t bns_rsrc(const char* base, unsigned bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(base), 0, bytes, 0x00020000);
+}
+
+// x chunk c (64 channels = 128 bytes per halo pixel) into the chunk buffer `dst`: LX 1-KiB loads (8 rows each) per wave of NW
+template <int NW, int LX>
+__device__ __forceinline__ void bns_issue_x(__amdgpu_buffer_rsrc_t rsrc_x, char* dst, int wave, const unsigned (&x_voff)[LX], int c) {
+#pragma unroll
+  for (int t = 0; t < LX; ++t)
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (lds_ptr)(dst + (t * NW + wave) * 1024), 16, x_voff[t], c * 128, 0, 0);
+}
+
+// T1: a halo pixel outside the image is conv2's zero padding
+__device__ __forceinline__ half8_t bns_keep_if(half8_t v, bool inside) {
+  uint4_t u = __builtin_bit_cast(uint4_t, v);
+  u.x = inside ? u.x : 0u; u.y = inside ? u.y : 0u; u.z = inside ? u.z : 0u; u.w = inside ? u.w : 0u;
+  return __builtin_bit_cast(half8_t, u);
+}
+
+// x-border flags of output column ox: bit 0 = first column (tap kx = 0 is padding), bit 1 = last column
+__device__ __forceinline__ int bns_edge(int ox, int W) { return (ox == 0 ? 1 : 0) | (ox == W - 1 ? 2 : 0); }
+
+// Folded operands (see bottleneck_stream_direct_kernel).  The shift pairs of MFMA row l31 of epilogues e0 .. e1-1 for the wave's CT
+// 32-channel tiles from `tile0` on (lanes 32..63 hold k = 8..15 of the shift slice: zeros, fetched out of range) ...
+template <int P, int CT>
+__device__ __forceinline__ void bns_load_shp(unsigned (&shp)[6][CT], __amdgpu_buffer_rsrc_t rsrc_t, int l31, int lhi, int tile0, int e0, int e1) {
+  const unsigned so = lhi == 0 ? 4u * (unsigned)bns_sigma(l31) : kBnsOOB;
+#pragma unroll
+  for (int e = e0; e < e1; ++e)
+#pragma unroll
+    for (int i = 0; i < CT; ++i)
+      shp[e][i] = __builtin_amdgcn_raw_buffer_load_b32(rsrc_t, so, 4 * (e * P + (tile0 + i) * 32), 0);
+}
+// ... A[i][j] += the shift of one epilogue: ONE extra MFMA per tile (A row = {hi, lo, 0 ..}, B = ones at k = 0, 1), on 32-pixel tiles ...
+template <int CT, int MT>
+__device__ __forceinline__ void bns_add_shift(float16_t (&A)[CT][MT], const unsigned (&sh)[CT]) {
+  const uint4_t onesB = uint4_t{0x3C003C00u, 0u, 0u, 0u};
+#pragma unroll
+  for (int i = 0; i < CT; ++i) {
+    const uint4_t sa = uint4_t{sh[i], 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < MT; ++j)
+      A[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, sa), __builtin_bit_cast(half8_t, onesB), A[i][j], 0, 0, 0);
+  }
+}
+// ... and on 16-pixel tiles ...
+template <int CT, int MT>
+__device__ __forceinline__ void bns_add_shift(float4_t (&A)[CT][MT], const unsigned (&sh)[CT]) {
+  const uint4_t onesB = uint4_t{0x3C003C00u, 0u, 0u, 0u};
+#pragma unroll
+  for (int t = 0; t < CT; ++t) {
+    const uint4_t sa = uint4_t{sh[t], 0u, 0u, 0u};
+#pragma unroll
+    for (int j = 0; j < MT; ++j)
+      A[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, sa), __builtin_bit_cast(half8_t, onesB), A[t][j], 0, 0, 0);
+  }
+}
+// ... and the last epilogue of a 32-pixel tile: shift3 of the quarter and the identity residual (its two slices through the 0/1 matrix
+// permA) join the accumulator as three MFMAs.  (onesB comes from the kernel: built in here, three kernels change registers.)
+__device__ __forceinline__ void bns_fold_tail(float16_t& a, unsigned sh, const uint4_t& onesB, const uint4_t (&permA)[2], const uint4_t (&res)[2]) {
+  const uint4_t sa = uint4_t{sh, 0u, 0u, 0u};
+  a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, sa), __builtin_bit_cast(half8_t, onesB), a, 0, 0, 0);
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+    a = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, permA[h]), __builtin_bit_cast(half8_t, res[h]), a, 0, 0, 0);
+}
+
+// dev (FT_BNS_DBG=32): phase timestamps of wave 0 over the strip's first output pixel (the output is garbage then).  Macros over the
+// kernel's own p, ts, tid, n, y0 and W: the tail as a function changed fifteen kernels.
+#define BNS_TS(i) do { if (p.dbg & 32) ts[i] = __builtin_amdgcn_s_memtime(); } while (0)
+#define BNS_TS_TAIL()                                                                                                                \
+  do {                                                                                                                               \
+    if (p.dbg & 32) {                                                                                                                \
+      ts[5] = __builtin_amdgcn_s_memtime();                                                                                          \
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                               \
+      ts[6] = __builtin_amdgcn_s_memtime();                                                                                          \
+      if (tid == 0) {                                                                                                                \
+        unsigned long long* o = reinterpret_cast<unsigned long long*>(p.y + ((size_t)((n * p.H + y0) * W) * p.y_cstride + p.y_coff) * 2); \
+        _Pragma("unroll") for (int i = 0; i < 8; ++i) o[i] = ts[i];                                                                  \
+      }                                                                                                                              \
+    }                                                                                                                                \
+  } while (0)
+
 // FOLD: the folded operands (see bottleneck_stream_direct_kernel): scales in the weights, shifts as (hi, lo) pairs in p.tab, shift and
 // residual added by MFMA, every epilogue = fp16(relu(acc)); no table ever travels through LDS.
 template <int P, int MT1, int MT2, bool FOLD = false>
@@ -111,7 +203,6 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
   static_assert(NOUT * ROWB <= 49152, "T2 fits below the staging tile / inside the T1 region");
   static_assert(2 * (LX + LW) + 6 + 12 <= 63, "vmcnt immediate");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef __attribute__((address_space(3))) void* lds_ptr;
   using c0 = std::integral_constant<int, 0>;
   using c1 = std::integral_constant<int, 1>;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -119,12 +210,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
   const int wcol = wave % WCOLS, pg = wave / WCOLS;
   const int l31 = lane & 31, lhi = lane >> 5;
 
-  int logical;
-  {
-    const int b = blockIdx.x;
-    const int q = p.total >> 3, r = p.total & 7, xcd = b & 7, loc = b >> 3;
-    logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  const int logical = xcd_logical_wg(p.total);
   const int n = logical / p.ppi;
   const int y0 = (logical - n * p.ppi) * p.TH;
   const int W = p.W;
@@ -132,24 +218,15 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
   const int npix_out = rows_out * W;
   const int npix_halo = (p.TH + 2) * W;
 
-  const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.x), 0, p.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.ws), 0, p.ws_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.tab), 0, FOLD ? (2 * P + G::C) * 4 : 6 * G::TABB, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_x = bns_rsrc(p.x, p.x_bytes), rsrc_y = bns_rsrc(p.y, p.y_bytes), rsrc_w = bns_rsrc(p.ws, p.ws_bytes);
+  const __amdgpu_buffer_rsrc_t rsrc_t = bns_rsrc(p.tab, FOLD ? (2 * P + G::C) * 4 : 6 * G::TABB);
   constexpr unsigned kOOB = 0x80000000u;
 
   // folded form: shift pairs of this wave's MFMA rows per (epilogue, tile) and the residual's 0/1 matrix (see the direct kernel)
   [[maybe_unused]] unsigned shp[6][2];
   [[maybe_unused]] uint4_t permA[2];
   [[maybe_unused]] const uint4_t onesB = uint4_t{0x3C003C00u, 0u, 0u, 0u};
-  auto load_shp = [&]() {
-    const unsigned so = lhi == 0 ? 4u * (unsigned)bns_sigma(l31) : kOOB;
-#pragma unroll
-    for (int e = 0; e < 6; ++e)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-        shp[e][i] = __builtin_amdgcn_raw_buffer_load_b32(rsrc_t, so, 4 * (e * P + (2 * wcol + i) * 32), 0);
-  };
+  auto load_shp = [&]() { bns_load_shp<P>(shp, rsrc_t, l31, lhi, 2 * wcol, 0, 6); };
   if constexpr (FOLD) {
     const int sg = bns_sigma(l31);
     const bool on = lhi == (sg >> 4);
@@ -162,16 +239,6 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
       permA[hh] = uint4_t{w[0], w[1], w[2], w[3]};
     }
   }
-  [[maybe_unused]] auto add_shift = [&](int e, auto& A, auto mtc) {      // A[i][j] += shift of epilogue e (one MFMA per tile)
-    constexpr int MT = decltype(mtc)::value;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const uint4_t sa = uint4_t{shp[e][i], 0u, 0u, 0u};
-#pragma unroll
-      for (int j = 0; j < MT; ++j)
-        A[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, sa), __builtin_bit_cast(half8_t, onesB), A[i][j], 0, 0, 0);
-    }
-  };
 
   // the first round of workgroups on an XCD pulls the block's weight stream into that XCD's L2, each its own 1/n-th, one
   // dword per 128-byte line (see the direct kernel); the scratch corner sits between the zero row and the weight ring.
@@ -209,12 +276,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
     x_voff[t] = v;
   }
   const unsigned lane16 = (unsigned)lane * 16u;
-  auto issue_x = [&](int c, int buf) {
-    char* dst = smem + buf * G::XSTRIDE;
-#pragma unroll
-    for (int t = 0; t < LX; ++t)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (lds_ptr)(dst + (t * 4 + wave) * 1024), 16, x_voff[t], c * 128, 0, 0);
-  };
+  auto issue_x = [&](int c, int buf) { bns_issue_x<4>(rsrc_x, smem + buf * G::XSTRIDE, wave, x_voff, c); };
   auto issue_w = [&](int g, int buf) {
     char* dst = smem + G::WBASE + buf * WSTEP;
 #pragma unroll
@@ -234,7 +296,6 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
   uint4_t fa[2][2];                   // A fragments, two register sets: slice k+1 is read while slice k multiplies
 
   unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define BNS_TS(i) do { if (p.dbg & 32) ts[i] = __builtin_amdgcn_s_memtime(); } while (0)
   BNS_TS(0);
   // prologue: chunk 0 (x + W1 slice) leads every wave's load queue, then the L2 touch and table 0 / the shift pairs, chunks 1 and 2,
   // the zero row
@@ -339,7 +400,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   BNS_BARRIER();
   {
-    if constexpr (FOLD) add_shift(0, acc1, std::integral_constant<int, MT1>{});
+    if constexpr (FOLD) bns_add_shift(acc1, shp[0]);
     [[maybe_unused]] const float* tb = reinterpret_cast<const float*>(smem + G::TAB);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -362,11 +423,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
         if constexpr (FOLD) relu_acc16(acc1[i][j], h8);
         else bn_relu_acc16(acc1[i][j], sc, sh, h8);
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          uint4_t u = __builtin_bit_cast(uint4_t, h8[h]);
-          u.x = inside ? u.x : 0u; u.y = inside ? u.y : 0u; u.z = inside ? u.z : 0u; u.w = inside ? u.w : 0u;
-          h8[h] = __builtin_bit_cast(half8_t, u);
-        }
+        for (int h = 0; h < 2; ++h) h8[h] = bns_keep_if(h8[h], inside);
         if (hp < npix_halo) {
           char* rowp = smem + hp * ROWB;
           const int cb = (2 * wcol + i) * 4 + 2 * lhi;           // 16-byte chunk of channel `ch`
@@ -411,10 +468,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
   // x-border flags of this lane's output pixels: bit 0 = first column (tap kx = 0 is padding), bit 1 = last column
   int edge[MT2];
 #pragma unroll
-  for (int j = 0; j < MT2; ++j) {
-    const int ox = m_out[j] % W;
-    edge[j] = (ox == 0 ? 1 : 0) | (ox == W - 1 ? 2 : 0);
-  }
+  for (int j = 0; j < MT2; ++j) edge[j] = bns_edge(m_out[j] % W, W);
   // byte base of pixel row `m + off` of the T region for K chunk kc (slice kk is one more XOR); lanes whose tap is
   // x-padding read the zero row instead
   auto row_bases = [&](int off, int kc, int bad, int (&rb)[MT2]) {
@@ -489,7 +543,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   BNS_BARRIER();
   {
-    if constexpr (FOLD) add_shift(1, acc, std::integral_constant<int, MT2>{});
+    if constexpr (FOLD) bns_add_shift(acc, shp[1]);
     [[maybe_unused]] const float* tb = reinterpret_cast<const float*>(smem + G::TAB);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -566,17 +620,9 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
       if constexpr (FOLD) {
         // shift3 of the quarter and the residual join the accumulators as three MFMAs per tile
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const uint4_t sa = uint4_t{shp[2 + q][i], 0u, 0u, 0u};
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int j = 0; j < MT2; ++j) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, sa), __builtin_bit_cast(half8_t, onesB), acc[i][j], 0, 0, 0);
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, permA[h]), __builtin_bit_cast(half8_t, res[q][i][j][h]),
-                                                                 acc[i][j], 0, 0, 0);
-          }
-        }
+          for (int j = 0; j < MT2; ++j) bns_fold_tail(acc[i][j], shp[2 + q][i], onesB, permA, res[q][i][j]);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
@@ -634,16 +680,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_kernel(const BnsPara
       }
     });
   }
-  if (p.dbg & 32) {       // dev: phase timestamps of wave 0 over the strip's first output pixel (the output is garbage then)
-    ts[5] = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ts[6] = __builtin_amdgcn_s_memtime();
-    if (tid == 0) {
-      unsigned long long* o = reinterpret_cast<unsigned long long*>(p.y + ((size_t)((n * p.H + y0) * W) * p.y_cstride + p.y_coff) * 2);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] = ts[i];
-    }
-  }
+  BNS_TS_TAIL();
 #endif
 }
 
@@ -693,7 +730,6 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
   constexpr int LDS_BYTES = STG + 2 * STGB;
   static_assert(XROWS * 128 <= G::XSTRIDE && NOUT * ROWB <= 61440 && LDS_BYTES <= 163840, "LDS map");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef __attribute__((address_space(3))) void* lds_ptr;
   using c0 = std::integral_constant<int, 0>;
   using c1 = std::integral_constant<int, 1>;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -701,12 +737,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
   const int wcol = wave;
   const int l31 = lane & 31, lhi = lane >> 5;
 
-  int logical;
-  {
-    const int b = blockIdx.x;
-    const int q = p.total >> 3, r = p.total & 7, xcd = b & 7, loc = b >> 3;
-    logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  const int logical = xcd_logical_wg(p.total);
   const int n = logical / p.ppi;
   const int W = p.W;
   const int TWc = XH ? p.TWc : (HEAD ? p.Wo : W);   // output columns of this workgroup; output pixel m = r * TWc + c
@@ -729,12 +760,11 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
   const int npix_halo = (HEAD ? 2 * p.TH + 1 : p.TH + 2) * PW;
   const int iy0 = HEAD ? 2 * y0 - 1 : y0 - 1;          // input row of the patch's first row
 
-  const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.x), 0, p.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.ws), 0, p.ws_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.tab), 0, FOLD ? (2 * P + G::C) * 4 : 6 * G::TABB, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_x = bns_rsrc(p.x, p.x_bytes), rsrc_y = bns_rsrc(p.y, p.y_bytes), rsrc_w = bns_rsrc(p.ws, p.ws_bytes);
+  const __amdgpu_buffer_rsrc_t rsrc_t = bns_rsrc(p.tab, FOLD ? (2 * P + G::C) * 4 : 6 * G::TABB);
   constexpr unsigned kOOB = 0x80000000u;
 
+  // (own copy of the x_voff set-up: NW waves, the column-split form's patch pitch and x-halo, the head form's first row)
   unsigned x_voff[LX];
 #pragma unroll
   for (int t = 0; t < LX; ++t) {
@@ -747,12 +777,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
     x_voff[t] = v;
   }
   const unsigned lane16 = (unsigned)lane * 16u;
-  auto issue_x = [&](int c, int buf) {
-    char* dst = smem + buf * G::XSTRIDE;
-#pragma unroll
-    for (int t = 0; t < LX; ++t)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (lds_ptr)(dst + (t * NW + wave) * 1024), 16, x_voff[t], c * 128, 0, 0);
-  };
+  auto issue_x = [&](int c, int buf) { bns_issue_x<NW>(rsrc_x, smem + buf * G::XSTRIDE, wave, x_voff, c); };
   // the weight fragments of step g for this wave: (kk, tile 2*wcol + i) at g * WSTEP + (kk * NCT + 2*wcol + i) KiB
   static_assert(NS >= 3 && 12 % NS == 0, "ring phase of the unrolled phase-2 body (12 steps per kernel row)");
   constexpr int D = NS - 1;
@@ -783,8 +808,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
       }
   };
   unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define BNSD_TS(i) do { if (p.dbg & 32) ts[i] = __builtin_amdgcn_s_memtime(); } while (0)
-  BNSD_TS(0);
+  BNS_TS(0);
   // Inside a network the block's weights are not in this XCD's L2 when the kernel starts, and every workgroup of the XCD
   // asks for the same lines at the same moment: the stream then costs 17 us of a 46-us block (FT_BNS_DBG=64 in situ).  The
   // first round of workgroups on an XCD therefore TOUCHES the whole stream once, each its own 1/n-th (one dword per
@@ -831,26 +855,11 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
   constexpr int kTabLoads = FOLD ? 6 * CTW : 48 / NW;
   auto load_tables = [&]() {
     if constexpr (FOLD) {
-      const unsigned so = lhi == 0 ? 4u * (unsigned)bns_sigma(l31) : kOOB;
-#pragma unroll
-      for (int e = 0; e < 6; ++e)
-#pragma unroll
-        for (int i = 0; i < CTW; ++i)
-          shp[e][i] = __builtin_amdgcn_raw_buffer_load_b32(rsrc_t, so, 4 * (e * P + (CTW * wcol + i) * 32), 0);
+      bns_load_shp<P>(shp, rsrc_t, l31, lhi, CTW * wcol, 0, 6);
     } else {
 #pragma unroll
       for (int t = 0; t < 48 / NW; ++t)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_t, (lds_ptr)(smem + TABS + (t * NW + wave) * 256), 4, (unsigned)lane * 4u, (t * NW + wave) * 256, 0, 0);
-    }
-  };
-  [[maybe_unused]] auto add_shift = [&](int e, auto& A, auto mtc) {      // A[i][j] += shift of epilogue e (one MFMA per tile)
-    constexpr int MT = decltype(mtc)::value;
-#pragma unroll
-    for (int i = 0; i < CTW; ++i) {
-      const uint4_t sa = uint4_t{shp[e][i], 0u, 0u, 0u};
-#pragma unroll
-      for (int j = 0; j < MT; ++j)
-        A[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, sa), __builtin_bit_cast(half8_t, onesB), A[i][j], 0, 0, 0);
     }
   };
   // order of every wave's (in-order) load queue: x chunk 0, the weights of step 0, the L2 touch, the tables / shift pairs, x chunks 1
@@ -926,7 +935,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
     static_assert(2 * LX + 4 * CTW * D + kTouch + kTabLoads <= 63, "vmcnt immediate");
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * LX + 4 * CTW * D + kTouch + kTabLoads) : "memory");
     BNS_BARRIER();
-    BNSD_TS(7);             // start-up: x chunk 0 of every wave has landed
+    BNS_TS(7);             // start-up: x chunk 0 of every wave has landed
     ldx(c0{}, 0, 0);
     bns_unroll<NC1>([&](auto cc) {
       constexpr int c = decltype(cc)::value;
@@ -955,6 +964,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
           __builtin_amdgcn_sched_group_barrier(0x100, (MT1 + 2) / 3, 0);
         });
       }
+      // (own copy of the residual pick-up: CTW tiles per wave, so the piece index goes by the tile's parity, and hp_out[] of the patch)
       if (!HEAD && !(FT_BNSD_ABL & 2) && c % 4 == (CTW * wcol) / 2) {  // this chunk holds the channels of this wave column for quarter c / 4
         constexpr int q = c / 4;
         const char* xb = smem + buf * G::XSTRIDE;
@@ -1006,11 +1016,11 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
       mma1(c1{}, slot{}, std::integral_constant<int, 3>{});
     });
   }
-  BNSD_TS(1);
+  BNS_TS(1);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   BNS_BARRIER();          // every wave is past its last x-chunk read: the x buffers become T1
   {
-    if constexpr (FOLD) add_shift(0, acc1, std::integral_constant<int, MT1>{});
+    if constexpr (FOLD) bns_add_shift(acc1, shp[0]);
     [[maybe_unused]] const float* tb = reinterpret_cast<const float*>(smem + TABS);
 #pragma unroll
     for (int i = 0; i < CTW; ++i) {
@@ -1033,11 +1043,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
         if constexpr (FOLD) relu_acc16(acc1[i][j], h8);
         else bn_relu_acc16(acc1[i][j], sc, sh, h8);
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          uint4_t u = __builtin_bit_cast(uint4_t, h8[h]);
-          u.x = inside ? u.x : 0u; u.y = inside ? u.y : 0u; u.z = inside ? u.z : 0u; u.w = inside ? u.w : 0u;
-          h8[h] = __builtin_bit_cast(half8_t, u);
-        }
+        for (int h = 0; h < 2; ++h) h8[h] = bns_keep_if(h8[h], inside);
         if (hp < npix_halo) {
           char* rowp = smem + hp * ROWB;
           const int cb = (CTW * wcol + i) * 4 + 2 * lhi;
@@ -1050,7 +1056,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   BNS_BARRIER();          // T1 complete
-  BNSD_TS(2);
+  BNS_TS(2);
 
   // ================= phases 2 + 3 =======================================================================================
   float16_t acc[CTW][MT2];
@@ -1146,11 +1152,11 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
       });
     }
   }
-  BNSD_TS(3);
+  BNS_TS(3);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   BNS_BARRIER();          // every wave is past its last T1 read: T2 overwrites T1
   {
-    if constexpr (FOLD) add_shift(1, acc, std::integral_constant<int, MT2>{});
+    if constexpr (FOLD) bns_add_shift(acc, shp[1]);
     [[maybe_unused]] const float* tb = reinterpret_cast<const float*>(smem + TABS + G::TABB);
 #pragma unroll
     for (int i = 0; i < CTW; ++i) {
@@ -1179,7 +1185,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
   zero_acc();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   BNS_BARRIER();          // T2 complete
-  BNSD_TS(4);
+  BNS_TS(4);
   if constexpr (HEAD) {
     // the head form ends here: the T2 tile (rows = output pixels, 16-byte chunk ^= row & 15) leaves as whole lines
     constexpr int CPRH = ROWB / 16, NSTH = NOUT * CPRH / NT;
@@ -1251,11 +1257,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
     // folded form: shift3 of the quarter and the residual join tile (i, j)'s accumulator as three MFMAs
     [[maybe_unused]] auto fold_tail = [&](auto qc, int i, int j, float16_t (&A)[CTW][MT2]) {
       constexpr int q = decltype(qc)::value;
-      const uint4_t sa = uint4_t{shp[2 + q][i], 0u, 0u, 0u};
-      A[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, sa), __builtin_bit_cast(half8_t, onesB), A[i][j], 0, 0, 0);
-#pragma unroll
-      for (int h = 0; h < 2; ++h)
-        A[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, permA[h]), __builtin_bit_cast(half8_t, res[q][i][j][h]), A[i][j], 0, 0, 0);
+      bns_fold_tail(A[i][j], shp[2 + q][i], onesB, permA, res[q][i][j]);
     };
     auto readout = [&](auto qc) {
       constexpr int q = decltype(qc)::value;
@@ -1299,16 +1301,7 @@ __global__ __launch_bounds__(64 * NW, NW / 4) void bottleneck_stream_direct_kern
       readout(qc);
     });
   }
-  if (p.dbg & 32) {
-    ts[5] = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ts[6] = __builtin_amdgcn_s_memtime();
-    if (tid == 0) {
-      unsigned long long* o = reinterpret_cast<unsigned long long*>(p.y + ((size_t)((n * p.H + y0) * W) * p.y_cstride + p.y_coff) * 2);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] = ts[i];
-    }
-  }
+  BNS_TS_TAIL();
 #endif
 }
 
@@ -1343,19 +1336,13 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
   constexpr int ZROW = 61440, TOUCH = 77824, STG = 81920, STGB = 4 * NOUT * 128;
   static_assert(LX * 4 * 8 * 128 <= G::XSTRIDE && MT1 * 16 * ROWB <= ZROW && STG + 2 * STGB <= 163840, "LDS map");
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef __attribute__((address_space(3))) void* lds_ptr;
   using c0 = std::integral_constant<int, 0>;
   using c1 = std::integral_constant<int, 1>;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, lq = lane >> 4;
 
-  int logical;
-  {
-    const int b = blockIdx.x;
-    const int q = p.total >> 3, r = p.total & 7, xcd = b & 7, loc = b >> 3;
-    logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  const int logical = xcd_logical_wg(p.total);
   const int n = logical / p.ppi;
   const int W = p.W;
   const int y0 = (logical - n * p.ppi) * p.TH;
@@ -1364,10 +1351,8 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
   const int npix_halo = (p.TH + 2) * W;
   const int iy0 = y0 - 1;
 
-  const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.x), 0, p.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.ws), 0, p.ws_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.tab), 0, (2 * P + G::C) * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_x = bns_rsrc(p.x, p.x_bytes), rsrc_y = bns_rsrc(p.y, p.y_bytes), rsrc_w = bns_rsrc(p.ws, p.ws_bytes);
+  const __amdgpu_buffer_rsrc_t rsrc_t = bns_rsrc(p.tab, (2 * P + G::C) * 4);
   constexpr unsigned kOOB = 0x80000000u;
 
   unsigned x_voff[LX];
@@ -1382,12 +1367,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
     x_voff[t] = v;
   }
   const unsigned lane16 = (unsigned)lane * 16u;
-  auto issue_x = [&](int c, int buf) {
-    char* dst = smem + buf * G::XSTRIDE;
-#pragma unroll
-    for (int t = 0; t < LX; ++t)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (lds_ptr)(dst + (t * 4 + wave) * 1024), 16, x_voff[t], c * 128, 0, 0);
-  };
+  auto issue_x = [&](int c, int buf) { bns_issue_x<4>(rsrc_x, smem + buf * G::XSTRIDE, wave, x_voff, c); };
   // the weight fragments of step g for this wave: (slice ks, tile 4 * wave + t) at g * WSTEP + (ks * 16 + 4 * wave + t) KiB
   static_assert(NS >= 3 && 12 % NS == 0, "ring phase of the unrolled phase-2 body (12 steps per kernel row)");
   constexpr int D = NS - 1;
@@ -1403,7 +1383,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
     load_a_slice(slotc, g, c1{});
   };
   unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  BNSD_TS(0);
+  BNS_TS(0);
   // the L2 touch of the direct kernel: exactly kTouch loads per thread, behind x chunk 0 and the weights of step 0
   constexpr int kTouch = 6;
   auto issue_touch = [&]() {
@@ -1422,10 +1402,9 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
   };
   // the shift pair of MFMA row l15 of every (epilogue, channel tile) of this wave (lanes 16..63 hold k = 8..31 of the shift slice: zeros,
   // fetched out of range; those of phase 3 are fetched behind phase 1, where its registers are free), and the two 0/1 matrices of the
-  // residual MFMAs
+  // residual MFMAs.  (own copies: rows of 16-channel tiles, not bns_sigma's order)
   unsigned shp[6][CT];
   uint4_t permA[2];
-  const uint4_t onesB = uint4_t{0x3C003C00u, 0u, 0u, 0u};
   {
     const bool on = lq == (l15 >> 2);
 #pragma unroll
@@ -1445,16 +1424,6 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
 #pragma unroll
       for (int t = 0; t < CT; ++t)
         shp[e][t] = __builtin_amdgcn_raw_buffer_load_b32(rsrc_t, so, 4 * (e * P + 64 * wave + 4 * t), 0);
-  };
-  auto add_shift = [&](int e, auto& A, auto mtc) {      // A[t][j] += shift of epilogue e (one MFMA per tile)
-    constexpr int MT = decltype(mtc)::value;
-#pragma unroll
-    for (int t = 0; t < CT; ++t) {
-      const uint4_t sa = uint4_t{shp[e][t], 0u, 0u, 0u};
-#pragma unroll
-      for (int j = 0; j < MT; ++j)
-        A[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, sa), __builtin_bit_cast(half8_t, onesB), A[t][j], 0, 0, 0);
-    }
   };
   // order of every wave's (in-order) load queue: x chunk 0, the weights of step 0, the L2 touch, the shift pairs, x chunks 1 and 2,
   // the weights of steps 1 .. D-1.  The first wait below counts them: nothing may move across the touch / shift-pair group.
@@ -1512,7 +1481,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
     static_assert(2 * LX + 2 * CT * D + kTouch + kTabLoads <= 63, "vmcnt immediate");
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * LX + 2 * CT * D + kTouch + kTabLoads) : "memory");
     BNS_BARRIER();
-    BNSD_TS(7);             // start-up: x chunk 0 of every wave has landed
+    BNS_TS(7);             // start-up: x chunk 0 of every wave has landed
     ldx(c0{}, 0, 0);
     bns_unroll<NC1>([&](auto cc) {
       constexpr int c = decltype(cc)::value;
@@ -1564,7 +1533,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
       mma1(c1{}, slot{}, c1{});
     });
   }
-  BNSD_TS(1);
+  BNS_TS(1);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   BNS_BARRIER();          // every wave is past its last x-chunk read: the x buffers become T1
   // the lane's 16 consecutive channels of pixel tile j as two 16-byte pieces: fp16(relu(acc))
@@ -1573,7 +1542,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
     h8[1] = relu_acc4x2(A[2][j], A[3][j]);
   };
   {
-    add_shift(0, acc1, std::integral_constant<int, MT1>{});
+    bns_add_shift(acc1, shp[0]);
 #pragma unroll
     for (int j = 0; j < MT1; ++j) {
       const int hp = j * 16 + l15;
@@ -1582,11 +1551,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
       half8_t h8[2];
       pieces(acc1, j, h8);
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        uint4_t u = __builtin_bit_cast(uint4_t, h8[h]);
-        u.x = inside ? u.x : 0u; u.y = inside ? u.y : 0u; u.z = inside ? u.z : 0u; u.w = inside ? u.w : 0u;
-        h8[h] = __builtin_bit_cast(half8_t, u);
-      }
+      for (int h = 0; h < 2; ++h) h8[h] = bns_keep_if(h8[h], inside);
       if (hp < npix_halo) {
         char* rowp = smem + hp * ROWB;
         const int cb = wave * 8 + 2 * lq;
@@ -1597,7 +1562,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   BNS_BARRIER();          // T1 complete
-  BNSD_TS(2);
+  BNS_TS(2);
   load_tables(2, 6);
 
   // ================= phases 2 + 3 =======================================================================================
@@ -1611,10 +1576,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
   zero_acc();
   int edge[MT2];
 #pragma unroll
-  for (int j = 0; j < MT2; ++j) {
-    const int ox = m_out[j] % W;
-    edge[j] = (ox == 0 ? 1 : 0) | (ox == W - 1 ? 2 : 0);
-  }
+  for (int j = 0; j < MT2; ++j) edge[j] = bns_edge(m_out[j] % W, W);
   // T1 / T2 row of the pixel operand: `off` relative to the lane's own row; the two x-border taps (bad) read the zero row
   auto row_bases = [&](int off, int kc, int bad, int (&rb)[MT2]) {
 #pragma unroll
@@ -1678,11 +1640,11 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
       });
     }
   }
-  BNSD_TS(3);
+  BNS_TS(3);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   BNS_BARRIER();          // every wave is past its last T1 read: T2 overwrites T1
   {
-    add_shift(1, acc, std::integral_constant<int, MT2>{});
+    bns_add_shift(acc, shp[1]);
 #pragma unroll
     for (int j = 0; j < MT2; ++j) {
       const int m = m_out[j];
@@ -1697,7 +1659,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
   zero_acc();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   BNS_BARRIER();          // T2 complete
-  BNSD_TS(4);
+  BNS_TS(4);
 
   // ---- phase 3: four quarters of P output channels; a quarter leaves through one of the wave's two private staging tiles ----------
   {
@@ -1726,7 +1688,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
         for (int j = 0; j < MT2; ++j) rb[j] = rbn[j];
       });
       // shift3 of the quarter and the residual join every tile's accumulator as two MFMAs
-      add_shift(2 + q, acc, std::integral_constant<int, MT2>{});
+      bns_add_shift(acc, shp[2 + q]);
 #pragma unroll
       for (int t = 0; t < CT; ++t)
 #pragma unroll
@@ -1753,16 +1715,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_tile16_kernel(const 
       }
     });
   }
-  if (p.dbg & 32) {
-    ts[5] = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ts[6] = __builtin_amdgcn_s_memtime();
-    if (tid == 0) {
-      unsigned long long* o = reinterpret_cast<unsigned long long*>(p.y + ((size_t)((n * p.H + y0) * W) * p.y_cstride + p.y_coff) * 2);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] = ts[i];
-    }
-  }
+  BNS_TS_TAIL();
 #endif
 }
 
@@ -1800,7 +1753,6 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_direct128_kernel(con
   static_assert(NS >= 2 && (3 * KC) % NS == 0, "ring phase of the unrolled phase-2 body");
   constexpr int D = NS - 1;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef __attribute__((address_space(3))) void* lds_ptr;
   using c0 = std::integral_constant<int, 0>;
   using c1 = std::integral_constant<int, 1>;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1808,12 +1760,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_direct128_kernel(con
   const int wcol = wave % WCOLS, pg = wave / WCOLS;
   const int l31 = lane & 31, lhi = lane >> 5;
 
-  int logical;
-  {
-    const int b = blockIdx.x;
-    const int q = p.total >> 3, r = p.total & 7, xcd = b & 7, loc = b >> 3;
-    logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
+  const int logical = xcd_logical_wg(p.total);
   const int n = logical / p.ppi;
   const int y0 = (logical - n * p.ppi) * p.TH;
   const int W = p.W;
@@ -1821,10 +1768,8 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_direct128_kernel(con
   const int npix_out = rows_out * W;
   const int npix_halo = (p.TH + 2) * W;
 
-  const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.x), 0, p.x_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, p.y_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.ws), 0, p.ws_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_t = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.tab), 0, (2 * P + G::C) * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_x = bns_rsrc(p.x, p.x_bytes), rsrc_y = bns_rsrc(p.y, p.y_bytes), rsrc_w = bns_rsrc(p.ws, p.ws_bytes);
+  const __amdgpu_buffer_rsrc_t rsrc_t = bns_rsrc(p.tab, (2 * P + G::C) * 4);
   constexpr unsigned kOOB = 0x80000000u;
 
   // x chunk: row = halo pixel, 128 bytes (64 channels); see the ring kernel
@@ -1840,12 +1785,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_direct128_kernel(con
     x_voff[t] = v;
   }
   const unsigned lane16 = (unsigned)lane * 16u;
-  auto issue_x = [&](int c, int buf) {
-    char* dst = smem + buf * G::XSTRIDE;
-#pragma unroll
-    for (int t = 0; t < LX; ++t)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (lds_ptr)(dst + (t * 4 + wave) * 1024), 16, x_voff[t], c * 128, 0, 0);
-  };
+  auto issue_x = [&](int c, int buf) { bns_issue_x<4>(rsrc_x, smem + buf * G::XSTRIDE, wave, x_voff, c); };
   // the weight fragments of step g for this wave: (kk, tile 2*wcol + i) at g * WSTEP + (kk * NCT + 2*wcol + i) KiB; both pixel groups of a
   // wave column load the same ones.  Steps past the end of the stream: out of range by the lane offset, zeros, never multiplied.
   uint4_t areg[NS][4][2];
@@ -1863,7 +1803,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_direct128_kernel(con
     load_a_half(slotc, g, c1{});
   };
   unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  BNSD_TS(0);
+  BNS_TS(0);
   // the first round of workgroups on an XCD pulls the block's weight stream into that XCD's L2 (see the direct kernel): EXACTLY kTouch
   // loads per thread, issued behind x chunk 0 and the weights of step 0 and counted by the first hand-counted wait
   constexpr int kTouch = 6;
@@ -1900,24 +1840,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_direct128_kernel(con
   }
   // (the pairs of epilogue 0 in the prologue, those of epilogues 1 .. 5 behind phase 1's loop, where the registers are free again)
   constexpr int kTabLoads = 2;
-  auto load_shp = [&](int e0, int e1) {
-    const unsigned so = lhi == 0 ? 4u * (unsigned)bns_sigma(l31) : kOOB;
-#pragma unroll
-    for (int e = e0; e < e1; ++e)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-        shp[e][i] = __builtin_amdgcn_raw_buffer_load_b32(rsrc_t, so, 4 * (e * P + (2 * wcol + i) * 32), 0);
-  };
-  auto add_shift = [&](int e, auto& A, auto mtc) {      // A[i][j] += shift of epilogue e (one MFMA per tile)
-    constexpr int MT = decltype(mtc)::value;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const uint4_t sa = uint4_t{shp[e][i], 0u, 0u, 0u};
-#pragma unroll
-      for (int j = 0; j < MT; ++j)
-        A[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, sa), __builtin_bit_cast(half8_t, onesB), A[i][j], 0, 0, 0);
-    }
-  };
+  auto load_shp = [&](int e0, int e1) { bns_load_shp<P>(shp, rsrc_t, l31, lhi, 2 * wcol, e0, e1); };
   // order of every wave's (in-order) load queue: x chunk 0, the weights of step 0, the L2 touch, the shift pairs, x chunk 1, the weights
   // of steps 1 .. D-1, x chunk 2 (the order of the steady state: weights of step c+1 between x chunks c+1 and c+2).  The first wait
   // counts them: compiler fences on both sides of the touch / shift group.
@@ -1976,7 +1899,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_direct128_kernel(con
     static_assert(2 * LX + 8 * D + kTouch + kTabLoads <= 63, "vmcnt immediate");
     asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * LX + 8 * D + kTouch + kTabLoads) : "memory");
     BNS_BARRIER();
-    BNSD_TS(7);             // start-up: x chunk 0 of every wave has landed
+    BNS_TS(7);             // start-up: x chunk 0 of every wave has landed
     ldx(c0{}, 0, 0);
     bns_unroll<NC1>([&](auto cc) {
       constexpr int c = decltype(cc)::value;
@@ -2039,12 +1962,12 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_direct128_kernel(con
       mma1(c1{}, slot{}, std::integral_constant<int, 3>{});
     });
   }
-  BNSD_TS(1);
+  BNS_TS(1);
   load_shp(1, 6);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   BNS_BARRIER();          // every wave is past its last x-chunk read: the x buffers become T1
   {
-    add_shift(0, acc1, std::integral_constant<int, MT1>{});
+    bns_add_shift(acc1, shp[0]);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -2056,11 +1979,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_direct128_kernel(con
         half8_t h8[2];
         relu_acc16(acc1[i][j], h8);
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          uint4_t u = __builtin_bit_cast(uint4_t, h8[h]);
-          u.x = inside ? u.x : 0u; u.y = inside ? u.y : 0u; u.z = inside ? u.z : 0u; u.w = inside ? u.w : 0u;
-          h8[h] = __builtin_bit_cast(half8_t, u);
-        }
+        for (int h = 0; h < 2; ++h) h8[h] = bns_keep_if(h8[h], inside);
         if (hp < npix_halo) {
           char* rowp = smem + hp * ROWB;
           const int cb = (2 * wcol + i) * 4 + 2 * lhi;
@@ -2073,7 +1992,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_direct128_kernel(con
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   BNS_BARRIER();          // T1 complete
-  BNSD_TS(2);
+  BNS_TS(2);
 
   // ================= phases 2 + 3: weight steps G2 .. GEND-1, pixel operand from T1 / T2 ==============================================
   float16_t acc[2][MT2];
@@ -2089,10 +2008,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_direct128_kernel(con
   // x-border flags of this lane's output pixels: bit 0 = first column (tap kx = 0 is padding), bit 1 = last column
   int edge[MT2];
 #pragma unroll
-  for (int j = 0; j < MT2; ++j) {
-    const int ox = m_out[j] % W;
-    edge[j] = (ox == 0 ? 1 : 0) | (ox == W - 1 ? 2 : 0);
-  }
+  for (int j = 0; j < MT2; ++j) edge[j] = bns_edge(m_out[j] % W, W);
   auto row_bases = [&](int off, int kc, int bad, int (&rb)[MT2]) {
 #pragma unroll
     for (int j = 0; j < MT2; ++j) {
@@ -2156,11 +2072,11 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_direct128_kernel(con
       });
     }
   }
-  BNSD_TS(3);
+  BNS_TS(3);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   BNS_BARRIER();          // every wave is past its last T1 read: T2 overwrites T1
   {
-    add_shift(1, acc, std::integral_constant<int, MT2>{});
+    bns_add_shift(acc, shp[1]);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
@@ -2178,7 +2094,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_direct128_kernel(con
   zero_acc();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   BNS_BARRIER();          // T2 complete
-  BNSD_TS(4);
+  BNS_TS(4);
 
   // ---- phase 3: four quarters of P output channels, K = P; the tile of a quarter leaves through one of two LDS staging tiles ---------
   {
@@ -2206,17 +2122,9 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_direct128_kernel(con
       char* stg = smem + ((q & 1) ? STG1 : STG0);
       // shift3 of the quarter and the residual join the accumulators as three MFMAs per tile
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const uint4_t sa = uint4_t{shp[2 + q][i], 0u, 0u, 0u};
+      for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < MT2; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, sa), __builtin_bit_cast(half8_t, onesB), acc[i][j], 0, 0, 0);
-#pragma unroll
-          for (int h = 0; h < 2; ++h)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, permA[h]), __builtin_bit_cast(half8_t, res[q][i][j][h]),
-                                                               acc[i][j], 0, 0, 0);
-        }
-      }
+        for (int j = 0; j < MT2; ++j) bns_fold_tail(acc[i][j], shp[2 + q][i], onesB, permA, res[q][i][j]);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -2241,16 +2149,7 @@ __global__ __launch_bounds__(256, 1) void bottleneck_stream_direct128_kernel(con
       }
     });
   }
-  if (p.dbg & 32) {       // dev: phase timestamps of wave 0 over the strip's first output pixel (the output is garbage then)
-    ts[5] = __builtin_amdgcn_s_memtime();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ts[6] = __builtin_amdgcn_s_memtime();
-    if (tid == 0) {
-      unsigned long long* o = reinterpret_cast<unsigned long long*>(p.y + ((size_t)((n * p.H + y0) * W) * p.y_cstride + p.y_coff) * 2);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) o[i] = ts[i];
-    }
-  }
+  BNS_TS_TAIL();
 #endif
 }
 
@@ -2335,10 +2234,21 @@ __global__ __launch_bounds__(256) void bns_pack_head_kernel(const half_t* __rest
   out[idx] = *reinterpret_cast<const uint4_t*>(src);
 }
 
+// The forms a plan can take.  The integers are what ft_bottleneck_stream_variant returns and what FT_BNS_VARIANT forces: they stay.
+enum BnsVariant {
+  BNS_RING128_LARGE = 0,    // bottleneck_stream_kernel<128, 4, 3>
+  BNS_RING256 = 1,          // bottleneck_stream_kernel<256, 4, 3>
+  BNS_DIRECT256 = 2,        // bottleneck_stream_direct_kernel<3, 2>: 64-pixel strips, weights straight to registers
+  BNS_DIRECT256_XSPLIT = 3, // bottleneck_stream_direct_kernel<2, 1, XH>: column-split
+  BNS_HEAD = 4,             // bottleneck_stream_direct_kernel<4, 1, HEADC = 8>: stride-2 head of an entry block (its own stream, no folding)
+  BNS_RING128_SMALL = 5,    // bottleneck_stream_kernel<128, 3, 2>
+  BNS_TILE16 = 6,           // bottleneck_stream_tile16_kernel: 256 planes on 16-pixel tiles (its own stream layout)
+  BNS_DIRECT128_LARGE = 7,  // bottleneck_stream_direct128_kernel<4, 3>
+  BNS_DIRECT128_SMALL = 8,  // bottleneck_stream_direct128_kernel<3, 2>
+};
+
 struct BnsPlan {
-  int variant;   // 0: <128,4,3>  1: <256,4,3>  2: <256,3,2>  3: <256,2,1> column-split (direct kernel only)  4: stride-2 head <4,1>
-                 // 5: <128,3,2>  6: 256 planes on 16-pixel tiles (bottleneck_stream_tile16_kernel; its own stream layout)
-                 // 7: <128,4,3> weights straight to registers (bottleneck_stream_direct128_kernel)  8: <128,3,2> likewise
+  int variant;   // BnsVariant
   int TH, ppi;
   int TWc, csplit;
 };
@@ -2370,7 +2280,7 @@ static int bns_plan(const ft_bottleneck_desc* d, BnsPlan* out) {
     if (th < 1) return FT_ERR_UNSUPPORTED;
     th = th < Ho ? th : Ho;
     th = ceil_div(Ho, ceil_div(Ho, th));
-    *out = BnsPlan{4, th, ceil_div(Ho, th), d->W, 1};
+    *out = BnsPlan{BNS_HEAD, th, ceil_div(Ho, th), d->W, 1};
     return FT_OK;
   }
   if (d->dtype != FT_F16 || d->projection || (d->P != 128 && d->P != 256) || d->C != 4 * d->P || d->stride > 1) return FT_ERR_UNSUPPORTED;
@@ -2408,7 +2318,7 @@ static int bns_plan(const ft_bottleneck_desc* d, BnsPlan* out) {
     if (force128 == 1 || force128 == 2) direct = false;
     if (force128 == 3 || force128 == 4) direct = d->folded != 0;
     const int th = small ? th_s : th_b;
-    *out = BnsPlan{direct ? (small ? 8 : 7) : (small ? 5 : 0), th, ceil_div(d->H, th), d->W, 1};
+    *out = BnsPlan{direct ? (small ? BNS_DIRECT128_SMALL : BNS_DIRECT128_LARGE) : (small ? BNS_RING128_SMALL : BNS_RING128_LARGE), th, ceil_div(d->H, th), d->W, 1};
     return FT_OK;
   }
   const int th_big = rows(96, 120), th_small = rows(64, 96);
@@ -2427,7 +2337,7 @@ static int bns_plan(const ft_bottleneck_desc* d, BnsPlan* out) {
   // 16-pixel tiles: <= 48 output pixels on <= 80 halo pixels; folded operands and four waves only
   const int th_16 = d->folded ? rows(48, 80) : 0;
   int pick;
-  if (force == 1 || force == 2 || (force == 3 && xs) || (force == 6 && th_16 >= 1)) pick = force;
+  if (force == BNS_RING256 || force == BNS_DIRECT256 || (force == BNS_DIRECT256_XSPLIT && xs) || (force == BNS_TILE16 && th_16 >= 1)) pick = force;
   else {
     // Both variants run one workgroup per CU at the matrix pipe's pace (the FT_BNS_DBG=64/128 ablation: same phase times
     // with every load out of range), so the cost of a launch is rounds of 256 workgroups x MFMAs per workgroup:
@@ -2436,55 +2346,55 @@ static int bns_plan(const ft_bottleneck_desc* d, BnsPlan* out) {
       const long long wg = (long long)d->N * ceil_div(d->H, th);
       return ((wg + 255) / 256) * (long long)(64 * mt1 + 208 * mt2);
     };
-    if (th_big < 1) pick = 2;
-    else if (th_small < 1) pick = 1;
-    else pick = cost(th_big, 4, 3) <= cost(th_small, 3, 2) ? 1 : 2;
-    if (pick == 1 && th_big < 1) pick = 2;
-    if (pick == 2 && th_small < 1) pick = th_big >= 1 ? 1 : 3;
-    long long cf = pick == 1 ? cost(th_big, 4, 3) : (pick == 2 ? cost(th_small, 3, 2) : -1);
+    if (th_big < 1) pick = BNS_DIRECT256;
+    else if (th_small < 1) pick = BNS_RING256;
+    else pick = cost(th_big, 4, 3) <= cost(th_small, 3, 2) ? BNS_RING256 : BNS_DIRECT256;
+    if (pick == BNS_RING256 && th_big < 1) pick = BNS_DIRECT256;
+    if (pick == BNS_DIRECT256 && th_small < 1) pick = th_big >= 1 ? BNS_RING256 : BNS_DIRECT256_XSPLIT;
+    long long cf = pick == BNS_RING256 ? cost(th_big, 4, 3) : (pick == BNS_DIRECT256 ? cost(th_small, 3, 2) : -1);
     // the 16-pixel tiles in the same unit (one 32-pixel tile of a pair of channel tiles for a K16 step = 64 MFMA cycles = two 16-pixel
     // tiles of four channel tiles for half a K32 step): 5 halo and 3 output tiles count as 2.5 and 1.5.  Not under FT_BNS_WAVES=8
     // (the eight-wave forms are 32-pixel kernels).
     if (th_16 >= 1 && dev_env_int("FT_BNS_WAVES", 4) != 8) {
       const long long wg = (long long)d->N * ceil_div(d->H, th_16);
       const long long c16 = ((wg + 255) / 256) * (long long)(32 * 5 + 104 * 3);
-      if (cf < 0 || c16 < cf) { pick = 6; cf = c16; }
+      if (cf < 0 || c16 < cf) { pick = BNS_TILE16; cf = c16; }
     }
-    if (xs && pick != 3) {
+    if (xs && pick != BNS_DIRECT256_XSPLIT) {
       // the column-split form only where it needs no more rounds of 256 workgroups than it saves in work per workgroup
       const long long wgx = (long long)d->N * ceil_div(d->H, x_th) * xs;
       const long long cx = ((wgx + 255) / 256) * (long long)(64 * 2 + 208 * 1);
-      if (cx < cf) pick = 3;
+      if (cx < cf) pick = BNS_DIRECT256_XSPLIT;
     }
   }
-  if (pick == 6) {
-    *out = BnsPlan{6, th_16, ceil_div(d->H, th_16), d->W, 1};
+  if (pick == BNS_TILE16) {
+    *out = BnsPlan{BNS_TILE16, th_16, ceil_div(d->H, th_16), d->W, 1};
     return FT_OK;
   }
-  if (pick == 1 && th_big < 1) pick = 2;
-  if (pick == 2 && th_small < 1) pick = th_big >= 1 ? 1 : 3;
-  if (pick == 3) {
-    *out = BnsPlan{3, x_th, ceil_div(d->H, x_th) * xs, x_tw, xs};
+  if (pick == BNS_RING256 && th_big < 1) pick = BNS_DIRECT256;
+  if (pick == BNS_DIRECT256 && th_small < 1) pick = th_big >= 1 ? BNS_RING256 : BNS_DIRECT256_XSPLIT;
+  if (pick == BNS_DIRECT256_XSPLIT) {
+    *out = BnsPlan{BNS_DIRECT256_XSPLIT, x_th, ceil_div(d->H, x_th) * xs, x_tw, xs};
     return FT_OK;
   }
-  const int th = pick == 1 ? th_big : th_small;
+  const int th = pick == BNS_RING256 ? th_big : th_small;
   *out = BnsPlan{pick, th, ceil_div(d->H, th), d->W, 1};
+  return FT_OK;
+}
+
+// One launch of a stream kernel, one workgroup per strip.  The kernel is a template argument: the LDS opt-in of FT_RAISE_LDS is kept
+// per kernel (and per device).
+template <void (*kernel)(BnsParams)>
+static int bns_run(int threads, int lds, const char* name, const BnsParams& p, hipStream_t s) {
+  FT_RAISE_LDS(kernel, lds);
+  hipLaunchKernelGGL(kernel, dim3(p.total), dim3(threads), lds, s, p);
+  FT_LAUNCH_CHECK(name);
   return FT_OK;
 }
 
 template <int P, int MT1, int MT2, bool FOLD = false>
 static int bns_launch(const BnsParams& p, hipStream_t s) {
-  auto k = bottleneck_stream_kernel<P, MT1, MT2, FOLD>;
-  static bool attr_done[64] = {};          // the LDS opt-in is per device
-  int dev = 0;
-  FT_HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    FT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, BnsGeom<P>::LDS_BYTES));
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
-  hipLaunchKernelGGL(k, dim3(p.total), dim3(256), BnsGeom<P>::LDS_BYTES, s, p);
-  FT_LAUNCH_CHECK("bottleneck_stream_kernel");
-  return FT_OK;
+  return bns_run<bottleneck_stream_kernel<P, MT1, MT2, FOLD>>(256, BnsGeom<P>::LDS_BYTES, "bottleneck_stream_kernel", p, s);
 }
 
 #ifndef FT_BNS_SLOTS
@@ -2495,18 +2405,8 @@ static int bns_launch(const BnsParams& p, hipStream_t s) {
 #endif
 template <int MT1, int MT2, bool XH, int HEADC = 0, int NW = 4, bool FOLD = false>
 static int bns_launch_direct(const BnsParams& p, hipStream_t s) {
-  auto k = bottleneck_stream_direct_kernel<MT1, MT2, XH, XH ? FT_BNS_XH_SLOTS : FT_BNS_SLOTS, HEADC, NW, FOLD>;
-  constexpr int lds = 81920 + 2 * MT2 * 32 * 512;
-  static bool attr_done[64] = {};          // the LDS opt-in is per device
-  int dev = 0;
-  FT_HIP_CHECK(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64 || !attr_done[dev]) {
-    FT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    if (dev >= 0 && dev < 64) attr_done[dev] = true;
-  }
-  hipLaunchKernelGGL(k, dim3(p.total), dim3(64 * NW), lds, s, p);
-  FT_LAUNCH_CHECK("bottleneck_stream_direct_kernel");
-  return FT_OK;
+  return bns_run<bottleneck_stream_direct_kernel<MT1, MT2, XH, XH ? FT_BNS_XH_SLOTS : FT_BNS_SLOTS, HEADC, NW, FOLD>>(
+      64 * NW, 81920 + 2 * MT2 * 32 * 512, "bottleneck_stream_direct_kernel", p, s);
 }
 
 #ifndef FT_BNS_SLOTS128
@@ -2514,21 +2414,12 @@ static int bns_launch_direct(const BnsParams& p, hipStream_t s) {
 #endif
 template <int MT1, int MT2>
 static int bns_launch_direct128(const BnsParams& p, hipStream_t s) {
-  auto k = bottleneck_stream_direct128_kernel<MT1, MT2, MT1 == 4 ? FT_BNS_SLOTS128 : 3>;
-  constexpr int lds = BnsGeom<128>::LDS_BYTES;
-  FT_RAISE_LDS(k, lds);
-  hipLaunchKernelGGL(k, dim3(p.total), dim3(256), lds, s, p);
-  FT_LAUNCH_CHECK("bottleneck_stream_direct128_kernel");
-  return FT_OK;
+  return bns_run<bottleneck_stream_direct128_kernel<MT1, MT2, MT1 == 4 ? FT_BNS_SLOTS128 : 3>>(256, BnsGeom<128>::LDS_BYTES,
+                                                                                             "bottleneck_stream_direct128_kernel", p, s);
 }
 
 static int bns_launch_tile16(const BnsParams& p, hipStream_t s) {
-  auto k = bottleneck_stream_tile16_kernel<FT_BNS_SLOTS>;
-  constexpr int lds = 81920 + 2 * 4 * 48 * 128;
-  FT_RAISE_LDS(k, lds);
-  hipLaunchKernelGGL(k, dim3(p.total), dim3(256), lds, s, p);
-  FT_LAUNCH_CHECK("bottleneck_stream_tile16_kernel");
-  return FT_OK;
+  return bns_run<bottleneck_stream_tile16_kernel<FT_BNS_SLOTS>>(256, 81920 + 2 * 4 * 48 * 128, "bottleneck_stream_tile16_kernel", p, s);
 }
 
 }  // namespace
@@ -2542,13 +2433,13 @@ extern "C" int ft_bottleneck_stream_supported(const ft_bottleneck_desc* d) {
 extern "C" int ft_bottleneck_stream_folds(const ft_bottleneck_desc* d) {
   ft::BnsPlan pl;
   if (ft::bns_plan(d, &pl) != FT_OK) return 0;
-  return pl.variant != 4;
+  return pl.variant != ft::BNS_HEAD;
 }
 
 extern "C" int ft_bottleneck_stream_layout(const ft_bottleneck_desc* d) {
   ft::BnsPlan pl;
   if (ft::bns_plan(d, &pl) != FT_OK) return -1;
-  return pl.variant == 6 ? 1 : 0;
+  return pl.variant == ft::BNS_TILE16 ? 1 : 0;
 }
 
 extern "C" int ft_bottleneck_stream_variant(const ft_bottleneck_desc* d) {
@@ -2560,7 +2451,7 @@ extern "C" int ft_bottleneck_stream_variant(const ft_bottleneck_desc* d) {
 extern "C" long long ft_bottleneck_stream_weight_bytes(const ft_bottleneck_desc* d) {
   ft::BnsPlan pl;
   if (ft::bns_plan(d, &pl) != FT_OK) return 0;
-  if (pl.variant == 4) return (long long)(d->C / 64 + 9 * ft::BnsGeom<256>::KC) * ft::BnsGeom<256>::WSTEP;
+  if (pl.variant == ft::BNS_HEAD) return (long long)(d->C / 64 + 9 * ft::BnsGeom<256>::KC) * ft::BnsGeom<256>::WSTEP;
   return d->P == 128 ? (long long)ft::BnsGeom<128>::GEND * ft::BnsGeom<128>::WSTEP : (long long)ft::BnsGeom<256>::GEND * ft::BnsGeom<256>::WSTEP;
 }
 
@@ -2570,10 +2461,10 @@ extern "C" int ft_bottleneck_stream_pack(const ft_bottleneck_desc* d, const void
   BnsPlan pl;
   const int st = bns_plan(d, &pl);
   if (st != FT_OK) return st;
-  if (!w1 || !w2 || (!w3 && pl.variant != 4) || !wstream) return FT_ERR_INVALID_ARG;
+  if (!w1 || !w2 || (!w3 && pl.variant != BNS_HEAD) || !wstream) return FT_ERR_INVALID_ARG;
   hipStream_t s = as_stream(stream);
   const half_t *a = static_cast<const half_t*>(w1), *b = static_cast<const half_t*>(w2), *c = static_cast<const half_t*>(w3);
-  if (pl.variant == 4) {
+  if (pl.variant == BNS_HEAD) {
     const int n16 = (int)(ft_bottleneck_stream_weight_bytes(d) / 16);
     hipLaunchKernelGGL(bns_pack_head_kernel, dim3(ceil_div(n16, 256)), dim3(256), 0, s, a, b, static_cast<uint4_t*>(wstream), d->C);
     FT_LAUNCH_CHECK("bns_pack_head_kernel");
@@ -2582,7 +2473,7 @@ extern "C" int ft_bottleneck_stream_pack(const ft_bottleneck_desc* d, const void
   if (d->P == 128) {
     const int n16 = BnsGeom<128>::GEND * BnsGeom<128>::WSTEP / 16;
     hipLaunchKernelGGL(bns_pack_kernel<128>, dim3(ceil_div(n16, 256)), dim3(256), 0, s, a, b, c, static_cast<uint4_t*>(wstream));
-  } else if (pl.variant == 6) {
+  } else if (pl.variant == BNS_TILE16) {
     const int n16 = BnsGeom<256>::GEND * BnsGeom<256>::WSTEP / 16;
     hipLaunchKernelGGL(bns_pack16_kernel, dim3(ceil_div(n16, 256)), dim3(256), 0, s, a, b, c, static_cast<uint4_t*>(wstream));
   } else {
@@ -2600,7 +2491,7 @@ extern "C" int ft_bottleneck_stream_fwd(const ft_bottleneck_desc* d, const void*
   const int st = bns_plan(d, &pl);
   if (st != FT_OK) return st;
   if (!x || !wstream || !tables || !y || x == y) return FT_ERR_INVALID_ARG;
-  if (d->folded && pl.variant == 4) return FT_ERR_UNSUPPORTED;      // the stride-2 head keeps its tables (ft_bottleneck_stream_folds)
+  if (d->folded && pl.variant == BNS_HEAD) return FT_ERR_UNSUPPORTED;      // the stride-2 head keeps its tables (ft_bottleneck_stream_folds)
   BnsParams p{};
   p.x = static_cast<const char*>(x);
   p.y = static_cast<char*>(y);
@@ -2608,13 +2499,13 @@ extern "C" int ft_bottleneck_stream_fwd(const ft_bottleneck_desc* d, const void*
   p.tab = reinterpret_cast<const char*>(tables);
   p.H = d->H; p.W = d->W; p.TH = pl.TH; p.ppi = pl.ppi;
   p.TWc = pl.TWc; p.csplit = pl.csplit;
-  if (pl.variant == 4) { p.Ho = d->H / 2; p.Wo = d->W / 2; }
+  if (pl.variant == BNS_HEAD) { p.Ho = d->H / 2; p.Wo = d->W / 2; }
   p.total = d->N * pl.ppi;
   p.x_cstride = d->x_cstride; p.x_coff = d->x_coff; p.y_cstride = d->y_cstride; p.y_coff = d->y_coff;
   p.x_bytes = (unsigned)((size_t)d->N * d->H * d->W * d->x_cstride * 2);
   p.y_bytes = (unsigned)((size_t)d->N * d->H * d->W * d->y_cstride * 2);
   p.ws_bytes = (unsigned)ft_bottleneck_stream_weight_bytes(d);
-  if (pl.variant == 4) p.y_bytes = (unsigned)((size_t)d->N * p.Ho * p.Wo * d->y_cstride * 2);
+  if (pl.variant == BNS_HEAD) p.y_bytes = (unsigned)((size_t)d->N * p.Ho * p.Wo * d->y_cstride * 2);
   static const int dbg = dev_env_int("FT_BNS_DBG", 0);
   p.dbg = dbg;
   if (dbg & 64) p.ws_bytes = 0;     // dev: every weight load out of range (returns 0, no L2 access): the kernel's time without its weight stream
@@ -2624,25 +2515,25 @@ extern "C" int ft_bottleneck_stream_fwd(const ft_bottleneck_desc* d, const void*
   // for the column-split form (R101 384x288 at 16 crops: 34.4 -> 33.3 us per block, R50 at 16 crops 30.0 -> 28.5), four for the
   // full-width strips (batch 64: 46.1 vs 46.0 us — the eight-wave form gains in phases 1 and 3 what its doubled pixel-operand
   // reads cost in phase 2; both forms sit on the CU's 64 B/clk weight path: 32 KiB of fragments per 16-MFMA step)
-  const bool waves8 = dev_env_int("FT_BNS_WAVES", pl.variant == 3 ? 8 : 4) == 8;
+  const bool waves8 = dev_env_int("FT_BNS_WAVES", pl.variant == BNS_DIRECT256_XSPLIT ? 8 : 4) == 8;
   if (d->folded) {
     switch (pl.variant) {
-      case 0: return bns_launch<128, 4, 3, true>(p, s);
-      case 5: return bns_launch<128, 3, 2, true>(p, s);
-      case 7: return bns_launch_direct128<4, 3>(p, s);
-      case 8: return bns_launch_direct128<3, 2>(p, s);
-      case 1: return bns_launch<256, 4, 3, true>(p, s);
-      case 6: return bns_launch_tile16(p, s);
-      case 3: return waves8 ? bns_launch_direct<2, 1, true, 0, 8, true>(p, s) : bns_launch_direct<2, 1, true, 0, 4, true>(p, s);
+      case BNS_RING128_LARGE: return bns_launch<128, 4, 3, true>(p, s);
+      case BNS_RING128_SMALL: return bns_launch<128, 3, 2, true>(p, s);
+      case BNS_DIRECT128_LARGE: return bns_launch_direct128<4, 3>(p, s);
+      case BNS_DIRECT128_SMALL: return bns_launch_direct128<3, 2>(p, s);
+      case BNS_RING256: return bns_launch<256, 4, 3, true>(p, s);
+      case BNS_TILE16: return bns_launch_tile16(p, s);
+      case BNS_DIRECT256_XSPLIT: return waves8 ? bns_launch_direct<2, 1, true, 0, 8, true>(p, s) : bns_launch_direct<2, 1, true, 0, 4, true>(p, s);
       default: return waves8 ? bns_launch_direct<3, 2, false, 0, 8, true>(p, s) : bns_launch_direct<3, 2, false, 0, 4, true>(p, s);
     }
   }
   switch (pl.variant) {
-    case 0: return bns_launch<128, 4, 3>(p, s);
-    case 5: return bns_launch<128, 3, 2>(p, s);
-    case 1: return bns_launch<256, 4, 3>(p, s);
-    case 3: return waves8 ? bns_launch_direct<2, 1, true, 0, 8>(p, s) : bns_launch_direct<2, 1, true>(p, s);
-    case 4: return waves8 ? bns_launch_direct<4, 1, false, 8, 8>(p, s) : bns_launch_direct<4, 1, false, 8>(p, s);
+    case BNS_RING128_LARGE: return bns_launch<128, 4, 3>(p, s);
+    case BNS_RING128_SMALL: return bns_launch<128, 3, 2>(p, s);
+    case BNS_RING256: return bns_launch<256, 4, 3>(p, s);
+    case BNS_DIRECT256_XSPLIT: return waves8 ? bns_launch_direct<2, 1, true, 0, 8>(p, s) : bns_launch_direct<2, 1, true>(p, s);
+    case BNS_HEAD: return waves8 ? bns_launch_direct<4, 1, false, 8, 8>(p, s) : bns_launch_direct<4, 1, false, 8>(p, s);
     default:     // 64-pixel strips at 256 planes: weights straight to registers
       return waves8 ? bns_launch_direct<3, 2, false, 0, 8>(p, s) : bns_launch_direct<3, 2, false>(p, s);
   }

@@ -61,6 +61,14 @@ typedef uint32_t uint4_t __attribute__((ext_vector_type(4)));
 typedef float float2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 
+// XCD-aware workgroup order of the fused bottleneck kernels: block b runs on XCD b % 8; every XCD gets one contiguous range of the
+// `total` logical workgroups (the first total % 8 XCDs one more than the others), so that neighbours share that XCD's L2.
+__device__ __forceinline__ int xcd_logical_wg(int total) {
+  const int b = blockIdx.x;
+  const int q = total >> 3, r = total & 7, xcd = b & 7, loc = b >> 3;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
+}
+
 // act(v) for k = 0 (ReLU) / 0 < k <= 1 (LeakyReLU) / 1 (none) = `v > 0 ? v : k * v` with torch's value for EVERY input, three vector
 // instructions: t = k (*) v with (*) = v_mul_legacy_f32 (0 * x = 0 for every x, so ReLU(-inf) = 0 where the IEEE product -inf * 0 = NaN
 // made the two-instruction max(v, k * v) of rounds 2-5 return -inf), then `!(v <= 0) ? v : t`: the negated ordered compare keeps a NaN

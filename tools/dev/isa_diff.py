@@ -6,8 +6,10 @@
 A refactor that must not change device code is checked here instead of on a GPU: every kernel (symbol with an .amdhsa_kernel block)
 of the new tree has to exist in the parent under the same mangled name - or under the parent instantiation given for it on the
 command line, where template parameters were dropped - with identical instruction text (comments stripped, the kernel's own name
-and the function index of local labels .LBB<n>_ replaced) and equal VGPR / SGPR / AGPR-offset / LDS / scratch figures.  Parent
-kernels that the new tree no longer has are listed.  Exit status 1 if any surviving kernel differs or has no parent."""
+and the function index of local labels .LBB<n>_ replaced) and equal VGPR / SGPR / AGPR-offset / LDS / scratch figures.  A kernel
+that differs is reported as "class B" if it has the same number of instruction lines with the same mnemonic (first token) on every line
+and equal descriptor figures, i.e. only operands changed.  Parent kernels that the new tree no longer has are listed.  Exit status 1 if
+any surviving kernel differs (class B included) or has no parent."""
 import os, re, subprocess, sys
 
 DESC = (".amdhsa_next_free_vgpr", ".amdhsa_next_free_sgpr", ".amdhsa_accum_offset", ".amdhsa_group_segment_fixed_size",
@@ -66,7 +68,10 @@ def compare(pdir, ndir, renames):
                 same += 1
             else:
                 what = "descriptor " + " ".join(f"{a}->{b}" for a, b in zip(par[pname][1], desc)) if desc != par[pname][1] else "instructions"
-                print(f"{unit}: DIFFERS ({what}): {name}")
+                # class B: the same instructions in the same places, only operands differ (register numbers, operand order)
+                mnem = [[line.split()[0] for line in b.split("\n")] for b in (par[pname][0], body)]
+                cls = "class B" if desc == par[pname][1] and mnem[0] == mnem[1] else "not class B"
+                print(f"{unit}: DIFFERS ({what}; {cls}): {name}")
                 bad += 1
         gone = [p for p in par if p not in used]
         for p in gone:
