@@ -106,9 +106,27 @@ struct CdGeom {
 // TAPS: a kh x kw convolution (3x3 / stride 2 of the stages' entry blocks, blocks.py:92-95 with stride on conv2): chunk c of
 // the K walk is channel chunk c % cpt of tap c / cpt; the pixel operand of a tap is a gather (input pixel oy*s - pad + ky,
 // ox*s - pad + kx: one base offset per ring row + a scalar tap offset, taps that leave the image read out of range = zeros).
-template <int KSPLIT, bool HAS_RES, int NCH, bool TAPS = false>
+// DECONV: ConvTranspose2d(4, 2, 1) on whole small maps as ONE GEMM + col2im (the pose head's first deconv, pose_deconv.py:43:
+// 2048 -> 256 on 8x6 maps).  col[pixel][ky][kx][co] = x[pixel][:] . w[:, co, ky, kx] is a plain 1x1-shaped GEMM over the INPUT
+// pixels with N = 16 taps x Cout, and y[2iy-1+ky][2ix-1+kx][co] sums the taps that land on an output pixel.  A channel block's 256
+// columns are [ky][kx][16 channels] (cdt_pack_kernel), so wave w owns ky = w and a lane's 16 accumulator values of tile (i, j) are
+// the 16 channels of tap kx = 2i + lhi for its pixel; a pixel tile is p.cpt WHOLE images (<= 96 pixels), so the scatter never
+// leaves the workgroup: accumulators -> fp32 slab in LDS (over the dead ring) -> every thread gathers its output elements in a
+// fixed tap order (no atomics) -> folded BN, activation, fp16.  An output row takes only the ky of one parity, so the slab is
+// built in two passes of eight taps (odd ky -> even output rows, then even ky -> odd rows): 48 KiB, the size of the 1x1 form's
+// staging tile, instead of 96 KiB — two workgroups stay resident per CU as in the 1x1 form, which a 96-KiB slab would halve.
+// The K walk is the 1x1 form's, untouched.  Fields reused: p.M = INPUT pixels, p.HqWq = Hi * Wi, p.Hi / p.Wi, p.cpt = images per tile.
+//   The form is selected by a NEGATIVE chunk-count parameter, cd_transposed(NCH) = -1 - NCH (-1: run-time loop), not by a flag of its
+// own: one more template parameter would rename every existing instantiation, and a shared body behind two kernels compiled to
+// different code for all of them (tools/dev/isa_diff.py).
+constexpr int cd_transposed(int nch) { return -1 - nch; }
+
+template <int KSPLIT, bool HAS_RES, int NCHF, bool TAPS = false>
 __global__ __launch_bounds__(256, 1) void conv_direct_kernel(const CdParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  constexpr bool DECONV = NCHF < 0;
+  constexpr int NCH = DECONV ? -1 - NCHF : NCHF;
+  static_assert(!DECONV || (KSPLIT == 1 && !HAS_RES && !TAPS), "the transposed form is the plain N-tile-256 walk");
   using G = CdGeom<KSPLIT>;
   constexpr int MT = G::MT, BP = G::BP, BN = G::BN, ROWB = G::ROWB, XB = G::XB, LX = G::LX;
   constexpr int TAB = G::LDS_BYTES - 2 * BN * 4;
@@ -132,7 +150,8 @@ __global__ __launch_bounds__(256, 1) void conv_direct_kernel(const CdParams p) {
   // wmajor (round 6): the XCD's contiguous range walks the pixel tiles of ONE channel block first, so an XCD's L2 holds its own
   // 1 / 8 of the weight stream instead of all of it (layers whose weights outweigh their input: see cd_wmajor)
   const int cb = p.wmajor ? logical / p.npt : logical % p.ncb, pt = p.wmajor ? logical % p.npt : logical / p.ncb;
-  const int m0 = pt * BP;
+  const int tile_rows = DECONV ? p.cpt * p.HqWq : BP;      // DECONV: whole images, the rows behind them stay zero
+  const int m0 = pt * tile_rows;
   const int nchunk = NCH > 0 ? NCH : p.nc1 + p.nc2;
 
   const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.x), 0, p.x_bytes, 0x00020000);
@@ -169,7 +188,7 @@ __global__ __launch_bounds__(256, 1) void conv_direct_kernel(const CdParams p) {
       x_voff[t] = v;
       continue;
     }
-    if (m < p.M) {
+    if (m < p.M && (!DECONV || row < tile_rows)) {
       v = (unsigned)((m * p.x_cstride + p.x_coff) * 2) + swz;
       if (p.nc2) {
         const int n = m / p.HqWq, rem = m - n * p.HqWq, qy = rem / p.Wq, qx = rem - qy * p.Wq;
@@ -216,9 +235,9 @@ __global__ __launch_bounds__(256, 1) void conv_direct_kernel(const CdParams p) {
   };
 
   // folded-BN table of this channel block -> LDS (scale may be absent: the K-concat form folds it into the weights)
-  if (tid < BN / 4) {
+  if (tid < (DECONV ? 16 : BN) / 4) {              // DECONV: a channel block is 16 output channels
     const float4_t one = {1.f, 1.f, 1.f, 1.f}, zero = {0.f, 0.f, 0.f, 0.f};
-    const int ch = cb * BN + tid * 4;
+    const int ch = cb * (DECONV ? 16 : BN) + tid * 4;
     reinterpret_cast<float4_t*>(smem + TAB)[tid] = p.scale ? *reinterpret_cast<const float4_t*>(p.scale + ch) : one;
     reinterpret_cast<float4_t*>(smem + TAB + BN * 4)[tid] = p.shift ? *reinterpret_cast<const float4_t*>(p.shift + ch) : zero;
   }
@@ -345,6 +364,82 @@ __global__ __launch_bounds__(256, 1) void conv_direct_kernel(const CdParams p) {
   // ---- epilogue ----------------------------------------------------------------------------------------------------------
   const float* tsc = reinterpret_cast<const float*>(smem + TAB);
   const float* tsh = tsc + BN;
+  if constexpr (DECONV) {
+    // col2im slab of one pass: row = input pixel (512 B: 2 ky x 4 kx taps x 16 channels fp32), 16-byte position = (ky / 2) * 16 +
+    // kx * 4 + channel quad, its low four bits XOR the row (a 512-byte pitch would put the 32 pixels of a wave's store in one bank group)
+    static_assert(BP * 512 <= TAB, "LDS map");
+    const float act_k = p.act == FT_ACT_RELU ? 0.f : (p.act == FT_ACT_LEAKY ? p.slope : 1.f);
+    const int HW = p.HqWq, Wo = 2 * p.Wi, OHW2 = 2 * HW;      // output pixels of one row parity per image
+    const int nitems = p.cpt * OHW2 * 2;                      // one item = 8 channels of one output pixel: <= 96 x 2 x 2 = 384
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+      if (pass) CD_BARRIER();                                 // every gather of pass 0 has its values
+      if ((wave & 1) != pass) {                               // pass 0: ky = 1, 3 (waves 1, 3); pass 1: ky = 0, 2
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+          for (int j = 0; j < MT; ++j) {
+            const int row = j * 32 + l31, slot = (wave >> 1) * 4 + 2 * i + lhi;
+#pragma unroll
+            for (int g4 = 0; g4 < 4; ++g4) {
+              const float4_t v = {acc[i][j][4 * g4], acc[i][j][4 * g4 + 1], acc[i][j][4 * g4 + 2], acc[i][j][4 * g4 + 3]};
+              *reinterpret_cast<float4_t*>(smem + row * 512 + (((slot * 4 + g4) ^ (row & 15)) << 4)) = v;
+            }
+          }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      CD_BARRIER();
+      if (pass == 0) CD_TS(4);
+      // gather: output pixel (oy, ox), oy = 2 * oyh + pass, takes the taps ky = (oy + 1) % 2 + {0, 2} from input row iy = (oy + 1 - ky) / 2
+      // (kx / ix likewise) that lie inside the map, summed in ascending (ky, kx) order
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int idx = tid + 256 * k;
+        if (idx >= nitems) continue;
+        const int h = idx & 1, q = idx >> 1;
+        const int img = q / OHW2, rem = q - img * OHW2, oyh = rem / Wo, ox = rem - oyh * Wo, oy = 2 * oyh + pass;
+        float4_t s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+          const int iy = oyh + pass - a;                    // ky = 1 - pass + 2 a
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            const int kx = ((ox + 1) & 1) + 2 * b, ix = (ox + 1 - kx) >> 1;
+            if ((unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi) {
+              const int row = img * HW + iy * p.Wi + ix, pos = (a * 4 + kx) * 4 + 2 * h;
+              const char* rp = smem + row * 512;
+              s0 += *reinterpret_cast<const float4_t*>(rp + ((pos ^ (row & 15)) << 4));
+              s1 += *reinterpret_cast<const float4_t*>(rp + (((pos + 1) ^ (row & 15)) << 4));
+            }
+          }
+        }
+        const float4_t sc0 = *reinterpret_cast<const float4_t*>(tsc + 8 * h), sc1 = *reinterpret_cast<const float4_t*>(tsc + 8 * h + 4);
+        const float4_t sh0 = *reinterpret_cast<const float4_t*>(tsh + 8 * h), sh1 = *reinterpret_cast<const float4_t*>(tsh + 8 * h + 4);
+        half8_t o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          o[e] = (half_t)act_mul(s0[e] * sc0[e] + sh0[e], act_k);
+          o[4 + e] = (half_t)act_mul(s1[e] * sc1[e] + sh1[e], act_k);
+        }
+        // 32-byte pieces of 512-byte pixel rows: plain stores, the L2 merges a line's pieces (FT_CD_DBG=64, dev: write-through)
+        const int mi = m0 + img * HW;               // first input pixel of the image; its first output pixel is 4 * mi
+        const unsigned voff = mi < p.M ? (unsigned)(((mi * 4 + oy * Wo + ox) * p.y_cstride + p.y_coff + cb * 16 + 8 * h) * 2) : kOOB;
+        if (p.dbg & 64) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_t, o), rsrc_y, voff, 0, 16);
+        else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_t, o), rsrc_y, voff, 0, 0);
+      }
+    }
+    if (p.dbg & 32) {                               // stamps 0-3 into the tile's first output pixel, 4-7 into its second
+      ts[5] = __builtin_amdgcn_s_memtime();
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      ts[6] = __builtin_amdgcn_s_memtime();
+      if (tid < 2 && m0 < p.M) {
+        unsigned long long* o = reinterpret_cast<unsigned long long*>(p.y + ((size_t)(m0 * 4 + tid) * p.y_cstride + p.y_coff + cb * 16) * 2);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = ts[4 * tid + i];
+      }
+    }
+    return;
+  }
   constexpr int SCPR = G::STG_ROWB / 16;            // 16-byte chunks per staging row: 32 or 8
   constexpr int SMASK = SCPR < 16 ? SCPR - 1 : 15;
   char* stg = smem + G::PART;
@@ -1396,6 +1491,25 @@ __global__ __launch_bounds__(256) void cd_pack_kernel(const half_t* __restrict__
   out[idx] = v;
 }
 
+// The transposed form's stream: cd_pack_kernel<1>'s fragment order for the matrix [N = (16-channel group, ky, kx, channel)][K = Cin],
+// from the four 2x2 phase sets of the implicit GEMM ([4 phases][cout_pad][kpad], k = tap * Cin + ci; ft_conv_tap_source:
+// phase (py, px) tap (ty, tx) holds kernel element ky = py ? 2 ty : 1 + 2 ty, kx likewise — so ky odd <=> py = 0 and ty = ky / 2).
+__global__ __launch_bounds__(256) void cdt_pack_kernel(const half_t* __restrict__ w, uint4_t* __restrict__ out, int nchunk, int ncb,
+                                                       int kpad, int cout_pad) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= ncb * nchunk * 2048) return;
+  const int lane = idx & 63;
+  int f = idx >> 6;
+  const int i = f & 1; f >>= 1;
+  const int kk = f & 3; f >>= 2;
+  const int wv = f & 3; f >>= 2;
+  const int c = f % nchunk, cb = f / nchunk;
+  const int col = (2 * wv + i) * 32 + cd_sigma(lane & 31);        // column inside the channel block: [ky][kx][16 channels]
+  const int ky = col >> 6, kx = (col >> 4) & 3, co = cb * 16 + (col & 15);
+  const int phase = ((ky & 1) ? 0 : 2) + ((kx & 1) ? 0 : 1), tap = (ky >> 1) * 2 + (kx >> 1);
+  const int k = tap * (nchunk * 64) + c * 64 + kk * 16 + 8 * (lane >> 5);
+  out[idx] = *reinterpret_cast<const uint4_t*>(w + ((size_t)phase * cout_pad + co) * kpad + k);
+}
 
 // ---- 1x1, K = 256, MANY pixels (layer2.0.conv1: 256 -> 128 on 196 k pixels at batch 64): weight-stationary, persistent -----
 // That layer is HBM-bound (150 MB) and ran at 3.1 TB/s on the tiled kernels: a tile's life there is load -> 4 K-steps ->
@@ -1606,6 +1720,39 @@ static int cd_plan(const ft_conv_desc* d, CdPlan* out) {
   return FT_OK;
 }
 
+// The transposed form (conv_direct_kernel, DECONV): ConvTranspose2d(4, 2, 1), fp16, whole maps of at most 96 pixels, 16-channel blocks.
+// ksplit = 1, nc1 = Cin / 64, npt = ceil(N / images per tile), ncb = Cout / 16.  Larger maps (12x9 of the 384x288 configuration)
+// stay on the implicit GEMM.
+static int cdt_plan(const ft_conv_desc* d, CdPlan* out) {
+  if (!d) return FT_ERR_INVALID_ARG;
+  if (d->act == FT_ACT_LEAKY && !(d->slope >= 0.f && d->slope <= 1.f)) return FT_ERR_UNSUPPORTED;
+  if (d->dtype != FT_F16 || d->transposed != 1 || d->kh != 4 || d->kw != 4 || d->stride != 2 || d->pad != 1) return FT_ERR_UNSUPPORTED;
+  if (d->has_residual || d->x2_cin || d->tail_cout || d->pool || d->x_wpitch || d->shift_nstride || d->x_nchw_f32 ||
+      d->out_layout != FT_LAYOUT_NHWC) return FT_ERR_UNSUPPORTED;
+  if (d->N <= 0 || d->Hi <= 0 || d->Wi <= 0 || d->Cin <= 0 || d->Cout <= 0) return FT_ERR_UNSUPPORTED;
+  if (d->Ho != 2 * d->Hi || d->Wo != 2 * d->Wi) return FT_ERR_INVALID_ARG;
+  if ((long long)d->Hi * d->Wi > 96 || d->Cin % 64 || d->Cout % 16) return FT_ERR_UNSUPPORTED;
+  if (d->x_coff % 8 || d->x_cstride % 8 || d->y_coff % 8 || d->y_cstride % 8) return FT_ERR_UNSUPPORTED;
+  if (d->x_cstride < d->x_coff + d->Cin || d->y_cstride < d->y_coff + d->Cout) return FT_ERR_INVALID_ARG;
+  const long long lim = 1LL << 31;
+  if ((long long)d->N * d->Hi * d->Wi * d->x_cstride * 2 >= lim || (long long)d->N * d->Ho * d->Wo * d->y_cstride * 2 >= lim ||
+      32LL * d->Cin * d->Cout >= lim) return FT_ERR_UNSUPPORTED;
+  const int ipw = 96 / (d->Hi * d->Wi);
+  *out = CdPlan{1, d->Cin / 64, 0, (d->N + ipw - 1) / ipw, d->Cout / 16};
+  return FT_OK;
+}
+
+template <int NCH>
+static int cdt_launch(const CdParams& p, hipStream_t s) {
+  auto k = conv_direct_kernel<1, false, cd_transposed(NCH)>;
+  constexpr int lds = CdGeom<1>::LDS_BYTES;
+  static_assert(lds <= 163840, "LDS map");
+  FT_RAISE_LDS(k, lds);
+  hipLaunchKernelGGL(k, dim3(p.npt * p.ncb), dim3(256), lds, s, p);
+  FT_LAUNCH_CHECK("conv_direct_kernel (transposed)");
+  return FT_OK;
+}
+
 template <int KSPLIT, bool HAS_RES, int NCH, bool TAPS = false>
 static int cd_launch(const CdParams& p, hipStream_t s) {
   auto k = conv_direct_kernel<KSPLIT, HAS_RES, NCH, TAPS>;
@@ -1668,6 +1815,7 @@ extern "C" int ft_conv_direct_supported(const ft_conv_desc* d) {
   ft::CdPlan pl;
   ft::C3Plan p3;
   ft::WsPlan pw;
+  if (d && d->transposed) return ft::cdt_plan(d, &pl);                    // ConvTranspose2d(4, 2, 1) on whole small maps: GEMM + col2im
   if (d && d->kh == 5) return ft::ws_plan(d, &pw);                        // 5x5 / stride 2 on 64 channels: register-stationary (conv_wstat.hip)
   if (d && d->kh == 3 && ft::c3_plan(d, &p3) == FT_OK) return FT_OK;     // whole small maps; other 3x3s: the gather form
   return ft::cd_plan(d, &pl);
@@ -1680,6 +1828,7 @@ extern "C" int ft_conv_direct_stream_id(const ft_conv_desc* d) {
   ft::CdPlan pl;
   ft::C3Plan p3;
   ft::WsPlan pw;
+  if (d && d->transposed) return ft::cdt_plan(d, &pl) == FT_OK ? (0x60000000 | (pl.nc1 << 12) | pl.ncb) : -1;
   if (d && d->kh == 5) return ft::ws_plan(d, &pw) == FT_OK ? (0x50000000 | pw.ncg) : -1;
   if (d && d->kh == 3 && ft::c3_plan(d, &p3) == FT_OK) return 0x40000000 | (p3.stride == 2 ? (p3.ipw == 2 ? 0x30000000 : 0x10000000) : 0) | (p3.ncb << 8) | p3.spt;
   if (ft::cd_plan(d, &pl) != FT_OK) return -1;
@@ -1690,6 +1839,7 @@ extern "C" long long ft_conv_direct_weight_bytes(const ft_conv_desc* d) {
   ft::CdPlan pl;
   ft::C3Plan p3;
   ft::WsPlan pw;
+  if (d && d->transposed) return ft::cdt_plan(d, &pl) == FT_OK ? (long long)pl.ncb * pl.nc1 * 32768 : 0;
   if (d && d->kh == 5) return ft::ws_plan(d, &pw) == FT_OK ? ft::ws_weight_bytes(pw) : 0;
   if (d && d->kh == 3 && ft::c3_plan(d, &p3) == FT_OK) return (long long)p3.ncb * 4 * 9 * p3.spt * 8192;
   if (ft::cd_plan(d, &pl) != FT_OK) return 0;
@@ -1700,6 +1850,16 @@ extern "C" long long ft_conv_direct_weight_bytes(const ft_conv_desc* d) {
 extern "C" int ft_conv_direct_pack(const ft_conv_desc* d, const void* w_packed, int kpad, int cout_pad, void* wstream, ft_stream_t stream) {
   using namespace ft;
   C3Plan p3;
+  if (d && d->transposed) {
+    CdPlan pt;
+    const int st = cdt_plan(d, &pt);
+    if (st != FT_OK) return st;
+    if (!w_packed || !wstream || kpad < 4 * d->Cin || cout_pad < d->Cout) return FT_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(cdt_pack_kernel, dim3(pt.ncb * pt.nc1 * 8), dim3(256), 0, as_stream(stream), static_cast<const half_t*>(w_packed),
+                       static_cast<uint4_t*>(wstream), pt.nc1, pt.ncb, kpad, cout_pad);
+    FT_LAUNCH_CHECK("cdt_pack_kernel");
+    return FT_OK;
+  }
   if (d && d->kh == 5) {
     WsPlan pw;
     const int st = ws_plan(d, &pw);
@@ -1746,6 +1906,38 @@ extern "C" int ft_conv_direct_fwd(const ft_conv_desc* d, const void* x, const vo
                                   const void* residual, void* y, ft_stream_t stream) {
   using namespace ft;
   C3Plan p3;
+  if (d && d->transposed) {
+    CdPlan pt;
+    const int st = cdt_plan(d, &pt);
+    if (st != FT_OK) return st;
+    if (!x || !wstream || !y) return FT_ERR_INVALID_ARG;
+    CdParams p{};
+    p.x = static_cast<const char*>(x);
+    p.y = static_cast<char*>(y);
+    p.ws = static_cast<const char*>(wstream);
+    p.scale = scale;
+    p.shift = shift;
+    p.M = d->N * d->Hi * d->Wi;                   // rows of the GEMM are INPUT pixels
+    p.nc1 = pt.nc1; p.npt = pt.npt; p.ncb = pt.ncb;
+    p.x_cstride = d->x_cstride; p.x_coff = d->x_coff;
+    p.HqWq = d->Hi * d->Wi; p.Wq = d->Wi; p.Hi = d->Hi; p.Wi = d->Wi;
+    p.cpt = 96 / p.HqWq;                          // whole images per pixel tile
+    p.y_cstride = d->y_cstride; p.y_coff = d->y_coff;
+    p.Cout = d->Cout; p.act = d->act; p.slope = d->slope;
+    p.x_bytes = (unsigned)((size_t)p.M * d->x_cstride * 2);
+    p.y_bytes = (unsigned)((size_t)p.M * 4 * d->y_cstride * 2);
+    p.ws_bytes = (unsigned)((size_t)pt.ncb * pt.nc1 * 32768);
+    static const int dbg = dev_env_int("FT_CD_DBG", 0);
+    p.dbg = dbg;
+    // workgroup order: FT_CD_WMAJOR as for the other forms (see cd_wmajor)
+    p.wmajor = cd_wmajor((long long)p.M * d->Cin * 2, p.ws_bytes, p.npt, p.ncb);
+    hipStream_t s = as_stream(stream);
+    switch (pt.nc1) {      // K = 256 / 2048 (the pose head's deconvs); other K: the run-time loop
+      case 4: return cdt_launch<4>(p, s);
+      case 32: return cdt_launch<32>(p, s);
+      default: return cdt_launch<0>(p, s);
+    }
+  }
   if (d && d->kh == 5) {
     WsPlan pw;
     const int st = ws_plan(d, &pw);

@@ -850,7 +850,8 @@ class FusedConv:
             if tuple(shift.shape) != (x.N, self.cout) or shift.dtype != torch.float32 or not shift.is_contiguous():
                 raise FlowtrackHipError(f"{self.label}: per-sample shift must be contiguous fp32 {(x.N, self.cout)}")
         flops = float(self.lib.ft_conv_flops(ctypes.byref(d)))
-        ws = _direct_stream(self, d, w, x.t.device) if (self.k in (1, 3, 5) and isinstance(y, ActView) and not self.tail_cout and not pool) else None
+        # (a transposed layer on whole small maps has a direct form too: one GEMM + col2im, the pose head's first deconv)
+        ws = _direct_stream(self, d, w, x.t.device) if ((self.k in (1, 3, 5) or self.transposed) and isinstance(y, ActView) and not self.tail_cout and not pool) else None
         if ws is not None:
             # two forms of the same launch; the in-situ benchmark (Program.tune_choices) keeps the faster one
             dd = ConvDesc.from_buffer_copy(d)
