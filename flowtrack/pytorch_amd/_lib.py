@@ -156,6 +156,10 @@ _PROTOTYPES = {
     "ft_bottleneck_cluster_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ft_crop_affine_cv2_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_float,
                                        c_void_p, c_void_p, c_void_p]),
+    "ft_track_propagate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "ft_track_select": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float] + [c_int] * 5
+                        + [c_void_p] * 8),
+    "ft_track_place_rows": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p, c_void_p]),
 }
 
 # declared only under FT_EXPERIMENTAL in the header: measured alternatives the default plans do not record (tests / tools/dev reach them)

@@ -274,9 +274,9 @@ class PoseRunner:
         except Exception:
             pass
 
-    def _launch(self, sl, plan, sh):
-        """Plan replay + rows back into the pinned buffer + event, all through the C ABI on stream `sh`: a captured plan is one
-        ft_graph_launch; the first call of a plan (eager run, tile benchmark, capture) goes through the model."""
+    def _replay(self, plan, sh):
+        """Plan replay on stream `sh`: a captured plan is one ft_graph_launch; the first call of a plan (eager run, tile benchmark,
+        capture) goes through the model."""
         prog = plan.prog
         if plan.runs == 0 or prog.graph_exec is None or torch.cuda.current_device() != self.dev.index:
             if self.stream is not None:
@@ -287,6 +287,10 @@ class PoseRunner:
         else:
             check(self.lib.ft_graph_launch(prog.graph_exec, sh), "ft_graph_launch")
             plan.runs += 1
+
+    def _launch(self, sl, plan, sh):
+        """Plan replay + rows back into the pinned buffer + event, all through the C ABI on stream `sh`."""
+        self._replay(plan, sh)
         check(self.lib.ft_memcpy_async(sl["rows_ptr"], plan.kp_rows.data_ptr(), sl["rows_bytes"], sh), "ft_memcpy_async")
         check(self.lib.ft_event_record(sl["event"], sh), "ft_event_record")
         sl["pending"] = True

@@ -61,6 +61,12 @@ class FlowTracker:
     next_id: int = 0
     tracks: Dict[int, dict] = field(default_factory=dict)   # id -> {"kpts": [K,3], "age": int}
 
+    def propagated(self, ids: List[int], flow) -> np.ndarray:
+        """The poses [len(ids),K,3] of the live tracks `ids` (not empty) in the current frame: moved by the flow from the
+        previous frame, as they are without one.  The one step of update() a subclass may compute elsewhere."""
+        kpts = np.stack([self.tracks[i]["kpts"] for i in ids])
+        return propagate_keypoints(kpts, flow) if flow is not None else kpts
+
     def update(self, keypoints: np.ndarray, boxes: np.ndarray, flow: np.ndarray = None) -> List[int]:
         """keypoints [N,K,3], boxes [N,>=4] (x1,y1,x2,y2[,score]) of the current frame, flow from the previous
         frame (None on the first frame). Returns the track id of every detection."""
@@ -72,10 +78,7 @@ class FlowTracker:
         else:
             boxes = boxes.reshape(len(keypoints), -1)
         ids = list(self.tracks)
-        if flow is not None and ids:
-            moved = propagate_keypoints(np.stack([self.tracks[i]["kpts"] for i in ids]), flow)
-        else:
-            moved = np.stack([self.tracks[i]["kpts"] for i in ids]) if ids else np.zeros((0,) + keypoints.shape[1:])
+        moved = self.propagated(ids, flow) if ids else np.zeros((0,) + keypoints.shape[1:])
         scores = boxes[:, 4] if boxes.shape[1] > 4 else keypoints[..., 2].mean(1)
         order = np.argsort(-scores, kind="stable")
         taken, assigned = set(), [-1] * len(keypoints)
@@ -103,4 +106,31 @@ class FlowTracker:
                     del self.tracks[tid]
         for d, tid in enumerate(assigned):
             self.tracks[tid] = {"kpts": keypoints[d].copy(), "age": 0}
+        return assigned
+
+
+@dataclass
+class HistoryTracker(FlowTracker):
+    """FlowTracker whose propagated poses were computed elsewhere (tracking/device_pass.py: on the GPU, while the clip ran).
+    update()'s third argument is the frame's slab of the moved-pose history instead of a flow field: hist_t [max_age+1,cap,K,2]
+    float64, hist_t[a][s] = the (x, y) of the pose in slot s of frame t-1-a moved into frame t by the flows in between (None on
+    a frame without flow: the tracks stay where they are).  A track remembers the (frame, slot) it was last matched at, so its
+    pose in frame t is hist_t[t-1-frame][slot] with its own scores: the values FlowTracker gets by moving the track once per
+    frame, bit for bit, when the history was built by the same rule."""
+    frame: int = 0                         # index of the frame the next update() is given
+
+    def propagated(self, ids: List[int], flow) -> np.ndarray:
+        kpts = np.stack([self.tracks[i]["kpts"] for i in ids])
+        if flow is None:
+            return kpts
+        age = np.array([self.frame - 1 - self.tracks[i]["origin"][0] for i in ids])
+        slot = np.array([self.tracks[i]["origin"][1] for i in ids])
+        kpts[..., :2] = np.asarray(flow)[age, slot]
+        return kpts
+
+    def update(self, keypoints: np.ndarray, boxes: np.ndarray, flow: np.ndarray = None) -> List[int]:
+        assigned = super().update(keypoints, boxes, flow)
+        for d, tid in enumerate(assigned):
+            self.tracks[tid]["origin"] = (self.frame, d)
+        self.frame += 1
         return assigned

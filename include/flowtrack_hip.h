@@ -595,6 +595,43 @@ int ft_crop_affine_cv2_fwd(const uint8_t* img, int H, int W, int C, const double
                            const float* mean, const float* inv_std, float pre_scale, uint8_t* out_u8, float* out,
                            ft_stream_t stream);
 
+/* ---- N3: the clip's sequential tracking pass on the device ------------------------------------------------------
+ * What tools/tracking/demo.py: tracking_pass_steps does per frame on the host between two pose replays, as three
+ * single-workgroup launches whose counts live in device int32 words: no entry reads a count from the host, so a whole clip is
+ * enqueued without a host wait (tracking/device_pass.py).  Bit-exact to the host functions they restate for finite inputs
+ * with coordinates below 2^31 in magnitude (float64 geometry, float32 NMS, every operation rounded separately; NaN scores
+ * are outside the contract).  Refused arguments launch nothing.
+ *
+ * ft_track_propagate — tracking/tracker.py:21 propagate_keypoints + tracking/flow_utils.py:15 box_propagation
+ * (lib/tracking/flow_utils.py:7-35).  kps_prev: float[P*K*3] (x, y, score); flow: float[2*H*W] (u, v);
+ * older_in: double[n_old*P*K*2] (NULL with n_old = 0).  moved_out: double[(1+n_old)*P*K*2]: [0] = kps_prev's (x, y) moved by
+ * the flow at the truncated, clipped pixel, [1+a] = older_in[a] advanced by the same rule; boxes_out: float[P*4] = the
+ * propagated boxes (joints with score > 0, grown by 15 %, clipped to the image).  All P rows are processed. */
+int ft_track_propagate(const float* kps_prev, const float* flow, int H, int W, const double* older_in, int n_old, int P,
+                       int K, double* moved_out, float* boxes_out, ft_stream_t stream);
+
+/* ft_track_select — tools/tracking/demo.py:118-133: union of the detector boxes dets float[n*5] with the propagated boxes
+ * prop_boxes float[P*4] (scores: column 4 of prev_boxes float[P*5]; the first *count_prev of them, a NULL count_prev or a
+ * count of 0 = no previous poses: the detector boxes pass through, no NMS, no cap), tracking/flow_utils.py:35 nms
+ * (lib/detection/nms/src/nms.c:36-63: score-descending, stable on ties, IoU >= thresh suppresses, +1 widths), the first
+ * max_keep survivors kept.  Out: boxes float[cap*5], src int32[cap] (index into the union, -1 past the count), *count,
+ * kps float[cap*K*3] (kp_det float[n*K*3] rows of the boxes that come from the detector, zero elsewhere), *nprop and
+ * prop_slot int32[bucket] (the slots of the kept propagated boxes, in kept order, -1 past nprop), params float[bucket*3] =
+ * (center_x, center_y, scale) of those boxes for ft_crop_affine_fwd (tracking/net_utils.py:36 boxes_to_center_scale in
+ * float64, cast to float32; rows past nprop repeat row 0, (0, 0, 1) when nprop = 0).  rh, rw: the pose input resolution.
+ * FT_ERR_INVALID_ARG: n > cap, max_keep > cap, sizes <= 0; FT_ERR_UNSUPPORTED: n + P > 512, K > 32, bucket < min(cap, P). */
+int ft_track_select(const float* dets, const float* kp_det, int n, const float* prop_boxes, const float* prev_boxes, int P,
+                    const int32_t* count_prev, int K, float thresh, int max_keep, int cap, int rh, int rw, int bucket,
+                    float* boxes, int32_t* src, int32_t* count, float* kps, int32_t* nprop, int32_t* prop_slot,
+                    float* params, ft_stream_t stream);
+
+/* ft_track_place_rows — tracking/net_utils.py:143 heatmap_rows_to_image (the inverse crop affine of
+ * lib/pose/utils/transforms.py:173-184): rows float[bucket*K*3] (x, y, score) in pixels of the h x w heat map ->
+ * kps[prop_slot[j]] for j < *nprop in image pixels; centre and scale recomputed in float64 from boxes float[cap*5]
+ * (params is not read), result cast to float32, score copied.  K <= 32. */
+int ft_track_place_rows(const float* rows, const float* boxes, const int32_t* prop_slot, const int32_t* nprop, int bucket,
+                        int cap, int K, int h, int w, int rh, int rw, float* kps, ft_stream_t stream);
+
 /* ---- experimental entry points (NOT part of the drop-in boundary) -------------------------------------------
  * Measured alternatives of the fused-block kernels that the default plans do not record (profiles/README.md has their
  * numbers).  They are exported by the library so that the tests and tools/dev can reach them, but they are declared only

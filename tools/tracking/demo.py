@@ -34,7 +34,7 @@ if ROOT not in sys.path:
 from flowtrack.pytorch_amd import parallel, synth                                  # noqa: E402
 from flowtrack.pytorch_amd.flownet import models as flow_models                     # noqa: E402
 from flowtrack.pytorch_amd.pose import models as pose_models                        # noqa: E402
-from flowtrack.pytorch_amd.tracking import FlowTracker, GroupPoseRunner, PoseRunner, box_propagation, detect, flow_est, net_utils, pose_est, pose_est_frames  # noqa: E402
+from flowtrack.pytorch_amd.tracking import DeviceTrackingPass, FlowTracker, GroupPoseRunner, PoseRunner, box_propagation, detect, flow_est, net_utils, pose_est, pose_est_frames  # noqa: E402
 
 
 def synthetic_clip(n_frames, H=384, W=512, n_people=5, seed=0):
@@ -160,10 +160,11 @@ def tracking_pass(dets, kp_det, flows, pose_boxes, thresh=0.3, max_boxes=None):
             return done.value
 
 
-def _batched_phases(frames, dets, pose_net, flow_net, rank, world, flow_batch, pose_frames, pose_fn, flow_fn, dev, runner):
+def _batched_phases(frames, dets, pose_net, flow_net, rank, world, flow_batch, pose_frames, pose_fn, flow_fn, dev, runner, on_device=False):
     """Phases 1 and 2 of a clip (both batch-parallel, sharded over ranks): the flow of every (t-1, t) pair and the pose of
     every detector box.  Returns (frames on the device, flows as a pinned host tensor on rank 0 | None, key points [T,nmax,K,3]
-    numpy, timing dict)."""
+    numpy, timing dict).  on_device (the device pass reads both where they are): the flows and the key points as device tensors,
+    neither copied to the host."""
     T = len(frames)
     batched_pose = pose_fn is None
     fr = torch.from_numpy(frames).to(dev)                                     # clip resident in HBM
@@ -180,8 +181,10 @@ def _batched_phases(frames, dets, pose_net, flow_net, rank, world, flow_batch, p
         local[b0 - lo:b1 - lo] = flow_fn(net_utils.pad_pairs_to_64(ims))[:, :, :H, :W]    # edge-replicated to multiples of 64
     flows = parallel.all_gather_rows(local, T - 1)
     # the tracker reads the fields on the host: pinned buffer, copy overlapped with phase 2
-    flows_host = torch.empty(flows.shape, dtype=flows.dtype, pin_memory=dev.type == "cuda") if rank == 0 else None
-    if rank == 0:
+    flows_host = torch.empty(flows.shape, dtype=flows.dtype, pin_memory=dev.type == "cuda") if rank == 0 and not on_device else None
+    if on_device:
+        flows_host = flows
+    elif rank == 0:
         flows_host.copy_(flows, non_blocking=True)
     _sync(dev)
     tm["flow_s"] = time.perf_counter() - t0
@@ -206,7 +209,9 @@ def _batched_phases(frames, dets, pose_net, flow_net, rank, world, flow_batch, p
         for t in range(lo, hi):
             kp = pose_fn(fr[t], dets[t][:, :4])
             kp_local[t - lo, :len(kp)] = torch.from_numpy(np.asarray(kp, dtype=np.float32)).to(dev)
-    kp_all = parallel.all_gather_rows(kp_local, T).cpu().numpy()
+    kp_all = parallel.all_gather_rows(kp_local, T)
+    if not on_device:
+        kp_all = kp_all.cpu().numpy()
     _sync(dev)
     tm["pose_s"] = time.perf_counter() - t0
     return fr, flows_host, kp_all, tm
@@ -221,10 +226,12 @@ def _frame_runner(runner, fr):
 
 
 def run_clip(frames, dets, pose_net, flow_net, rank=0, world=1, thresh=0.3, flow_batch=16, pose_frames=6, pose_fn=None,
-             flow_fn=None, device=None, max_boxes=None):
+             flow_fn=None, device=None, max_boxes=None, device_pass=False):
     """Returns (per-frame dict list on rank 0 | None elsewhere, timing dict).
     pose_fn(frame [H,W,3] uint8 tensor, boxes [n,4]) -> [n,K,3] and flow_fn(ims [b,3,2,Hp,Wp]) -> [b,2,Hp,Wp] default to
-    the HIP networks (pose_est / flow_net); the CPU tests inject stand-ins to check the sharding (device="cpu")."""
+    the HIP networks (pose_est / flow_net); the CPU tests inject stand-ins to check the sharding (device="cpu").
+    device_pass: phase 3 as tracking.DeviceTrackingPass — the whole pass enqueued on the GPU without a host wait, the flows and
+    phase 2's key points read where they are, the ids assigned afterwards; needs the HIP pose net and max_boxes."""
     T = len(frames)
     dev = torch.device(device) if device is not None else next(pose_net.parameters()).device
     # the HIP pose net: one device round trip per call, asynchronous (PoseRunner); any other module that maps crops to heat maps
@@ -235,10 +242,21 @@ def run_clip(frames, dets, pose_net, flow_net, rank=0, world=1, thresh=0.3, flow
         pose_fn = lambda frame, boxes: pose_est(pose_net, frame, boxes, max_batch=8)     # noqa: E731
     if flow_fn is None:
         flow_fn = flow_net
+    if device_pass and runner is None:
+        raise ValueError("device_pass runs the HIP pose net's plans: it takes no pose_fn / stand-in pose module")
     fr, flows_host, kp_all, tm = _batched_phases(frames, dets, pose_net, flow_net, rank, world, flow_batch, pose_frames,
-                                                 None if batched else pose_fn, flow_fn, dev, runner)
+                                                 None if batched else pose_fn, flow_fn, dev, runner, on_device=device_pass)
     if rank != 0:
         return None, tm
+    if device_pass:
+        t0 = time.perf_counter()
+        dpass = DeviceTrackingPass(pose_net)
+        out = dpass.run(fr, dets, kp_all, flows_host.contiguous(), thresh, max_boxes)
+        tm["track_s"] = time.perf_counter() - t0
+        tm.update({"track_" + k: v for k, v in dpass.last_timing.items()})
+        dpass.close()
+        runner.close()
+        return out, tm
     # ---- phase 3: sequential tracking pass ----------------------------------------------------------------
     t0 = time.perf_counter()
     flows_np = flows_host.numpy()
@@ -404,6 +422,9 @@ def main(argv=None):
     ap.add_argument("--flip_test", action="store_true",
                     help="pose with the flip test: every crop and its mirror image through the net, heat maps averaged with the COCO "
                          "left/right joints swapped back, inside the runners' plans (DeconvResnet.flip_pairs); needs --pose_classes 17")
+    ap.add_argument("--device_pass", action="store_true",
+                    help="run the sequential tracking pass on the GPU without a host round trip per frame (tracking.DeviceTrackingPass; "
+                         "single clip, needs a --max_boxes bound)")
     ap.add_argument("--max_boxes", type=str, default="auto",
                     help="boxes kept per frame after NMS: 'none' (the reference: every survivor), an integer, '2x' = twice the "
                          "detector boxes; 'auto' = 'none' with --pose_model, '2x' with the synthetic (untrained) weights")
@@ -421,6 +442,8 @@ def main(argv=None):
             raise SystemExit("--flip_test swaps the COCO left/right joints: it needs --pose_classes 17")
         pose_net.flip_pairs = tuple(COCO_FLIP_PAIRS)       # every PoseRunner / GroupPoseRunner plan of this net becomes a flip plan
     if args.clips > 1:
+        if args.device_pass:
+            raise SystemExit("--device_pass runs one clip (the interleaved clips share their host pass)")
         if world != 1:
             raise SystemExit("--clips is the per-GPU throughput mode: run one process per GPU, each with its own clips")
         clips = [synthetic_clip(args.frames, n_people=args.people, seed=c) for c in range(args.clips)]
@@ -434,18 +457,18 @@ def main(argv=None):
                 args.clips, args.frames, "interleaved" if mode else "one after the other", dt, args.clips * args.frames / dt))
         return 0
     frames, dets = synthetic_clip(args.frames, n_people=args.people)
-    run_clip(frames, dets, pose_net, flow_net, rank, world, max_boxes=max_boxes)          # warm-up: every plan / graph the timed run replays
+    run_clip(frames, dets, pose_net, flow_net, rank, world, max_boxes=max_boxes, device_pass=args.device_pass)   # warm-up: every plan / graph the timed run replays
     parallel.barrier()
     t0 = time.perf_counter()
-    out, tm = run_clip(frames, dets, pose_net, flow_net, rank, world, max_boxes=max_boxes)
+    out, tm = run_clip(frames, dets, pose_net, flow_net, rank, world, max_boxes=max_boxes, device_pass=args.device_pass)
     parallel.barrier()
     dt = time.perf_counter() - t0
     if rank == 0:
         n_ids = len({i for f in out for i in f["ids"]})
         print("clip: {} frames {}x{} on {} GPU(s): {:.2f} s = {:.1f} frames/s (flow {:.2f} s, detector-box pose {:.2f} s, "
-              "tracking pass {:.2f} s); {} track ids for {} people".format(
+              "{}tracking pass {:.2f} s); {} track ids for {} people".format(
                   args.frames, frames.shape[2], frames.shape[1], world, dt, args.frames / dt, tm["flow_s"], tm["pose_s"],
-                  tm["track_s"], n_ids, args.people))
+                  "device " if args.device_pass else "", tm["track_s"], n_ids, args.people))
         if args.save:
             np.savez_compressed(args.save, boxes=np.array([f["boxes"] for f in out], dtype=object),
                                 ids=np.array([f["ids"] for f in out], dtype=object), allow_pickle=True)
