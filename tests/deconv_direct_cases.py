@@ -7,6 +7,8 @@ import torch.nn.functional as F
 
 from flowtrack.pytorch_amd import synth
 
+from conv_bound import derived_bound
+
 # name, N, Hi, Wi, Cin, Cout, (x_coff, y_coff) of the views inside wider buffers
 CASES = [
     ("n1_8x6_k2048_unrolled", 1, 8, 6, 2048, 48, (0, 0)),      # Cin 2048: the unrolled 32-chunk walk; one image in a two-image tile
@@ -47,7 +49,7 @@ def bound(Cin, S, pre, scale, want):
     """Per element: worst-case fp32 accumulation of the 4 * Cin exact fp16 x fp16 products of an output element (every partial sum
     is at most S, one rounding of 2^-24 relative each), doubled for the summation order inside an MFMA; the rounding of the sum
     into the scale / shift FMA; one rounding to fp16 (2^-11 relative, 2^-25 absolute in the subnormal range)."""
-    return 2.0 * (4 * Cin * 2.0 ** -24 * S + 2.0 ** -23 * pre.abs()) * scale.abs().view(1, -1, 1, 1) + 2.0 ** -11 * want.abs() + 2.0 ** -25
+    return derived_bound(4 * Cin, S, pre, scale, want)
 
 
 def sequential_fp32(x, w, scale, shift):
