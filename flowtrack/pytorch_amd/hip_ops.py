@@ -1465,6 +1465,17 @@ def record_upsample4x(prog: Program, x: torch.Tensor, y: torch.Tensor, mul: floa
     prog.add("ft_upsample_bilinear4x", x.data_ptr(), y.data_ptr(), N, C, h, w, ctypes.c_float(mul), keep=(x, y))
 
 
+def record_upsample_ac(prog: Program, x: ActView, y: ActView, scale: Optional[torch.Tensor] = None) -> None:
+    """y = scale[c] * F.upsample(x, size=(y.H, y.W), mode='bilinear', align_corners=True) on NHWC views (ft_upsample_bilinear_ac_fwd);
+    scale: fp32 [C] on the views' device, or None."""
+    if x.rowpacked or y.rowpacked or x.N != y.N or x.C != y.C or x.t.dtype != y.t.dtype or not (x.t.is_contiguous() and y.t.is_contiguous()):
+        raise FlowtrackHipError("upsample: input and output must be plain contiguous NHWC views of one dtype, batch and channel count")
+    if scale is not None and (tuple(scale.shape) != (x.C,) or scale.dtype != torch.float32 or scale.device != x.t.device or not scale.is_contiguous()):
+        raise FlowtrackHipError(f"upsample: scale must be contiguous fp32 [{x.C}] on the input's device")
+    prog.add("ft_upsample_bilinear_ac_fwd", x.t.data_ptr(), y.t.data_ptr(), _lib.dtype_code(x.t.dtype), x.N, x.C, x.H, x.W, y.H, y.W,
+             x.cstride, x.coff, y.cstride, y.coff, scale.data_ptr() if scale is not None else None, keep=(x.t, y.t, scale))
+
+
 def current_stream_handle(device=None) -> ctypes.c_void_p:
     """Handle of torch's current stream on `device` (default: the current device)."""
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)

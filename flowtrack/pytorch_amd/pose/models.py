@@ -1,9 +1,10 @@
-"""Pose network of FlowTrack on MI355X: ResNet-50/101/152 trunk + 3x ConvTranspose(4,2,1) head +
-1x1 heatmap conv, executed as fused HIP launches (libflowtrack_hip.so).
+"""Pose networks of FlowTrack on MI355X: ResNet-50/101/152 trunk + either the 3x ConvTranspose(4,2,1) head or the FPN
+top-down head, + 1x1 heatmap conv, executed as fused HIP launches (libflowtrack_hip.so).
 
-Drop-in surface (reference: lib/pose/models/pose_deconv.py:12-63,166-179, resnet.py:15-55,
+Drop-in surface (reference: lib/pose/models/pose_deconv.py:12-63,166-179, pose_fpn.py:48-104,171-184, resnet.py:15-55,
 blocks.py:83-120):
     models.deconv(backbone: str, num_classes: int, pretrained: bool) -> module
+    models.fpn(backbone: str, num_classes: int, pretrained: bool) -> module
     module.forward(x[B,3,H,W]) -> heatmaps [B,K,H/4,W/4] (fp32)
     module.state_dict() / load_state_dict() / init_net(path) / .cuda() / .half() / .eval()
 with the reference's parameter names and shapes, so its checkpoints
@@ -26,7 +27,7 @@ import torch.nn as nn
 from ..engine import HipModule
 from ..hip_ops import (ActView, FlowtrackHipError, FusedConv, FusedShortcutConv, Program, bottleneck_exit_fusable, bottleneck_fusable,
                        bottleneck_entry_fusable, bottleneck_head_fusable, bottleneck_cluster_supported, bottleneck_strips_supported, bottleneck_head_stream_fusable, bottleneck_prefers_fused, new_act, new_rowpacked_act, record_bottleneck, record_bottleneck_entry, record_bottleneck_head, record_bottleneck_head_stream,
-                       record_bottleneck_exit, record_maxpool, record_pack_input)
+                       record_bottleneck_exit, record_maxpool, record_pack_input, fold_scale_shift, record_upsample_ac)
 from ..params import ActMarker, BatchNormParams, ConvParams, ConvTransposeParams
 
 # depth -> blocks per stage; only Bottleneck nets are valid because the head hard-codes 2048
@@ -75,7 +76,17 @@ class _Stages(dict):
         raise KeyError(key)
 
 
-class DeconvResnet(HipModule):
+class PoseResnet(HipModule):
+    """What the pose models share: the ResNet trunk and its recording, the plan cache, forward / replay, key points and the flip
+    test inside the plan, the exact-arg-max mode.  A model adds its head through three hooks: _make_head (parameters, under the
+    reference's names), _init_head (the reference's init_net) and _record_head (the launches from the stage maps to the NCHW fp32
+    heat maps)."""
+    #: True: the head reads the full maps of layer1..layer3 as well as layer4's, so every stage seam is recorded as today's
+    #: launches whatever fuse_stage_exit says (the exit form writes only the even pixels of a stage's last block), and
+    #: split_lanes stays off
+    full_stage_maps: bool = False
+    #: the exact-arg-max mode (exact_in_plan, exact_submit*, forward_keypoint_rows_exact): its error bound was measured for this head
+    supports_exact: bool = True
     #: fold each block-0 projection shortcut into its conv3 launch (FusedShortcutConv); FT_FUSE_SHORTCUT=0 keeps them apart
     fuse_shortcut: bool = os.environ.get("FT_FUSE_SHORTCUT", "1") != "0"
     #: identity-shortcut blocks of the 256-wide stage as one launch (ft_bottleneck_fwd); FT_FUSE_BOTTLENECK=0 keeps 3 convs
@@ -128,14 +139,7 @@ class DeconvResnet(HipModule):
         self.layer2 = self._make_layer(128, layers[1], stride=2)
         self.layer3 = self._make_layer(256, layers[2], stride=2)
         self.layer4 = self._make_layer(512, layers[3], stride=2)
-        # head (pose_deconv.py:16-30)
-        self.deconv_bias = False
-        feats = 256
-        self.deconv = nn.Sequential(
-            ConvTransposeParams(2048, feats, bias=False), BatchNormParams(feats), ActMarker("relu"),
-            ConvTransposeParams(feats, feats, bias=False), BatchNormParams(feats), ActMarker("relu"),
-            ConvTransposeParams(feats, feats, bias=False), BatchNormParams(feats), ActMarker("relu"))
-        self.heatmap = ConvParams(feats, num_classes, 1, bias=True)
+        self._make_head(num_classes)
 
     def _make_layer(self, planes: int, blocks: int, stride: int = 1) -> nn.Sequential:
         mods = [Bottleneck(self.inplanes, planes, stride)]
@@ -159,15 +163,20 @@ class DeconvResnet(HipModule):
 
     def init_net(self, pretrained: str = "") -> None:
         self.init_weights(pretrained)
-        for m in self.deconv:
-            if isinstance(m, ConvTransposeParams):
-                nn.init.normal_(m.weight, std=0.001)
-            elif isinstance(m, BatchNormParams):
-                nn.init.constant_(m.weight, 1)
-                nn.init.constant_(m.bias, 0)
-        nn.init.normal_(self.heatmap.weight, std=0.001)
-        nn.init.constant_(self.heatmap.bias, 0)
+        self._init_head()
         self._invalidate()
+
+    # -- the head: what a model adds to the trunk -----------------------------------------------
+    def _make_head(self, num_classes: int) -> None:
+        raise NotImplementedError
+
+    def _init_head(self) -> None:
+        raise NotImplementedError
+
+    def _record_head(self, prog, stages, cur, dtype, device) -> torch.Tensor:
+        """Record the head's launches behind the trunk (`cur` = layer4's map, `stages` the views behind every stage) and return
+        the NCHW fp32 heat maps they write."""
+        raise NotImplementedError
 
     # -- plan construction ----------------------------------------------------------------------
     def _flip_perm(self):
@@ -190,6 +199,16 @@ class DeconvResnet(HipModule):
             seen.update((a, b))
             perm[a], perm[b] = b, a
         return tuple(perm)
+
+    def _check_exact_supported(self, what: str) -> None:
+        if not self.supports_exact:
+            raise FlowtrackHipError(f"{what}: the exact-arg-max mode is not available for {type(self).__name__} (its screen's error bound "
+                                    "was measured for the deconv head only)")
+
+    def _check_exact_allowed(self, what: str) -> None:
+        """Entry check of the exact-arg-max mode: the model has the mode, and no flip test is set."""
+        self._check_exact_supported(what)
+        self._no_flip(what)
 
     def _no_flip(self, what: str) -> None:
         if self.flip_pairs is not None:
@@ -220,7 +239,7 @@ class DeconvResnet(HipModule):
         stem = self.fused("conv1" + ("+maxpool" if pool_in_stem else ""), self.conv1.weight, stride=2, pad=3, bn=self.bn1.as_dict(),
                           act="relu", **mk)
         cur = new_act(B, H // 4, W // 4, 64, dtype, device)
-        split = self.split_lanes if (dtype == torch.float16 and B % 2 == 0 and B >= 32 and pool_in_stem) else 0
+        split = self.split_lanes if (dtype == torch.float16 and B % 2 == 0 and B >= 32 and pool_in_stem and not self.full_stage_maps) else 0
         if split == 2:
             stem.record(prog, a_in.batch_slice(0, B // 2), cur.batch_slice(0, B // 2), pool=True, x_nchw=xs(0, B // 2))     # (the other half: on the second lane)
         elif pool_in_stem:
@@ -304,35 +323,15 @@ class DeconvResnet(HipModule):
                     continue
                 name = f"layer{li}.{bi}"
                 out = new_act(B, cur.H // blk.stride, cur.W // blk.stride, blk.conv1.cout * 4, dtype, device)
-                if bi == len(layer) - 1 and bi > 0 and li < 4 and not split:
+                if bi == len(layer) - 1 and bi > 0 and li < 4 and not split and not self.full_stage_maps:
                     seam = self._record_stage_exit(prog, name, blk, f"layer{li + 1}.0", trunk[li][0], cur, out, dtype, device)
                     if seam is not None:
                         continue
                 self._record_block(prog, name, blk, cur, out, dtype, device)
                 cur = out
 
-        # head: 3 x (ConvTranspose 4/2/1 + bn + relu), then the 1x1 heatmap conv (pose_deconv.py:43-45) — fused behind
-        # the last deconv as its tail in fp16 mode: the [B, 64, 48, 256] map, the largest tensor of the head, never
-        # reaches HBM
         stages["layer4"] = cur
-        fuse_tail = self.fuse_heatmap and dtype == torch.float16 and self.num_classes <= 32 and self.deconv[6].cout in (64, 128, 256)
-        heatmaps = None
-        for i in (0, 3, 6):
-            tail = dict(tail_weight=self.heatmap.weight, tail_bias=self.heatmap.bias) if (i == 6 and fuse_tail) else {}
-            dc = self.fused(f"deconv.{i}" + ("+heatmap" if tail else ""), self.deconv[i].weight, transposed=True, stride=2, pad=1,
-                            bias=self.deconv[i].bias, bn=self.deconv[i + 1].as_dict(), act="relu", **tail, **mk)
-            if tail:
-                heatmaps = torch.empty((B, self.num_classes, cur.H * 2, cur.W * 2), dtype=torch.float32, device=device)
-                dc.record(prog, cur, heatmaps)
-            else:
-                nxt = new_act(B, cur.H * 2, cur.W * 2, dc.cout, dtype, device)
-                dc.record(prog, cur, nxt)
-                cur = nxt
-                stages[f"deconv.{i}"] = cur
-        if heatmaps is None:
-            hm = self.fused("heatmap", self.heatmap.weight, bias=self.heatmap.bias, act=None, **mk)
-            heatmaps = torch.empty((B, self.num_classes, cur.H, cur.W), dtype=torch.float32, device=device)
-            hm.record(prog, cur, heatmaps)
+        heatmaps = self._record_head(prog, stages, cur, dtype, device)
         if perm is not None:
             # last launch: average the two halves (mirror + left/right swap of the second) and, with keypoints_in_plan, the key points
             # of the merged maps — in place of the separate ft_heatmap_keypoint_rows launch
@@ -543,6 +542,8 @@ class DeconvResnet(HipModule):
 
     def _plan_for(self, B: int, H: int, W: int, replica: int = 0, perm=None) -> _PosePlan:
         """plan_for() with the flip test stated by the caller: perm = None is the plain plan of the shape whatever flip_pairs says."""
+        if self.exact_in_plan:
+            self._check_exact_supported("exact_in_plan")
         device, dtype = self._resolve()
         key = (B, H, W, device, dtype, self.keypoints_in_plan) + (("exact", float(self.exact_argmax_rel_bound)) if self.exact_in_plan else ()) + \
             ((replica,) if replica else ()) + ((("flip",) + tuple(perm),) if perm is not None else ())
@@ -674,7 +675,7 @@ class DeconvResnet(HipModule):
         """First half of the exact-arg-max step (see above): everything is queued on the current stream, nothing is waited for."""
         if self.keypoints_in_plan is None:
             raise FlowtrackHipError("set model.keypoints_in_plan = True / False (adjust_coords) before exact_submit()")
-        self._no_flip("exact_submit")
+        self._check_exact_allowed("exact_submit")
         import ctypes
         from .. import _lib
         from ..hip_ops import check, current_stream_handle
@@ -714,7 +715,7 @@ class DeconvResnet(HipModule):
         place): ONE graph replay — network, key-point rows, screen, gather, header copy — and an event.  The plan's buffers are the
         step's state, so a plan must be finished (exact_finish_plan) before it is submitted again: callers that keep several steps
         in flight rotate plan replicas."""
-        self._no_flip("exact_submit_plan")
+        self._check_exact_allowed("exact_submit_plan")
         ex = getattr(plan, "exact", None)
         if ex is None:
             raise FlowtrackHipError("exact_submit_plan: the plan was built without exact_in_plan (fp16, keypoints_in_plan, B <= 1024)")
@@ -811,7 +812,7 @@ class DeconvResnet(HipModule):
         per call sits between 2 and 3."""
         if self.keypoints_in_plan is None:
             raise FlowtrackHipError("set model.keypoints_in_plan = True / False (adjust_coords) before forward_keypoint_rows_exact()")
-        self._no_flip("forward_keypoint_rows_exact")
+        self._check_exact_allowed("forward_keypoint_rows_exact")
         want = self.compute_dtype
         if want not in (None, torch.float16) and next(self.parameters()).dtype != torch.float16:
             raise FlowtrackHipError("forward_keypoint_rows_exact() is the fp16 mode's exact-arg-max path: compute_dtype must be fp16")
@@ -857,6 +858,123 @@ class _ExactHandle:
     __slots__ = ("rows", "slot", "B", "H", "W", "done")
 
 
+class DeconvResnet(PoseResnet):
+    """ResNet trunk + 3 x ConvTranspose(4,2,1) + 1x1 heatmap conv (pose_deconv.py:12-63)."""
+
+    def _make_head(self, num_classes: int) -> None:
+        # head (pose_deconv.py:16-30)
+        self.deconv_bias = False
+        feats = 256
+        self.deconv = nn.Sequential(
+            ConvTransposeParams(2048, feats, bias=False), BatchNormParams(feats), ActMarker("relu"),
+            ConvTransposeParams(feats, feats, bias=False), BatchNormParams(feats), ActMarker("relu"),
+            ConvTransposeParams(feats, feats, bias=False), BatchNormParams(feats), ActMarker("relu"))
+        self.heatmap = ConvParams(feats, num_classes, 1, bias=True)
+
+    def _init_head(self) -> None:
+        for m in self.deconv:
+            if isinstance(m, ConvTransposeParams):
+                nn.init.normal_(m.weight, std=0.001)
+            elif isinstance(m, BatchNormParams):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+        nn.init.normal_(self.heatmap.weight, std=0.001)
+        nn.init.constant_(self.heatmap.bias, 0)
+
+    def _record_head(self, prog, stages, cur, dtype, device) -> torch.Tensor:
+        # head: 3 x (ConvTranspose 4/2/1 + bn + relu), then the 1x1 heatmap conv (pose_deconv.py:43-45) — fused behind
+        # the last deconv as its tail in fp16 mode: the [B, 64, 48, 256] map, the largest tensor of the head, never
+        # reaches HBM
+        B, mk = cur.N, dict(dtype=dtype, device=device)
+        fuse_tail = self.fuse_heatmap and dtype == torch.float16 and self.num_classes <= 32 and self.deconv[6].cout in (64, 128, 256)
+        heatmaps = None
+        for i in (0, 3, 6):
+            tail = dict(tail_weight=self.heatmap.weight, tail_bias=self.heatmap.bias) if (i == 6 and fuse_tail) else {}
+            dc = self.fused(f"deconv.{i}" + ("+heatmap" if tail else ""), self.deconv[i].weight, transposed=True, stride=2, pad=1,
+                            bias=self.deconv[i].bias, bn=self.deconv[i + 1].as_dict(), act="relu", **tail, **mk)
+            if tail:
+                heatmaps = torch.empty((B, self.num_classes, cur.H * 2, cur.W * 2), dtype=torch.float32, device=device)
+                dc.record(prog, cur, heatmaps)
+            else:
+                nxt = new_act(B, cur.H * 2, cur.W * 2, dc.cout, dtype, device)
+                dc.record(prog, cur, nxt)
+                cur = nxt
+                stages[f"deconv.{i}"] = cur
+        if heatmaps is None:
+            hm = self.fused("heatmap", self.heatmap.weight, bias=self.heatmap.bias, act=None, **mk)
+            heatmaps = torch.empty((B, self.num_classes, cur.H, cur.W), dtype=torch.float32, device=device)
+            hm.record(prog, cur, heatmaps)
+        return heatmaps
+
+
+def _bn_relu_conv(cin: int, cout: int, kernel_size: int, padding: int = 0, bias: bool = True) -> nn.Sequential:
+    """_make_conv of pose_fpn.py:41-46: BatchNorm, ReLU, conv — pre-activation order, so index 0 is the BN and 2 the conv."""
+    return nn.Sequential(BatchNormParams(cin), ActMarker("relu"), ConvParams(cin, cout, kernel_size, padding=padding, bias=bias))
+
+
+class FpnResnet(PoseResnet):
+    """ResNet trunk + FPN top-down path + 1x1 heatmap conv (pose_fpn.py:48-104).  With c2..c5 the maps behind layer1..layer4:
+
+        p5 = latlayer1(c5)
+        p4 = toplayer1(up(p5) + latlayer2(c4)),  p3 = toplayer2(up(p4) + latlayer3(c3)),  p2 = toplayer3(up(p3) + latlayer4(c2))
+        heatmaps = heatmap(p2)                      toplayer_j, heatmap = BatchNorm -> ReLU -> conv;  up = bilinear, align_corners=True
+
+    Each top-down step is three launches.  With (s, b) the fold of toplayer_j's BatchNorm,
+    relu(bn(up(p) + lat(c))) = relu(s * lat(c) + b + s * up(p)): ft_upsample_bilinear_ac_fwd writes u = s * up(p), the lateral 1x1 conv
+    takes s, b as its scale / shift and u as its residual input, and toplayer_j's 3x3 conv reads the activated map (its zero padding
+    pads that map, as in the reference).  Nothing else reads the un-normalised sum.  The last 3x3 conv carries heatmap.0's BatchNorm
+    and ReLU in its epilogue, since only the heatmap conv reads p2."""
+    full_stage_maps = True
+    supports_exact = False
+
+    def _make_head(self, num_classes: int) -> None:
+        feats = 256
+        for i, cin in enumerate((2048, 1024, 512, 256), start=1):       # lateral layers (pose_fpn.py:54-58)
+            setattr(self, f"latlayer{i}", ConvParams(cin, feats, 1, bias=False))
+        for j in (1, 2, 3):                                             # top-down layers (pose_fpn.py:60-63)
+            setattr(self, f"toplayer{j}", _bn_relu_conv(feats, feats, 3, padding=1, bias=False))
+        self.heatmap = _bn_relu_conv(feats, num_classes, 1)
+
+    def _init_head(self) -> None:
+        # pose_fpn.py:92-104
+        for name, m in self.named_modules():
+            if "lat" in name or "top" in name:
+                if isinstance(m, ConvParams):
+                    nn.init.normal_(m.weight, std=0.001)
+                elif isinstance(m, BatchNormParams):
+                    nn.init.constant_(m.weight, 1)
+                    nn.init.constant_(m.bias, 0)
+        nn.init.normal_(self.heatmap[2].weight, std=0.001)
+        nn.init.constant_(self.heatmap[2].bias, 0)
+
+    def _record_head(self, prog, stages, cur, dtype, device) -> torch.Tensor:
+        B, mk = cur.N, dict(dtype=dtype, device=device)
+        feats = self.latlayer1.cout
+        p = new_act(B, cur.H, cur.W, feats, dtype, device)
+        self.fused("latlayer1", self.latlayer1.weight, act=None, **mk).record(prog, cur, p)
+        stages["p5"] = p
+        for j, stage in ((1, "layer3"), (2, "layer2"), (3, "layer1")):
+            lat, top, c = getattr(self, f"latlayer{j + 1}"), getattr(self, f"toplayer{j}"), stages[stage]
+            bn = top[0].as_dict()
+            key = (f"toplayer{j}.0.scale", dtype, str(device))
+            scale = self._layers.get(key)
+            if scale is None:
+                scale = self._layers[key] = fold_scale_shift(feats, feats, None, bn, device)[0]
+            u = new_act(B, c.H, c.W, feats, dtype, device)
+            record_upsample_ac(prog, p, u, scale)
+            a = new_act(B, c.H, c.W, feats, dtype, device)
+            self.fused(f"latlayer{j + 1}+toplayer{j}.0", lat.weight, bn=bn, act="relu", **mk).record(prog, c, a, residual=u)
+            last = j == 3
+            conv = self.fused(f"toplayer{j}.2" + ("+heatmap.0" if last else ""), top[2].weight, pad=1,
+                              bn=self.heatmap[0].as_dict() if last else None, act="relu" if last else None, **mk)
+            p = new_act(B, c.H, c.W, feats, dtype, device)
+            conv.record(prog, a, p)
+            stages[f"p{5 - j}"] = p
+        heatmaps = torch.empty((B, self.num_classes, p.H, p.W), dtype=torch.float32, device=device)
+        self.fused("heatmap.2", self.heatmap[2].weight, bias=self.heatmap[2].bias, act=None, **mk).record(prog, p, heatmaps)
+        return heatmaps
+
+
 def deconv(backbone: str, num_classes: int, pretrained: bool) -> DeconvResnet:
     """Factory with the reference's signature (pose_deconv.py:166-179): backbone 'resnet50' |
     'resnet101' | 'resnet152'; pretrained=True loads data/pretrained/<backbone>.pth if present."""
@@ -866,6 +984,18 @@ def deconv(backbone: str, num_classes: int, pretrained: bool) -> DeconvResnet:
     if depth not in resnet_dict:
         raise FlowtrackHipError(f"resnet{depth}: the deconv head needs a Bottleneck trunk (50/101/152)")
     model = DeconvResnet(resnet_dict[depth], num_classes=num_classes)
+    path = os.path.join("data", "pretrained", "{}.pth".format(backbone)) if pretrained else ""
+    model.init_net(path)
+    return model
+
+
+def fpn(backbone: str, num_classes: int, pretrained: bool) -> FpnResnet:
+    """Factory with the reference's signature (pose_fpn.py:171-184) for backbone 'resnet50' | 'resnet101' | 'resnet152';
+    pretrained=True loads data/pretrained/<backbone>.pth if present.  The reference's DenseNet trunks are not on the HIP path."""
+    depth = backbone[len("resnet"):] if backbone.startswith("resnet") else ""
+    if not depth.isdigit() or int(depth) not in resnet_dict:
+        raise FlowtrackHipError(f"backbone '{backbone}': the FPN head is on the HIP path for resnet50 / resnet101 / resnet152 only")
+    model = FpnResnet(resnet_dict[int(depth)], num_classes=num_classes)
     path = os.path.join("data", "pretrained", "{}.pth".format(backbone)) if pretrained else ""
     model.init_net(path)
     return model

@@ -462,6 +462,26 @@ int ft_flow_mean_pack_pair(const float* inputs, float rgb_max, void* y, int lpad
 int ft_upsample_bilinear4x(const float* x, float* y, int N, int C, int h, int w,
                            float mul, ft_stream_t stream);
 
+/* ---- FPN head: F.upsample(x, size=(ho, wo), mode='bilinear', align_corners=True) * scale ----
+ * (lib/pose/models/pose_fpn.py:9-26, the resize inside _upsample_add).  NHWC `dtype` in, NHWC `dtype` out:
+ *   y[n, oy, ox, c] = scale[c] * bilerp_ac(x[n, :, :, c], oy, ox)      c in [0, C); scale fp32 [C], NULL = 1
+ * with torch's coordinate rule for float inputs, restated exactly (all of it in fp32):
+ *   rh  = ho > 1 ? (float)(hi - 1) / (ho - 1) : 0        src = rh * oy
+ *   i0  = (int)src          i1 = i0 + (i0 < hi - 1)      l1 = src - i0      l0 = 1 - l1
+ * the same along x, and with a, b = row i0 at columns j0, j1 and c, d = row i1 at columns j0, j1
+ *   bilerp_ac = l0h * (l0w * a + l1w * b) + l1h * (l0w * c + l1w * d)
+ * Arithmetic is fp32 (a product and the sum behind it may be one fused multiply-add); the result is rounded once, on store.
+ * x_cstride / x_coff and y_cstride / y_coff as in ft_conv_desc: channel c of a pixel sits at element pixel * cstride + coff + c.
+ * Channels [C, y_cstride - y_coff) of an output pixel, and everything in front of y_coff, stay untouched.
+ * One thread per (output pixel, 16-byte channel group: 8 fp16 / 4 fp32 channels), so both offsets and both strides must be
+ * multiples of that group and x, y 16-byte aligned (FT_ERR_INVALID_ARG otherwise, as for sizes <= 0); C itself may be any
+ * positive number (a last partial group goes element by element).  x and y must not overlap.  No cap on N: the grid strides.
+ * FT_ERR_UNSUPPORTED for a side above 2^24, where fp32 source coordinates stop being exact at the far end, and for an output
+ * row of 2^31 or more channel groups (wo x ceil(C / group)). */
+int ft_upsample_bilinear_ac_fwd(const void* x, void* y, int dtype, int N, int C, int hi, int wi, int ho, int wo,
+                                int x_cstride, int x_coff, int y_cstride, int y_coff, const float* scale,
+                                ft_stream_t stream);
+
 /* ---- F4: Correlation forward ---------------------------------------------
  * Replaces Correlation_forward_cuda (correlation_package/src/correlation_cuda.c:11-93,
  * kernels correlation_cuda_kernel.cu:10-106).  Same parameters and output

@@ -1,4 +1,5 @@
-"""Per-launch timing of a whole plan (dev tool): python tools/dev/net_bench.py FlowNet2C 16 384 512 fp16"""
+"""Per-launch timing of a whole plan (dev tool): python tools/dev/net_bench.py FlowNet2C 16 384 512 fp16
+(pose nets: resnet50 = ResNet-50 + deconv head, fpn_resnet50 = ResNet-50 + FPN head)"""
 import sys, os, types
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -6,9 +7,10 @@ import torch
 from flowtrack.pytorch_amd import synth
 name, B, H, W, dt = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), sys.argv[5]
 dtype = torch.float16 if dt == "fp16" else torch.float32
-if name.startswith("resnet"):
+if name.startswith("resnet") or name.startswith("fpn_resnet"):      # resnet50 = the deconv head, fpn_resnet50 = the FPN head
     from flowtrack.pytorch_amd.pose import models
-    m = models.deconv(name, 17, False); m.load_state_dict(synth.fill_pose_state_dict(m.state_dict(), 1))
+    m = models.fpn(name[4:], 17, False) if name.startswith("fpn_") else models.deconv(name, 17, False)
+    m.load_state_dict(synth.fill_pose_state_dict(m.state_dict(), 1))
     x = synth.pose_crops(1, B, H, W)
 else:
     from flowtrack.pytorch_amd.flownet import models

@@ -144,8 +144,9 @@ def main(**kwargs):
     opt.work_dir = os.path.join(opt.checkpoint_path, opt.dataset, opt.exp_id)
     num_classes = num_joints[opt.dataset] + (1 if opt.with_bg else 0)
     print("==> creating model '{}', backbone = {}".format(opt.model, opt.backbone))
-    if opt.model != 'deconv':
-        raise ValueError("only model='deconv' (ResNet + 3-deconv head) is on the HIP path; got '{}'".format(opt.model))
+    if opt.model not in ('deconv', 'fpn'):
+        raise ValueError("only model='deconv' (ResNet + 3-deconv head) and model='fpn' (ResNet + FPN head) are on the HIP path; "
+                         "got '{}'".format(opt.model))
     model = getattr(models, opt.model)(opt.backbone, num_classes=num_classes, pretrained=opt.pretrained)
     opt.model_name = '{}_{}'.format(opt.model, opt.backbone)
     if not opt.use_gpu:

@@ -67,7 +67,7 @@ def synthetic_clip(n_frames, H=384, W=512, n_people=5, seed=0):
 
 
 def build_nets(args, device):
-    pose = pose_models.deconv("resnet%d" % args.pose_backbone, num_classes=getattr(args, "pose_classes", 17), pretrained=False)
+    pose = getattr(pose_models, getattr(args, "pose_head", "deconv"))("resnet%d" % args.pose_backbone, num_classes=getattr(args, "pose_classes", 17), pretrained=False)
     if args.pose_model:
         pose.load_state_dict(torch.load(args.pose_model, map_location="cpu")["state_dict"])
     else:
@@ -410,6 +410,8 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=60)
     ap.add_argument("--people", type=int, default=5)
     ap.add_argument("--pose_backbone", default=50, type=int, help="50, 101, 152")
+    ap.add_argument("--pose_head", default="deconv", choices=("deconv", "fpn"),
+                    help="pose model factory (the reference's opt.model): ResNet + 3-deconv head, or ResNet + FPN head")
     ap.add_argument("--pose_model", type=str, default="", help="pose checkpoint (ckpt['state_dict'])")
     ap.add_argument("--flow_net", type=str, default="FlowNet2S", help="FlowNet2S, FlowNet2C, FlowNet2CS")
     ap.add_argument("--flow_model", type=str, default="", help="optical flow checkpoint (ckpt['state_dict'])")
