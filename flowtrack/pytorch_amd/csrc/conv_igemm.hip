@@ -326,7 +326,8 @@ void conv_igemm_dma_kernel(const ConvParams p) {
     b_mask[t] = mask;
   }
 
-  // second input (K-concat): one more K-run per pixel row, read from another tensor at (n, qy * s2, qx * s2)
+  // second input (K-concat): one more K-run per pixel row, read from another tensor at the row's OUTPUT pixel times s2:
+  // (n, qy * s2, qx * s2), and behind a transposed conv (s2 = 1) pixel (2 qy + py, 2 qx + px) of this workgroup's phase
   const bool dual = p.kc2 > 0;
   const __amdgpu_buffer_rsrc_t rsrc_b2 =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(dual ? p.x2 : p.x), 0, dual ? p.x2_bytes : p.x_bytes, 0x00020000);
@@ -343,7 +344,8 @@ void conv_igemm_dma_kernel(const ConvParams p) {
         const int rem = m - n * p.HqWq;
         const int qy = rem / p.Wq;
         const int qx = rem - qy * p.Wq;
-        v = (unsigned)((((n * p.x2_hi + qy * p.x2_stride) * p.x2_wi + qx * p.x2_stride) * p.x2_cstride + p.x2_coff) * esz + lc * 16);
+        const int oy = qy * p.omul + py, ox = qx * p.omul + px;      // (omul = 1, py = px = 0 unless transposed)
+        v = (unsigned)((((n * p.x2_hi + oy * p.x2_stride) * p.x2_wi + ox * p.x2_stride) * p.x2_cstride + p.x2_coff) * esz + lc * 16);
       }
     }
     b2_voff[t] = v;
@@ -2241,12 +2243,14 @@ static int validate(const ft_conv_desc* d) {
   }
   if (d->pool != 0 && d->pool != 1) return FT_ERR_INVALID_ARG;
   if (d->x2_cin < 0) return FT_ERR_INVALID_ARG;
-  if (d->x2_cin > 0) {   // second input (K-concat): 1x1 / stride 1 main conv, no residual, plain NHWC views
-    if (d->transposed || d->kh != 1 || d->kw != 1 || d->stride != 1 || d->pad != 0 || d->has_residual || d->x_wpitch > 0)
-      return FT_ERR_UNSUPPORTED;
+  if (d->x2_cin > 0) {   // second input (K-concat): 1x1 / stride 1 or transposed 4x4 / stride 2 main conv, no residual, plain NHWC views
+    if (!d->transposed && (d->kh != 1 || d->kw != 1 || d->stride != 1 || d->pad != 0)) return FT_ERR_UNSUPPORTED;
+    if (d->has_residual || d->x_wpitch > 0) return FT_ERR_UNSUPPORTED;
     if (d->x2_stride <= 0 || d->x2_hi <= 0 || d->x2_wi <= 0 || d->x2_cstride % 8 || d->x2_coff % 8 || d->x2_coff < 0)
       return FT_ERR_INVALID_ARG;
     if (d->x2_cstride < d->x2_coff + round_up(d->x2_cin, 8)) return FT_ERR_INVALID_ARG;
+    // behind a transposed conv x2 is given at the output geometry: every phase reads it at its own output pixels
+    if (d->transposed && (d->x2_stride != 1 || d->x2_hi != d->Ho || d->x2_wi != d->Wo)) return FT_ERR_INVALID_ARG;
     if (d->Ho != (d->x2_hi - 1) / d->x2_stride + 1 || d->Wo != (d->x2_wi - 1) / d->x2_stride + 1) return FT_ERR_INVALID_ARG;
   }
   return FT_OK;

@@ -997,6 +997,91 @@ class FusedShortcutConv:
             prog.end_choice()
 
 
+class FusedLateralDeconv:
+    """One top-down step of the lateral-deconv pose head (lib/pose/models/pose_net.py:63-65) and the BatchNorm + ReLU that read
+    its sum, as ONE launch:  out = act(bn(ConvTranspose2d(4,2,1)(x) + lateral_1x1(c))).
+    Per output-parity phase the transposed conv is a GEMM over its four taps; the lateral conv of the same output pixel is one more
+    K-run of that GEMM (`ft_conv_desc.x2_*` behind transposed = 1), so the sum never exists in HBM.  The BatchNorm FOLLOWS the sum
+    and stays in the epilogue's scale / shift, not in the weights: their fp16 rounding is that of a plain deconv."""
+
+    def __init__(self, wt: torch.Tensor, w2: torch.Tensor, bn: Optional[dict], *, dtype: torch.dtype, device: torch.device,
+                 act: Optional[str] = "relu", label: str = ""):
+        require_gpu(device)
+        self.lib = _lib.load()
+        self.dtype, self.device, self.code = dtype, device, _lib.dtype_code(dtype)
+        self.cin, self.cout = wt.shape[0], wt.shape[1]
+        self.cin2 = w2.shape[1]
+        if tuple(wt.shape[2:]) != (4, 4) or w2.shape[0] != self.cout or tuple(w2.shape[2:]) != (1, 1):
+            raise FlowtrackHipError(f"{label}: needs a ConvTranspose2d(4,2,1) weight [Cin, Cout, 4, 4] and a 1x1 lateral conv to Cout channels")
+        self.act, self.label = ACT_CODES[act], label
+        self._wt = wt.detach().to(torch.float32).cpu()
+        self._w2 = w2.detach().to(torch.float32).cpu()[:, :, 0, 0]
+        self._bn = None if bn is None else {k: (v.detach().to(torch.float32).cpu() if torch.is_tensor(v) else v) for k, v in bn.items()}
+        self._packed = {}
+
+    def _packed_for(self, d: ConvDesc):
+        """[taps | W2] per phase: the taps from ft_conv_tap_source (pack_conv_weights: the x2 fields only widen kpad), the same W2
+        block behind them in every phase."""
+        g = conv_geometry(d)
+        key = g.key()
+        hit = self._packed.get(key)
+        if hit is None:
+            w, cout_pad = pack_conv_weights(self._wt, d, dtype=torch.float32, device=torch.device("cpu"))
+            k2 = g.ntaps * g.cin_pad
+            if tuple(w.shape) != (4, g.cout_pad, g.kpad) or g.kpad != k2 + g.cin2_pad or g.cin2_pad < self.cin2:
+                raise FlowtrackHipError(f"{self.label}: unexpected packed geometry {tuple(w.shape)} / cin2_pad {g.cin2_pad}")
+            w[:, :self.cout, k2:k2 + self.cin2] = self._w2
+            scale, shift = fold_scale_shift(self.cout, cout_pad, None, self._bn, self.device)
+            hit = self._packed[key] = (w.to(device=self.device, dtype=self.dtype).contiguous(), scale, shift)
+        return hit
+
+    def supported(self, x: ActView, c: ActView, y: ActView) -> bool:
+        """True where the library takes the step as one launch (the channel-aligned kernel for both inputs)."""
+        g = ConvGeometry()
+        return self.lib.ft_conv_pack_geometry(ctypes.byref(self._desc(x, c, y)), ctypes.byref(g)) == 0
+
+    def _desc(self, x: ActView, c: ActView, y: ActView) -> ConvDesc:
+        if x.C != self.cin or c.C != self.cin2 or y.C != self.cout:
+            raise FlowtrackHipError(f"{self.label}: channel mismatch")
+        if (c.N, c.H, c.W) != (x.N, 2 * x.H, 2 * x.W) or (y.N, y.H, y.W) != (c.N, c.H, c.W):
+            raise FlowtrackHipError(f"{self.label}: the lateral map and the output must have twice the deconv input's height and width")
+        if any(v.t.dtype != self.dtype or not v.t.is_contiguous() or v.rowpacked for v in (x, c, y)):
+            raise FlowtrackHipError(f"{self.label}: views must be plain contiguous {self.dtype} NHWC buffers")
+        d = ConvDesc()
+        d.dtype = self.code
+        d.N, d.Hi, d.Wi = x.N, x.H, x.W
+        d.Cin, d.x_cstride, d.x_coff = self.cin, x.cstride, x.coff
+        d.Cout, d.kh, d.kw, d.stride, d.pad, d.transposed = self.cout, 4, 4, 2, 1, 1
+        d.Ho, d.Wo = y.H, y.W
+        d.y_cstride, d.y_coff, d.out_layout = y.cstride, y.coff, FT_LAYOUT_NHWC
+        d.act, d.slope = self.act, 0.0
+        d.x2_cin, d.x2_hi, d.x2_wi, d.x2_cstride, d.x2_coff, d.x2_stride = self.cin2, c.H, c.W, c.cstride, c.coff, 1
+        return d
+
+    def record(self, prog: "Program", x: ActView, c: ActView, y: ActView) -> None:
+        d = self._desc(x, c, y)
+        w, scale, shift = self._packed_for(d)
+        flops = float(self.lib.ft_conv_flops(ctypes.byref(d)))
+        prog.flops += flops
+        prog.conv_records.append((self.label, len(prog.calls), flops, d))
+        prog.add("ft_conv2d_fwd", ctypes.byref(d), x.t.data_ptr(), w.data_ptr(), scale.data_ptr() if scale is not None else None,
+                 shift.data_ptr() if shift is not None else None, c.t.data_ptr(), y.t.data_ptr(), keep=(d, x.t, c.t, y.t, w, scale, shift))
+
+
+def record_scale_shift_act(prog: Program, x: ActView, y: ActView, scale: torch.Tensor, shift: torch.Tensor, act: Optional[str] = "relu",
+                           slope: float = 0.0) -> None:
+    """y = act(scale[c] * x + shift[c]) on NHWC views of one size (ft_scale_shift_act_nhwc_fwd); scale, shift fp32 [>= C] on the device."""
+    if (x.N, x.H, x.W, x.C) != (y.N, y.H, y.W, y.C) or x.t.dtype != y.t.dtype or x.rowpacked or y.rowpacked or \
+            not x.t.is_contiguous() or not y.t.is_contiguous():
+        raise FlowtrackHipError(f"scale_shift_act: views do not line up ({tuple(x.t.shape)} C={x.C} -> {tuple(y.t.shape)} C={y.C})")
+    for v in (scale, shift):
+        if v.dtype != torch.float32 or v.numel() < x.C or not v.is_contiguous() or v.device != x.t.device:
+            raise FlowtrackHipError("scale_shift_act: scale and shift must be contiguous fp32 [C] on the views' device")
+    prog.add("ft_scale_shift_act_nhwc_fwd", x.t.data_ptr(), y.t.data_ptr(), _lib.dtype_code(x.t.dtype), ctypes.c_longlong(x.N * x.H * x.W), x.C,
+             x.cstride, x.coff, y.cstride, y.coff, scale.data_ptr(), shift.data_ptr(), ACT_CODES[act], ctypes.c_float(slope),
+             keep=(x.t, y.t, scale, shift))
+
+
 def bottleneck_fusable(c1: "FusedConv", c2: "FusedConv", c3: "FusedConv", x: ActView, y: ActView) -> bool:
     """True when ft_bottleneck_fwd covers this identity-shortcut block (fp16, 256 -> 64 -> 64 -> 256, stride 1)."""
     if x.t.dtype != torch.float16 or x.rowpacked or (x.N, x.H, x.W, x.C) != (y.N, y.H, y.W, y.C):

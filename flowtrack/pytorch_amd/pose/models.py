@@ -1,10 +1,11 @@
-"""Pose networks of FlowTrack on MI355X: ResNet-50/101/152 trunk + either the 3x ConvTranspose(4,2,1) head or the FPN
-top-down head, + 1x1 heatmap conv, executed as fused HIP launches (libflowtrack_hip.so).
+"""Pose networks of FlowTrack on MI355X: ResNet-50/101/152 trunk + the 3x ConvTranspose(4,2,1) head, the FPN top-down head or the
+lateral-deconv head, + 1x1 heatmap conv, executed as fused HIP launches (libflowtrack_hip.so).
 
-Drop-in surface (reference: lib/pose/models/pose_deconv.py:12-63,166-179, pose_fpn.py:48-104,171-184, resnet.py:15-55,
-blocks.py:83-120):
+Drop-in surface (reference: lib/pose/models/pose_deconv.py:12-63,166-179, pose_fpn.py:48-104,171-184, pose_net.py:30-91,163-177,
+resnet.py:15-55, blocks.py:83-120):
     models.deconv(backbone: str, num_classes: int, pretrained: bool) -> module
     models.fpn(backbone: str, num_classes: int, pretrained: bool) -> module
+    models.pose(backbone: str, num_classes: int, pretrained: bool) -> module
     module.forward(x[B,3,H,W]) -> heatmaps [B,K,H/4,W/4] (fp32)
     module.state_dict() / load_state_dict() / init_net(path) / .cuda() / .half() / .eval()
 with the reference's parameter names and shapes, so its checkpoints
@@ -25,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from ..engine import HipModule
-from ..hip_ops import (ActView, FlowtrackHipError, FusedConv, FusedShortcutConv, Program, bottleneck_exit_fusable, bottleneck_fusable,
+from ..hip_ops import (ActView, FlowtrackHipError, FusedConv, FusedLateralDeconv, FusedShortcutConv, Program, record_scale_shift_act, bottleneck_exit_fusable, bottleneck_fusable,
                        bottleneck_entry_fusable, bottleneck_head_fusable, bottleneck_cluster_supported, bottleneck_strips_supported, bottleneck_head_stream_fusable, bottleneck_prefers_fused, new_act, new_rowpacked_act, record_bottleneck, record_bottleneck_entry, record_bottleneck_head, record_bottleneck_head_stream,
                        record_bottleneck_exit, record_maxpool, record_pack_input, fold_scale_shift, record_upsample_ac)
 from ..params import ActMarker, BatchNormParams, ConvParams, ConvTransposeParams
@@ -975,6 +976,116 @@ class FpnResnet(PoseResnet):
         return heatmaps
 
 
+def _bn_relu_deconv(cin: int, cout: int) -> nn.Sequential:
+    """_make_deconv of pose_net.py:9-14: BatchNorm (over the INPUT channels), ReLU, ConvTranspose2d(4,2,1) without bias."""
+    return nn.Sequential(BatchNormParams(cin), ActMarker("relu"), ConvTransposeParams(cin, cout, bias=False))
+
+
+class LateralDeconvResnet(PoseResnet):
+    """ResNet trunk + three `BatchNorm -> ReLU -> ConvTranspose2d(4,2,1)` steps, each summed with a 1x1 lateral conv of the trunk
+    map at its output's scale, + `BatchNorm -> ReLU -> 1x1` heat maps (pose_net.py:30-91).  With c2..c5 the maps behind layer1..layer4:
+
+        p4 = deconv1(c5) + latlayer2(c4),  p3 = deconv2(p4) + latlayer3(c3),  p2 = deconv3(p3) + latlayer4(c2),  heatmaps = heatmap(p2)
+
+    Nothing reads a sum p_j but the BatchNorm + ReLU in front of the next layer, so with (s, b) the fold of that BatchNorm
+    (deconv2.0, deconv3.0, heatmap.0) the plan holds only the activated maps:
+
+        a5 = relu(bn_deconv1.0(c5))                       ft_scale_shift_act_nhwc_fwd (c5 is layer4's activated output: no epilogue to fold into)
+        a4 = relu(s (deconv1(a5) + lat2(c4)) + b)         one step, likewise a3 and a2
+        heatmaps = heatmap.2(a2) + bias                   1x1 conv to NCHW fp32
+
+    A step is recorded in two forms, the first-call benchmark keeps one (`lateral_step_form` forces one):
+      "kconcat"         ONE launch: the lateral conv as one more K-run of each parity phase of the transposed conv (FusedLateralDeconv);
+      "lateral+deconv"  two launches: the lateral conv writes l = s lat(c) + b, the transposed conv takes scale s, no shift, l as its
+                        residual input and the ReLU — on whatever kernel today's dispatch gives a transposed conv with a residual.
+    The heat-map conv stays a launch of its own: the fused tail, x2 and a residual all use the same pointer argument."""
+    full_stage_maps = True
+    supports_exact = False
+    #: None: both forms of a top-down step are recorded and the first-call benchmark keeps one; "kconcat" / "lateral+deconv" records
+    #: that form only (dev, tests; FT_LATERAL_STEP in the environment)
+    lateral_step_form = os.environ.get("FT_LATERAL_STEP") or None
+    STEP_FORMS = ("kconcat", "lateral+deconv")
+
+    def _make_head(self, num_classes: int) -> None:
+        feats = 256
+        for i, cin in ((2, 1024), (3, 512), (4, 256)):                   # lateral layers (pose_net.py:36-40): there is no latlayer1
+            setattr(self, f"latlayer{i}", ConvParams(cin, feats, 1, bias=False))
+        for j, cin in ((1, 2048), (2, feats), (3, feats)):               # top-down layers (pose_net.py:42-45)
+            setattr(self, f"deconv{j}", _bn_relu_deconv(cin, feats))
+        self.heatmap = _bn_relu_conv(feats, num_classes, 1)
+
+    def _init_head(self) -> None:
+        # pose_net.py:69-91
+        for name, m in self.named_modules():
+            if "lat" in name:
+                if isinstance(m, ConvParams):
+                    nn.init.normal_(m.weight, std=0.001)
+            elif "deconv" in name:
+                if isinstance(m, ConvTransposeParams):
+                    nn.init.normal_(m.weight, std=0.001)
+                elif isinstance(m, BatchNormParams):
+                    nn.init.constant_(m.weight, 1)
+                    nn.init.constant_(m.bias, 0)
+        nn.init.constant_(self.heatmap[0].weight, 1)
+        nn.init.constant_(self.heatmap[0].bias, 0)
+        nn.init.normal_(self.heatmap[2].weight, std=0.001)
+        nn.init.constant_(self.heatmap[2].bias, 0)
+
+    def _record_head(self, prog, stages, cur, dtype, device) -> torch.Tensor:
+        form = self.lateral_step_form
+        if form is not None and form not in self.STEP_FORMS:
+            raise FlowtrackHipError(f"lateral_step_form {form!r}: None or one of {self.STEP_FORMS}")
+        B, mk = cur.N, dict(dtype=dtype, device=device)
+        feats = self.latlayer2.cout
+        key = ("deconv1.0.scale_shift", dtype, str(device))
+        ss = self._layers.get(key)
+        if ss is None:
+            ss = self._layers[key] = fold_scale_shift(cur.C, cur.C, None, self.deconv1[0].as_dict(), device)
+        a = new_act(B, cur.H, cur.W, cur.C, dtype, device)
+        record_scale_shift_act(prog, cur, a, ss[0], ss[1], "relu")
+        stages["a5"] = a
+        steps = ((1, 2, "layer3", self.deconv2[0]), (2, 3, "layer2", self.deconv3[0]), (3, 4, "layer1", self.heatmap[0]))
+        for j, i, stage, bn_mod in steps:
+            dc, lat, c = getattr(self, f"deconv{j}")[2], getattr(self, f"latlayer{i}"), stages[stage]
+            bn = bn_mod.as_dict()
+            name = f"deconv{j}.2+latlayer{i}"
+            out = new_act(B, c.H, c.W, feats, dtype, device)
+            key = (name, dtype, str(device))
+            kc = self._layers.get(key)
+            if kc is None:
+                kc = self._layers[key] = FusedLateralDeconv(dc.weight, lat.weight, bn, act="relu", label=name, **mk)
+            # the two-launch form's layers: l = s lat(c) + b (no activation), then relu(s deconv(a) + l)
+            lat_conv = self.fused(f"latlayer{i}.bn", lat.weight, bn=bn, act=None, **mk)
+            key = (f"deconv{j}.2.scaled", dtype, str(device))
+            dc_conv = self._layers.get(key)
+            if dc_conv is None:
+                no_shift = dict(bn, bias=torch.zeros_like(bn["bias"]), running_mean=torch.zeros_like(bn["running_mean"]))
+                dc_conv = self._layers[key] = FusedConv(dc.weight, transposed=True, stride=2, pad=1, bn=no_shift, act="relu",
+                                                        label=f"deconv{j}.2+residual", **mk)
+            lbuf = new_act(B, c.H, c.W, feats, dtype, device)
+
+            def kconcat_form(kc=kc, a=a, c=c, out=out):
+                kc.record(prog, a, c, out)
+
+            def two_form(lat_conv=lat_conv, dc_conv=dc_conv, a=a, c=c, out=out, lbuf=lbuf):
+                lat_conv.record(prog, c, lbuf)
+                dc_conv.record(prog, a, out, residual=lbuf)
+            forms = {"kconcat": kconcat_form, "lateral+deconv": two_form}
+            if form is not None:
+                forms[form]()
+            else:
+                prog.begin_choice(f"lateral_step|{B},{a.H},{a.W},{a.C},{c.C},{feats},{a.cstride},{c.cstride},{dtype}")
+                for fname in self.STEP_FORMS:
+                    prog.option(fname)
+                    forms[fname]()
+                prog.end_choice()
+            a = out
+            stages[f"a{5 - j}"] = a
+        heatmaps = torch.empty((B, self.num_classes, a.H, a.W), dtype=torch.float32, device=device)
+        self.fused("heatmap.2", self.heatmap[2].weight, bias=self.heatmap[2].bias, act=None, **mk).record(prog, a, heatmaps)
+        return heatmaps
+
+
 def deconv(backbone: str, num_classes: int, pretrained: bool) -> DeconvResnet:
     """Factory with the reference's signature (pose_deconv.py:166-179): backbone 'resnet50' |
     'resnet101' | 'resnet152'; pretrained=True loads data/pretrained/<backbone>.pth if present."""
@@ -996,6 +1107,22 @@ def fpn(backbone: str, num_classes: int, pretrained: bool) -> FpnResnet:
     if not depth.isdigit() or int(depth) not in resnet_dict:
         raise FlowtrackHipError(f"backbone '{backbone}': the FPN head is on the HIP path for resnet50 / resnet101 / resnet152 only")
     model = FpnResnet(resnet_dict[int(depth)], num_classes=num_classes)
+    path = os.path.join("data", "pretrained", "{}.pth".format(backbone)) if pretrained else ""
+    model.init_net(path)
+    return model
+
+
+def pose(backbone: str, num_classes: int, pretrained: bool) -> LateralDeconvResnet:
+    """Factory with the reference's signature (pose_net.py:163-177) for backbone 'resnet50' | 'resnet101' | 'resnet152';
+    pretrained=True loads data/pretrained/<backbone>.pth if present.  The reference's own DenseNet form of this model cannot be
+    built (pose_net.py:101 names an undefined `bias`), so there is nothing to follow for it."""
+    if backbone.startswith("densenet"):
+        raise FlowtrackHipError(f"backbone '{backbone}': the reference itself cannot build this model (PoseDensenet raises NameError: "
+                                "name 'bias' is not defined); the lateral-deconv head is on the HIP path for resnet50 / resnet101 / resnet152 only")
+    depth = backbone[len("resnet"):] if backbone.startswith("resnet") else ""
+    if not depth.isdigit() or int(depth) not in resnet_dict:
+        raise FlowtrackHipError(f"backbone '{backbone}': the lateral-deconv head is on the HIP path for resnet50 / resnet101 / resnet152 only")
+    model = LateralDeconvResnet(resnet_dict[int(depth)], num_classes=num_classes)
     path = os.path.join("data", "pretrained", "{}.pth".format(backbone)) if pretrained else ""
     model.init_net(path)
     return model

@@ -134,6 +134,18 @@ typedef struct ft_conv_desc {
    * 104-119) into its conv3: the caller folds both BatchNorms into the weights (scale = NULL) and sums the shifts.
    * Requirements: 1x1 / stride 1 / pad 0 main conv, has_residual = 0 — x2 is passed in ft_conv2d_fwd's `residual`
    * argument — x2 is NHWC `dtype` [N, x2_hi, x2_wi, x2_cstride] with Ho = (x2_hi - 1) / x2_stride + 1 (same for Wo).
+   * Behind a TRANSPOSED main conv (transposed = 1, the 4x4 / stride 2 / pad 1 form) the same field gives one top-down step of
+   * the lateral-deconv pose head (lib/pose/models/pose_net.py:63-65) in one launch:
+   *   y[n, oy, ox, :] = act(scale .* (ConvT(x)[n, oy, ox, :] + W2 . x2[n, oy, ox, :]) + shift)
+   * x2 is given at the OUTPUT geometry: x2_hi = Ho, x2_wi = Wo, x2_stride = 1 (anything else: FT_ERR_INVALID_ARG).  Each of the four
+   * output-parity phases is one GEMM over K = [4 taps of x | x2], kpad = 4 * cin_pad + cin2_pad per phase, and every phase's
+   * packed matrix carries the same W2 block behind its four taps; phase (py, px) reads x2 at its own pixels (2 qy + py, 2 qx + px).
+   * Here scale / shift are usually a BatchNorm that FOLLOWS the sum, so the caller keeps them out of the weights.
+   * has_residual and tail_cout stay excluded (FT_ERR_UNSUPPORTED): all three use the `residual` argument.
+   * Both forms run on the channel-aligned kernel only: x_cstride >= x_coff + Cin padded to a K-step (32 fp16 / 16 fp32 channels) of
+   * at least two steps, the same for x2, Cout > 32 — FT_ERR_UNSUPPORTED otherwise.  No split-K tile is offered with a second input
+   * (ft_conv_tile_candidates lists none, ft_conv_workspace_bytes is 0); a hint for a form that does not take x2 (the 8-phase
+   * kernel, the LDS-patch forms, split-K) falls back to the heuristic tile.
    * x2_cin = 0: no second input. */
   int x2_cin, x2_hi, x2_wi, x2_cstride, x2_coff, x2_stride;
   /* Optional fused TAIL 1x1 conv: y = Wt . act(scale .* conv(x) + shift) + bt with tail_cout <= 32 outputs.  The
@@ -480,6 +492,24 @@ int ft_upsample_bilinear4x(const float* x, float* y, int N, int C, int h, int w,
  * row of 2^31 or more channel groups (wo x ceil(C / group)). */
 int ft_upsample_bilinear_ac_fwd(const void* x, void* y, int dtype, int N, int C, int hi, int wi, int ho, int wo,
                                 int x_cstride, int x_coff, int y_cstride, int y_coff, const float* scale,
+                                ft_stream_t stream);
+
+/* Per-channel affine + activation on an NHWC view: the pre-activation `BatchNorm -> ReLU` in front of the first deconv of the
+ * lateral-deconv pose head (lib/pose/models/pose_net.py:9-14), which reads layer4's already activated output and so folds into
+ * no conv epilogue.  `dtype` in, `dtype` out, npix = N * H * W pixels:
+ *   y[pix, c] = act(scale[c] * x[pix, c] + shift[c])      c in [0, C); scale, shift fp32 [C]
+ * The arithmetic is the conv epilogue's: scale * x + shift in fp32 as ONE fused multiply-add (a single rounding), then the
+ * activation (FT_ACT_*, `slope` for FT_ACT_LEAKY) with the epilogue's values for non-finite inputs (NaN stays NaN, ReLU(-inf) = 0),
+ * then one rounding to the output type on store.
+ * x_cstride / x_coff and y_cstride / y_coff as in ft_conv_desc: channel c of a pixel sits at element pixel * cstride + coff + c.
+ * Channels outside [coff, coff + C) of an output pixel stay untouched.  y may be the same view as x (in place); any other overlap
+ * is undefined.  Accesses are 16 bytes wide (8 fp16 / 4 fp32 channels per thread) where C, both offsets and both strides are
+ * multiples of that group and x, y, scale, shift are 16-byte aligned; any other view goes element by element.  The grid is capped
+ * and strides over the rest.
+ * FT_ERR_INVALID_ARG: a NULL pointer, npix or C <= 0, a stride smaller than offset + C, a negative offset, an unknown dtype or
+ * activation, a pointer that is not aligned to its element type.  FT_ERR_UNSUPPORTED: 2^31 or more (pixel, group) items. */
+int ft_scale_shift_act_nhwc_fwd(const void* x, void* y, int dtype, long long npix, int C, int x_cstride, int x_coff,
+                                int y_cstride, int y_coff, const float* scale, const float* shift, int act, float slope,
                                 ft_stream_t stream);
 
 /* ---- F4: Correlation forward ---------------------------------------------

@@ -1,5 +1,5 @@
 """Per-launch timing of a whole plan (dev tool): python tools/dev/net_bench.py FlowNet2C 16 384 512 fp16
-(pose nets: resnet50 = ResNet-50 + deconv head, fpn_resnet50 = ResNet-50 + FPN head)"""
+(pose nets: resnet50 = ResNet-50 + deconv head, fpn_resnet50 = ResNet-50 + FPN head, pose_resnet50 = ResNet-50 + lateral-deconv head)"""
 import sys, os, types
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -7,9 +7,9 @@ import torch
 from flowtrack.pytorch_amd import synth
 name, B, H, W, dt = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), sys.argv[5]
 dtype = torch.float16 if dt == "fp16" else torch.float32
-if name.startswith("resnet") or name.startswith("fpn_resnet"):      # resnet50 = the deconv head, fpn_resnet50 = the FPN head
+if name.startswith(("resnet", "fpn_resnet", "pose_resnet")):      # resnet50 = the deconv head, fpn_resnet50 = the FPN head, pose_resnet50 = the lateral-deconv head
     from flowtrack.pytorch_amd.pose import models
-    m = models.fpn(name[4:], 17, False) if name.startswith("fpn_") else models.deconv(name, 17, False)
+    m = models.fpn(name[4:], 17, False) if name.startswith("fpn_") else models.pose(name[5:], 17, False) if name.startswith("pose_") else models.deconv(name, 17, False)
     m.load_state_dict(synth.fill_pose_state_dict(m.state_dict(), 1))
     x = synth.pose_crops(1, B, H, W)
 else:

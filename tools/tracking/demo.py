@@ -410,8 +410,9 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=60)
     ap.add_argument("--people", type=int, default=5)
     ap.add_argument("--pose_backbone", default=50, type=int, help="50, 101, 152")
-    ap.add_argument("--pose_head", default="deconv", choices=("deconv", "fpn"),
-                    help="pose model factory (the reference's opt.model): ResNet + 3-deconv head, or ResNet + FPN head")
+    ap.add_argument("--pose_head", default="deconv", choices=("deconv", "fpn", "pose"),
+                    help="pose model factory (the reference's opt.model): ResNet + 3-deconv head, ResNet + FPN head, or ResNet + "
+                         "lateral-deconv head")
     ap.add_argument("--pose_model", type=str, default="", help="pose checkpoint (ckpt['state_dict'])")
     ap.add_argument("--flow_net", type=str, default="FlowNet2S", help="FlowNet2S, FlowNet2C, FlowNet2CS")
     ap.add_argument("--flow_model", type=str, default="", help="optical flow checkpoint (ckpt['state_dict'])")
