@@ -2,34 +2,9 @@
 // arbitrary output size, times an optional per-channel scale (the BatchNorm scale of the toplayer that follows the
 // upsample-and-add, so that the add itself rides in the lateral conv's residual input).  A pure gather, bound by HBM: one thread
 // per (output pixel, 16-byte channel group), four 16-byte loads and one 16-byte store, fp32 arithmetic, one rounding on store.
-#include "ft_common.h"
+#include "bilerp_ac.h"      // Group<T>, ac_source: shared with hourglass_ops.hip
 
 namespace ft {
-
-// G channels of T = 16 bytes
-template <typename T> struct Group;
-template <> struct Group<half_t> {
-  static constexpr int G = 8;
-  typedef half8_t vec;
-};
-template <> struct Group<float> {
-  static constexpr int G = 4;
-  typedef float4_t vec;
-};
-
-// source index pair and weights of output index o along one axis: torch's rule for float inputs (see the header comment of
-// ft_upsample_bilinear_ac_fwd).  The min() never acts for the ratios the host passes (r * (out - 1) <= in - 1 up to one rounding,
-// which (int) truncates back onto in - 1); it is there so that no ratio can index past the row.
-// Contraction is off here: `src` must be the ROUNDED product before i0 is taken off it (hipcc's default would fuse the product
-// into the subtraction, l1 = fma(r, o, -i0), which is not the rule's l1 and moves a result by up to a few 2^-24 of the data).
-__device__ __forceinline__ void ac_source(float r, int o, int in, int& i0, int& i1, float& l0, float& l1) {
-#pragma clang fp contract(off)
-  const float src = r * (float)o;
-  i0 = min((int)src, in - 1);
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = src - (float)i0;
-  l0 = 1.f - l1;
-}
 
 // grid = (ho, images in flight, pieces of one output row): blockIdx.x is the output row, so its source rows and weights are
 // uniform over the workgroup; a thread takes the (column, channel group) items j, j + 256 gridDim.z, .. of that row — lanes run

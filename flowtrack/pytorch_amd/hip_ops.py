@@ -1561,6 +1561,59 @@ def record_upsample_ac(prog: Program, x: ActView, y: ActView, scale: Optional[to
              x.cstride, x.coff, y.cstride, y.coff, scale.data_ptr() if scale is not None else None, keep=(x.t, y.t, scale))
 
 
+def _hg_views(what: str, ref: ActView, views, tables) -> None:
+    for v in views:
+        if v is not None and (v.rowpacked or v.N != ref.N or v.C != ref.C or v.t.dtype != ref.t.dtype or v.t.device != ref.t.device or not v.t.is_contiguous()):
+            raise FlowtrackHipError(f"{what}: every view must be a plain contiguous NHWC view of the input's dtype, batch and channel count")
+    for t in tables:
+        if t is not None and (t.dtype != torch.float32 or t.numel() < ref.C or not t.is_contiguous() or t.device != ref.t.device):
+            raise FlowtrackHipError(f"{what}: scale and shift must be contiguous fp32 [{ref.C}] on the views' device")
+
+
+def record_hourglass_down(prog: Program, x: ActView, pool: Optional[ActView] = None, a_pool: Optional[ActView] = None,
+                          bn_pool: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, a_full: Optional[ActView] = None,
+                          bn_full: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> None:
+    """The way down of an hourglass level (ft_hourglass_down_fwd): pool = MaxPool2d(2, 2)(x), a_pool = relu(s pool + b) with
+    (s, b) = bn_pool, a_full = relu(s x + b) with (s, b) = bn_full; any of the three outputs may be None, not all."""
+    if pool is None and a_pool is None and a_full is None:
+        raise FlowtrackHipError("hourglass_down: no output")
+    if (a_pool is None) != (bn_pool is None) or (a_full is None) != (bn_full is None):
+        raise FlowtrackHipError("hourglass_down: an activated output and its (scale, shift) come together")
+    _hg_views("hourglass_down", x, (pool, a_pool, a_full), (bn_pool or ()) + (bn_full or ()))
+    for v in (pool, a_pool):
+        if v is not None and (v.H, v.W) != (x.H // 2, x.W // 2):
+            raise FlowtrackHipError(f"hourglass_down: a pooled view of {v.H}x{v.W} behind an input of {x.H}x{x.W}")
+    if a_full is not None and (a_full.H, a_full.W) != (x.H, x.W):
+        raise FlowtrackHipError("hourglass_down: a_full must have the input's size")
+
+    def view(v):
+        return (v.t.data_ptr(), v.cstride, v.coff) if v is not None else (None, 0, 0)
+
+    def tabs(t):
+        return (t[0].data_ptr(), t[1].data_ptr()) if t is not None else (None, None)
+    prog.add("ft_hourglass_down_fwd", x.t.data_ptr(), _lib.dtype_code(x.t.dtype), x.N, x.H, x.W, x.C, x.cstride, x.coff, *view(pool),
+             *view(a_pool), *tabs(bn_pool), *view(a_full), *tabs(bn_full),
+             keep=(x.t,) + tuple(v.t for v in (pool, a_pool, a_full) if v is not None) + tuple(bn_pool or ()) + tuple(bn_full or ()))
+
+
+def record_hourglass_up(prog: Program, skip: ActView, low: ActView, out: ActView, a_sum: Optional[ActView] = None,
+                        bn: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> None:
+    """The way up of an hourglass level (ft_hourglass_up_fwd): out = skip + F.upsample(low, size=skip's, mode='bilinear',
+    align_corners=True), a_sum = relu(s out + b) with (s, b) = bn, from out as stored.  `out` may be the view `skip` itself."""
+    if (a_sum is None) != (bn is None):
+        raise FlowtrackHipError("hourglass_up: a_sum and its (scale, shift) come together")
+    _hg_views("hourglass_up", skip, (low, out, a_sum), bn or ())
+    for v in (out, a_sum):
+        if v is not None and (v.H, v.W) != (skip.H, skip.W):
+            raise FlowtrackHipError("hourglass_up: sum and a_sum must have the skip map's size")
+    prog.add("ft_hourglass_up_fwd", skip.t.data_ptr(), low.t.data_ptr(), _lib.dtype_code(skip.t.dtype), skip.N, skip.C, skip.H, skip.W,
+             low.H, low.W, skip.cstride, skip.coff, low.cstride, low.coff, out.t.data_ptr(), out.cstride, out.coff,
+             a_sum.t.data_ptr() if a_sum is not None else None, a_sum.cstride if a_sum is not None else 0,
+             a_sum.coff if a_sum is not None else 0, bn[0].data_ptr() if bn is not None else None,
+             bn[1].data_ptr() if bn is not None else None,
+             keep=(skip.t, low.t, out.t) + ((a_sum.t,) if a_sum is not None else ()) + tuple(bn or ()))
+
+
 def current_stream_handle(device=None) -> ctypes.c_void_p:
     """Handle of torch's current stream on `device` (default: the current device)."""
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)

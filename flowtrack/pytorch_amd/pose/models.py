@@ -6,6 +6,7 @@ resnet.py:15-55, blocks.py:83-120):
     models.deconv(backbone: str, num_classes: int, pretrained: bool) -> module
     models.fpn(backbone: str, num_classes: int, pretrained: bool) -> module
     models.pose(backbone: str, num_classes: int, pretrained: bool) -> module
+    models.hg(num_classes: int, num_stacks: int) -> module            (hourglass.py:227-231; forward returns one map per stack)
     module.forward(x[B,3,H,W]) -> heatmaps [B,K,H/4,W/4] (fp32)
     module.state_dict() / load_state_dict() / init_net(path) / .cuda() / .half() / .eval()
 with the reference's parameter names and shapes, so its checkpoints
@@ -28,7 +29,7 @@ import torch.nn as nn
 from ..engine import HipModule
 from ..hip_ops import (ActView, FlowtrackHipError, FusedConv, FusedLateralDeconv, FusedShortcutConv, Program, record_scale_shift_act, bottleneck_exit_fusable, bottleneck_fusable,
                        bottleneck_entry_fusable, bottleneck_head_fusable, bottleneck_cluster_supported, bottleneck_strips_supported, bottleneck_head_stream_fusable, bottleneck_prefers_fused, new_act, new_rowpacked_act, record_bottleneck, record_bottleneck_entry, record_bottleneck_head, record_bottleneck_head_stream,
-                       record_bottleneck_exit, record_maxpool, record_pack_input, fold_scale_shift, record_upsample_ac)
+                       record_bottleneck_exit, record_maxpool, record_pack_input, fold_scale_shift, record_upsample_ac, record_hourglass_down, record_hourglass_up)
 from ..params import ActMarker, BatchNormParams, ConvParams, ConvTransposeParams
 
 # depth -> blocks per stage; only Bottleneck nets are valid because the head hard-codes 2048
@@ -215,11 +216,15 @@ class PoseResnet(HipModule):
         if self.flip_pairs is not None:
             raise FlowtrackHipError(f"{what}: flip_pairs is set, and the exact-arg-max mode does not combine with the flip test")
 
-    def _build_plan(self, B: int, H: int, W: int, device, dtype, perm=None) -> _PosePlan:
+    def _check_input_size(self, H: int, W: int) -> None:
         if H % 32 or W % 32:
             raise FlowtrackHipError(f"input {H}x{W}: height and width must be multiples of 32")
+
+    def _build_plan(self, B: int, H: int, W: int, device, dtype, perm=None) -> _PosePlan:
+        """The plan of one input shape: the staged input (and its mirrored half in a flip plan), the network's own launches
+        (_record_net: what a model family overrides), then the flip merge / the key points / the exact-arg-max screen."""
+        self._check_input_size(H, W)
         prog = Program(self._side_stream(device))
-        mk = dict(dtype=dtype, device=device)
         B0 = B
         if perm is not None:
             # flip plan: everything below is the ordinary launch list at batch 2B; crops [B0, 2 B0) are the mirrored copies of [0, B0)
@@ -227,6 +232,60 @@ class PoseResnet(HipModule):
         x_static = torch.empty((B, 3, H, W), dtype=torch.float32, device=device)
         if perm is not None:
             prog.add("ft_hflip_nchw_f32", x_static.data_ptr(), x_static[B0:].data_ptr(), B0, 3, H, W)
+        stages, heatmaps = self._record_net(prog, x_static, dtype, device)
+        if perm is not None:
+            # last launch: average the two halves (mirror + left/right swap of the second) and, with keypoints_in_plan, the key points
+            # of the merged maps — in place of the separate ft_heatmap_keypoint_rows launch
+            K, hh, hw = self.num_classes, heatmaps.shape[2], heatmaps.shape[3]
+            merged = torch.empty((B0, K, hh, hw), dtype=torch.float32, device=device)
+            plan = _PosePlan(prog, x_static[:B0], merged)
+            plan.stages, plan.heatmaps_raw, plan.x_full = stages, heatmaps, x_static
+            plan.flip_perm = torch.tensor(perm, dtype=torch.int32, device=device)
+            plan.kp_idx = plan.kp_rows = None
+            keep = [merged, heatmaps, plan.flip_perm]
+            if self.keypoints_in_plan is not None:
+                plan.kp_idx = torch.empty((B0, K), dtype=torch.int32, device=device)
+                plan.kp_rows = torch.empty((B0, K, 3), dtype=torch.float32, device=device)
+                plan.kp_score, plan.kp_coords = plan.kp_rows[:, :, 2:], plan.kp_rows[:, :, :2]
+                keep += [plan.kp_idx, plan.kp_rows]
+            prog.add("ft_heatmap_flip_merge", heatmaps.data_ptr(), heatmaps[B0:].data_ptr(), plan.flip_perm.data_ptr(), B0, K, hh, hw,
+                     int(bool(self.keypoints_in_plan)), merged.data_ptr(), plan.kp_idx.data_ptr() if plan.kp_idx is not None else None,
+                     plan.kp_rows.data_ptr() if plan.kp_rows is not None else None, keep=tuple(keep))
+            return plan
+        plan = _PosePlan(prog, x_static, heatmaps)
+        plan.stages = stages
+        if self.keypoints_in_plan is not None:
+            # max_preds (+ the 0.25 px nudge of final_preds) as the last launch of the plan: no extra stream work per call
+            K, hh, hw = self.num_classes, heatmaps.shape[2], heatmaps.shape[3]
+            # written as (x, y, score) rows — what the tracking glue and the multi-GPU gather consume; scores / coords are views
+            plan.kp_idx = torch.empty((B, K), dtype=torch.int32, device=device)
+            plan.kp_rows = torch.empty((B, K, 3), dtype=torch.float32, device=device)
+            plan.kp_score, plan.kp_coords = plan.kp_rows[:, :, 2:], plan.kp_rows[:, :, :2]
+            prog.add("ft_heatmap_keypoint_rows", heatmaps.data_ptr(), B, K, hh, hw, int(bool(self.keypoints_in_plan)),
+                     plan.kp_idx.data_ptr(), plan.kp_rows.data_ptr(), keep=(plan.kp_idx, plan.kp_rows))
+            if self.exact_in_plan and dtype == torch.float16 and B <= 1024:
+                # the exact-arg-max mode's device side INSIDE the plan's graph (round 5): screen -> flag compaction + gather of the
+                # flagged crops' inputs -> header {count, indices} to pinned memory.  As graph nodes they cost their kernel time
+                # (~10 us); as five eager launches behind the replay they cost ~70 us of gaps per step.  exact_rel_bound is frozen
+                # into the plan (DeconvResnet.exact_submit_plan / exact_finish_plan).
+                import ctypes
+                ex = {"flags": torch.empty(B, dtype=torch.int32, device=device), "stats": torch.empty((B, 4), dtype=torch.float32, device=device),
+                      "stage": torch.empty((B, 3, H, W), dtype=torch.float32, device=device),
+                      "header": torch.zeros(1 + B, dtype=torch.int32, device=device), "header_host": torch.zeros(1 + B, dtype=torch.int32).pin_memory(),
+                      "rel_bound": float(self.exact_argmax_rel_bound), "event": None, "busy": False}
+                prog.add("ft_heatmap_argmax_screen", heatmaps.data_ptr(), B, K, hh, hw, ctypes.c_float(ex["rel_bound"]), ex["flags"].data_ptr(),
+                         ex["stats"].data_ptr(), keep=(ex["flags"], ex["stats"]))
+                prog.add("ft_gather_flagged_rows", ex["flags"].data_ptr(), B, x_static.data_ptr(), ctypes.c_longlong(3 * H * W * 4), ex["stage"].data_ptr(),
+                         ex["header"].data_ptr(), keep=(ex["stage"], ex["header"]))
+                prog.add("ft_memcpy_async", ex["header_host"].data_ptr(), ex["header"].data_ptr(), ctypes.c_size_t((1 + B) * 4), keep=(ex["header_host"],))
+                plan.exact = ex
+        return plan
+
+    def _record_net(self, prog, x_static, dtype, device):
+        """Record everything between "the input is staged in x_static [B,3,H,W] fp32" and "the heat maps exist": returns (stages,
+        the NCHW fp32 heat maps the plan's tail reads).  Here: the ResNet trunk and, through _record_head, the model's head."""
+        B, _, H, W = x_static.shape
+        mk = dict(dtype=dtype, device=device)
         # 7x7/s2/p3 stem: one kernel row = one K-run.  fp16: conv1 + bn1 + relu + maxpool (resnet.py:19-23) are ONE launch
         # (ft_conv_desc.pool; its patch starts one stem column further left: 5 physical pad columns instead of 3) and the
         # [B, H/2, W/2, 64] stem map never exists
@@ -333,53 +392,7 @@ class PoseResnet(HipModule):
 
         stages["layer4"] = cur
         heatmaps = self._record_head(prog, stages, cur, dtype, device)
-        if perm is not None:
-            # last launch: average the two halves (mirror + left/right swap of the second) and, with keypoints_in_plan, the key points
-            # of the merged maps — in place of the separate ft_heatmap_keypoint_rows launch
-            K, hh, hw = self.num_classes, heatmaps.shape[2], heatmaps.shape[3]
-            merged = torch.empty((B0, K, hh, hw), dtype=torch.float32, device=device)
-            plan = _PosePlan(prog, x_static[:B0], merged)
-            plan.stages, plan.heatmaps_raw, plan.x_full = stages, heatmaps, x_static
-            plan.flip_perm = torch.tensor(perm, dtype=torch.int32, device=device)
-            plan.kp_idx = plan.kp_rows = None
-            keep = [merged, heatmaps, plan.flip_perm]
-            if self.keypoints_in_plan is not None:
-                plan.kp_idx = torch.empty((B0, K), dtype=torch.int32, device=device)
-                plan.kp_rows = torch.empty((B0, K, 3), dtype=torch.float32, device=device)
-                plan.kp_score, plan.kp_coords = plan.kp_rows[:, :, 2:], plan.kp_rows[:, :, :2]
-                keep += [plan.kp_idx, plan.kp_rows]
-            prog.add("ft_heatmap_flip_merge", heatmaps.data_ptr(), heatmaps[B0:].data_ptr(), plan.flip_perm.data_ptr(), B0, K, hh, hw,
-                     int(bool(self.keypoints_in_plan)), merged.data_ptr(), plan.kp_idx.data_ptr() if plan.kp_idx is not None else None,
-                     plan.kp_rows.data_ptr() if plan.kp_rows is not None else None, keep=tuple(keep))
-            return plan
-        plan = _PosePlan(prog, x_static, heatmaps)
-        plan.stages = stages
-        if self.keypoints_in_plan is not None:
-            # max_preds (+ the 0.25 px nudge of final_preds) as the last launch of the plan: no extra stream work per call
-            K, hh, hw = self.num_classes, heatmaps.shape[2], heatmaps.shape[3]
-            # written as (x, y, score) rows — what the tracking glue and the multi-GPU gather consume; scores / coords are views
-            plan.kp_idx = torch.empty((B, K), dtype=torch.int32, device=device)
-            plan.kp_rows = torch.empty((B, K, 3), dtype=torch.float32, device=device)
-            plan.kp_score, plan.kp_coords = plan.kp_rows[:, :, 2:], plan.kp_rows[:, :, :2]
-            prog.add("ft_heatmap_keypoint_rows", heatmaps.data_ptr(), B, K, hh, hw, int(bool(self.keypoints_in_plan)),
-                     plan.kp_idx.data_ptr(), plan.kp_rows.data_ptr(), keep=(plan.kp_idx, plan.kp_rows))
-            if self.exact_in_plan and dtype == torch.float16 and B <= 1024:
-                # the exact-arg-max mode's device side INSIDE the plan's graph (round 5): screen -> flag compaction + gather of the
-                # flagged crops' inputs -> header {count, indices} to pinned memory.  As graph nodes they cost their kernel time
-                # (~10 us); as five eager launches behind the replay they cost ~70 us of gaps per step.  exact_rel_bound is frozen
-                # into the plan (DeconvResnet.exact_submit_plan / exact_finish_plan).
-                import ctypes
-                ex = {"flags": torch.empty(B, dtype=torch.int32, device=device), "stats": torch.empty((B, 4), dtype=torch.float32, device=device),
-                      "stage": torch.empty((B, 3, H, W), dtype=torch.float32, device=device),
-                      "header": torch.zeros(1 + B, dtype=torch.int32, device=device), "header_host": torch.zeros(1 + B, dtype=torch.int32).pin_memory(),
-                      "rel_bound": float(self.exact_argmax_rel_bound), "event": None, "busy": False}
-                prog.add("ft_heatmap_argmax_screen", heatmaps.data_ptr(), B, K, hh, hw, ctypes.c_float(ex["rel_bound"]), ex["flags"].data_ptr(),
-                         ex["stats"].data_ptr(), keep=(ex["flags"], ex["stats"]))
-                prog.add("ft_gather_flagged_rows", ex["flags"].data_ptr(), B, x_static.data_ptr(), ctypes.c_longlong(3 * H * W * 4), ex["stage"].data_ptr(),
-                         ex["header"].data_ptr(), keep=(ex["stage"], ex["header"]))
-                prog.add("ft_memcpy_async", ex["header_host"].data_ptr(), ex["header"].data_ptr(), ctypes.c_size_t((1 + B) * 4), keep=(ex["header_host"],))
-                plan.exact = ex
-        return plan
+        return stages, heatmaps
 
     def _record_stage_exit(self, prog, name: str, blk, nname: str, nblk, cur, out, dtype, device):
         """The seam between two stages: `blk` = the stage's last identity block (from `cur` into `out`), `nblk` = the stride-2 entry
@@ -1086,6 +1099,235 @@ class LateralDeconvResnet(PoseResnet):
         return heatmaps
 
 
+class HgBottleneck(nn.Module):
+    """Parameter layout of the hourglass's pre-activation block (hourglass.py:10-45): out = branch(relu(bn(x))) + shortcut(x) with
+    branch = 1x1 -> bn -> relu -> 3x3 -> bn -> relu -> 1x1 at half the output's planes; `shortcut` is a 1x1 conv where the channel
+    count changes, and the 'no_preact' form (res1, behind the stem's own ReLU) has no `preact`."""
+
+    def __init__(self, inplanes: int, outplanes: int, preact: bool = True, bias: bool = True):
+        super().__init__()
+        planes = outplanes // 2
+        self.shortcut = ConvParams(inplanes, outplanes, 1, bias=bias) if inplanes != outplanes else None
+        if preact:
+            self.preact = nn.Sequential(BatchNormParams(inplanes), ActMarker("relu"))
+        self.branch = nn.Sequential(ConvParams(inplanes, planes, 1, bias=bias), BatchNormParams(planes), ActMarker("relu"),
+                                    ConvParams(planes, planes, 3, padding=1, bias=bias), BatchNormParams(planes), ActMarker("relu"),
+                                    ConvParams(planes, outplanes, 1, bias=bias))
+
+
+def _hg_residual(inplanes: int, outplanes: int, num_blocks: int, preact: bool = True) -> nn.Sequential:
+    """_make_residual (hourglass.py:56-63,175-182): num_blocks blocks, the first one carries the change of width."""
+    return nn.Sequential(HgBottleneck(inplanes, outplanes, preact), *[HgBottleneck(outplanes, outplanes) for _ in range(1, num_blocks)])
+
+
+class Hourglass(nn.Module):
+    """Parameter layout of one hourglass (hourglass.py:47-74): hg[d] = the three chains of level d + 1 (up, low1, low3), and a
+    fourth (low2) at the lowest level d = 0."""
+
+    def __init__(self, num_blocks: int, planes: int, depth: int):
+        super().__init__()
+        self.depth = depth
+        self.maxpool = ActMarker("maxpool2x2s2")
+        self.hg = nn.ModuleList(nn.ModuleList(_hg_residual(planes, planes, num_blocks) for _ in range(4 if d == 0 else 3))
+                                for d in range(depth))
+
+
+class HourglassNet(PoseResnet):
+    """The stacked hourglass (hourglass.py:127-231; Newell et al., ECCV 2016) on the HIP path.  Of PoseResnet it keeps everything
+    behind the network itself — the plan cache, forward / replay, the flip plan, the key points inside the plan — and replaces the
+    parameters and the launch list (_record_net); none of the ResNet trunk's switches applies.
+
+        x = res3(res2(maxpool(res1(pre(input)))))                                            [B, H/4, W/4, 256]
+        per stack i:  y = proj[i](res[i](hg[i](x)));  heatmap_i = heatmap[i](y);  x = x + proj_[i](y) + heatmap_[i](heatmap_i)
+        hg level n:   up1 = hg[n-1][0](x);  low1 = hg[n-1][1](maxpool(x));  low2 = level n-1 (low1), or hg[0][3](low1) at n = 1
+                      out = up1 + upsample_ac(hg[n-1][2](low2), size of up1)
+
+    Every block is pre-activation: conv1 reads relu(bn(x)), the residual add reads x.  A block is three conv launches — 1x1 + bn +
+    relu, 3x3 + bn + relu, 1x1 + bias + residual (no activation) — and its activated input comes from where its raw input is made:
+      ft_hourglass_down_fwd  at the top of every level reads the level's input once and writes a_full (for hg[n-1][0]), the pooled
+                             map and its activated copy (for hg[n-1][1]); behind res1 it writes the pooled pair only;
+      ft_hourglass_up_fwd    at the end of every level writes the sum (in place of up1) and its activated copy for the next block
+                             (hg[n][2] of the level above, res[i] at the top);
+      ft_scale_shift_act_nhwc_fwd  only where the input is a conv3 output: inside chains of more than one block, hg[0][3], the
+                             lowest hg[0][2], res3.
+    fuse_seams = False records the same arithmetic unfused (pool alone, sum alone, stand-alone activations): the fused outputs
+    are bit-identical to it (tests/test_hourglass_gpu.py).  The join between stacks is two convs chained through the residual
+    input; stack i's heat map is written twice by the same layer, NCHW fp32 for the caller and NHWC as heatmap_[i]'s input."""
+    supports_exact = False
+    #: write the activated copies at the level seams (ft_hourglass_down_fwd / ft_hourglass_up_fwd) instead of stand-alone launches
+    fuse_seams: bool = True
+    depth, num_feats = 4, 256
+
+    def __init__(self, num_classes: int, num_stacks: int, num_blocks: int):
+        HipModule.__init__(self)        # (not PoseResnet's: that one builds the ResNet trunk)
+        self.num_classes, self.num_stacks, self.num_blocks = num_classes, num_stacks, num_blocks
+        feats = self.num_feats
+        self.pre = nn.Sequential(ConvParams(3, 64, 7, stride=2, padding=3, bias=True), BatchNormParams(64), ActMarker("relu"))
+        self.res1 = _hg_residual(64, 256, 1, preact=False)
+        self.res2 = _hg_residual(256, 256, 1)
+        self.res3 = _hg_residual(256, feats, 1)
+        self.maxpool = ActMarker("maxpool2x2s2")
+        self.hg = nn.ModuleList(Hourglass(num_blocks, feats, self.depth) for _ in range(num_stacks))
+        self.res = nn.ModuleList(_hg_residual(feats, feats, num_blocks) for _ in range(num_stacks))
+        self.proj = nn.ModuleList(nn.Sequential(ConvParams(feats, feats, 1), BatchNormParams(feats), ActMarker("relu")) for _ in range(num_stacks))
+        self.heatmap = nn.ModuleList(ConvParams(feats, num_classes, 1) for _ in range(num_stacks))
+        self.proj_ = nn.ModuleList(ConvParams(feats, feats, 1) for _ in range(num_stacks - 1))
+        self.heatmap_ = nn.ModuleList(ConvParams(num_classes, feats, 1) for _ in range(num_stacks - 1))
+        self.init_weights()
+
+    # -- initialisation (hourglass.py:166-173): the constructor's, there is no init_net in the reference ------------------------
+    def init_weights(self, pretrained: str = "") -> None:
+        if pretrained and os.path.isfile(pretrained):
+            print("=> loading pretrained model {}".format(pretrained))
+            self.load_state_dict(torch.load(pretrained, map_location="cpu"), strict=False)
+            return
+        for m in self.modules():
+            if isinstance(m, ConvParams):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+            elif isinstance(m, BatchNormParams):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+        self._invalidate()
+
+    def _init_head(self) -> None:
+        pass
+
+    def _check_input_size(self, H: int, W: int) -> None:
+        low = 1 << self.depth
+        if H % 4 or W % 4 or H // 4 < low or W // 4 < low:
+            raise FlowtrackHipError(f"input {H}x{W}: height and width must be multiples of 4 and at least {4 * low} (the map of the "
+                                    f"hourglass's lowest level, 1/{4 * low} of the input rounded down, must not be empty)")
+
+    @torch.no_grad()
+    def forward(self, x: torch.Tensor, copy_output: bool = True) -> List[torch.Tensor]:
+        """x: [B,3,H,W] on the model's GPU -> the reference's list of num_stacks heat-map tensors [B,K,H/4,W/4] fp32, one per
+        stack (hourglass.py:203-225); the last one is what plans, the flip test and the key points are built on."""
+        self._forward(x, False, None)
+        maps = [self._last_plan.stages[f"heatmap.{i}"] for i in range(self.num_stacks)]
+        return [t.clone() for t in maps] if copy_output else maps
+
+    # -- the launch list --------------------------------------------------------------------------------------------------------
+    def _bn_table(self, name: str, bn, dtype, device):
+        """(scale, shift) fp32 [C] of an eval-mode BatchNorm for the element-wise kernels, folded once per (dtype, device)."""
+        key = (name + ".scale_shift", dtype, str(device))
+        tab = self._layers.get(key)
+        if tab is None:
+            tab = self._layers[key] = fold_scale_shift(bn.num_features, bn.num_features, None, bn.as_dict(), device)
+        return tab
+
+    def _record_net(self, prog, x_static, dtype, device):
+        B, _, H, W = x_static.shape
+        mk = dict(dtype=dtype, device=device)
+        stages = _Stages()
+        scratch = {}
+
+        def tmp(tag, h, w, c):          # t1 / t2 of a block: read by the next launch only, so one buffer per size serves every block
+            key = (tag, h, w, c)
+            if key not in scratch:
+                scratch[key] = new_act(B, h, w, c, dtype, device)
+            return scratch[key]
+
+        def act_of(name, blk, raw):     # stand-alone relu(bn(raw)) for block `name`
+            a = new_act(B, raw.H, raw.W, raw.C, dtype, device)
+            record_scale_shift_act(prog, raw, a, *self._bn_table(name + ".preact.0", blk.preact[0], dtype, device), "relu")
+            return a
+
+        def block(name, blk, raw, a):
+            br = blk.branch
+            c1 = self.fused(name + ".branch.0", br[0].weight, bias=br[0].bias, bn=br[1].as_dict(), act="relu", **mk)
+            c2 = self.fused(name + ".branch.3", br[3].weight, pad=1, bias=br[3].bias, bn=br[4].as_dict(), act="relu", **mk)
+            c3 = self.fused(name + ".branch.6", br[6].weight, bias=br[6].bias, act=None, **mk)
+            t1, t2 = tmp("t1", raw.H, raw.W, c1.cout), tmp("t2", raw.H, raw.W, c2.cout)
+            c1.record(prog, a, t1)
+            c2.record(prog, t1, t2)
+            res = raw
+            if blk.shortcut is not None:        # res1's 64 -> 256 projection: a conv of its own that feeds the residual input
+                res = new_act(B, raw.H, raw.W, c3.cout, dtype, device)
+                self.fused(name + ".shortcut", blk.shortcut.weight, bias=blk.shortcut.bias, act=None, **mk).record(prog, raw, res)
+            out = new_act(B, raw.H, raw.W, c3.cout, dtype, device)
+            c3.record(prog, t2, out, residual=res)
+            return out
+
+        def chain(name, seq, raw, a):   # a = the first block's activated input where a seam wrote it, else None
+            for k, blk in enumerate(seq):
+                bname = f"{name}.{k}"
+                if a is None:
+                    a = act_of(bname, blk, raw)
+                raw, a = block(bname, blk, raw, a), None
+            return raw
+
+        def down(x, tab_pool, tab_full):
+            pool = new_act(B, x.H // 2, x.W // 2, x.C, dtype, device)
+            a_pool = new_act(B, x.H // 2, x.W // 2, x.C, dtype, device)
+            a_full = new_act(B, x.H, x.W, x.C, dtype, device) if tab_full is not None else None
+            if self.fuse_seams:
+                record_hourglass_down(prog, x, pool, a_pool, tab_pool, a_full, tab_full)
+            else:
+                record_hourglass_down(prog, x, pool)
+                if a_full is not None:
+                    record_scale_shift_act(prog, x, a_full, *tab_full, "relu")
+                record_scale_shift_act(prog, pool, a_pool, *tab_pool, "relu")
+            return pool, a_pool, a_full
+
+        def level(i, n, x, tab_next):
+            """Level n of hourglass i on the raw map x -> (out, relu(bn_next(out)))."""
+            mods, name = self.hg[i].hg[n - 1], f"hg.{i}.hg.{n - 1}"
+            pool, a_pool, a_full = down(x, self._bn_table(name + ".1.0.preact.0", mods[1][0].preact[0], dtype, device),
+                                        self._bn_table(name + ".0.0.preact.0", mods[0][0].preact[0], dtype, device))
+            up1 = chain(name + ".0", mods[0], x, a_full)
+            low1 = chain(name + ".1", mods[1], pool, a_pool)
+            if n > 1:
+                low2, a_low2 = level(i, n - 1, low1, self._bn_table(name + ".2.0.preact.0", mods[2][0].preact[0], dtype, device))
+            else:
+                low2, a_low2 = chain(name + ".3", mods[3], low1, None), None
+            low3 = chain(name + ".2", mods[2], low2, a_low2)
+            a_out = new_act(B, up1.H, up1.W, up1.C, dtype, device)
+            if self.fuse_seams:
+                record_hourglass_up(prog, up1, low3, up1, a_out, tab_next)      # (the sum takes up1's place: nothing else reads up1)
+            else:
+                record_hourglass_up(prog, up1, low3, up1)
+                record_scale_shift_act(prog, up1, a_out, *tab_next, "relu")
+            return up1, a_out
+
+        # pre = 7x7/s2/p3 conv + bias + bn + relu on the row-packed input (one kernel row = one K-run), res1, the 2x2 pool, res2, res3
+        a_in = new_rowpacked_act(B, H, W, 3, 3, dtype, device)
+        record_pack_input(prog, x_static, a_in)
+        p = new_act(B, H // 2, W // 2, 64, dtype, device)
+        self.fused("pre", self.pre[0].weight, stride=2, pad=3, bias=self.pre[0].bias, bn=self.pre[1].as_dict(), act="relu", **mk).record(prog, a_in, p)
+        stages["pre"] = p
+        r1 = chain("res1", self.res1, p, p)             # 'no_preact': the block reads the stem's activated map as it is
+        stages["res1"] = r1
+        pool, a_pool, _ = down(r1, self._bn_table("res2.0.preact.0", self.res2[0].preact[0], dtype, device), None)
+        x = chain("res3", self.res3, chain("res2", self.res2, pool, a_pool), None)
+        stages["res3"] = x
+        K = self.num_classes
+        heatmaps = None
+        for i in range(self.num_stacks):
+            y, a_y = level(i, self.depth, x, self._bn_table(f"res.{i}.0.preact.0", self.res[i][0].preact[0], dtype, device))
+            stages[f"hg.{i}"] = y
+            y = chain(f"res.{i}", self.res[i], y, a_y)
+            y2 = new_act(B, y.H, y.W, self.num_feats, dtype, device)
+            self.fused(f"proj.{i}", self.proj[i][0].weight, bias=self.proj[i][0].bias, bn=self.proj[i][1].as_dict(), act="relu", **mk).record(prog, y, y2)
+            hm = self.fused(f"heatmap.{i}", self.heatmap[i].weight, bias=self.heatmap[i].bias, act=None, **mk)
+            heatmaps = torch.empty((B, K, y.H, y.W), dtype=torch.float32, device=device)
+            hm.record(prog, y2, heatmaps)
+            stages[f"heatmap.{i}"] = heatmaps
+            if i < self.num_stacks - 1:
+                # x + proj_(y) + heatmap_(heatmap): the heat map once more as an NHWC map of the compute type (its pad channels
+                # [K, 32 k) stay zero: the conv reads them against zero weights), then two convs chained through the residual input
+                hm_nhwc = new_act(B, y.H, y.W, K, dtype, device, cstride=(K + 31) // 32 * 32)
+                hm.record(prog, y2, hm_nhwc)
+                t = new_act(B, y.H, y.W, self.num_feats, dtype, device)
+                self.fused(f"proj_.{i}", self.proj_[i].weight, bias=self.proj_[i].bias, act=None, **mk).record(prog, y2, t, residual=x)
+                xn = new_act(B, y.H, y.W, self.num_feats, dtype, device)
+                self.fused(f"heatmap_.{i}", self.heatmap_[i].weight, bias=self.heatmap_[i].bias, act=None, **mk).record(prog, hm_nhwc, xn, residual=t)
+                x = xn
+                stages[f"stack.{i}"] = x
+        return stages, heatmaps
+
+
 def deconv(backbone: str, num_classes: int, pretrained: bool) -> DeconvResnet:
     """Factory with the reference's signature (pose_deconv.py:166-179): backbone 'resnet50' |
     'resnet101' | 'resnet152'; pretrained=True loads data/pretrained/<backbone>.pth if present."""
@@ -1126,3 +1368,11 @@ def pose(backbone: str, num_classes: int, pretrained: bool) -> LateralDeconvResn
     path = os.path.join("data", "pretrained", "{}.pth".format(backbone)) if pretrained else ""
     model.init_net(path)
     return model
+
+
+def hg(num_classes: int, num_stacks: int) -> HourglassNet:
+    """Factory with the reference's signature (hourglass.py:227-231): num_stacks hourglasses of depth 4 on 256 features with
+    8 // num_stacks blocks per chain, every conv with bias; the constructor's init is the reference's (there is no checkpoint path)."""
+    if isinstance(num_stacks, bool) or not isinstance(num_stacks, int) or not 1 <= num_stacks <= 8:
+        raise FlowtrackHipError(f"num_stacks {num_stacks!r}: an integer from 1 to 8 (the reference builds 8 // num_stacks blocks per chain)")
+    return HourglassNet(num_classes, num_stacks, 8 // num_stacks)

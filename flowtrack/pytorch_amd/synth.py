@@ -131,6 +131,40 @@ def fill_pose_state_dict(sd: Dict[str, torch.Tensor], seed: int) -> Dict[str, to
     return out
 
 
+#: gain of the hourglass convs that write into the residual stream (fill_hg_state_dict)
+HG_STREAM_GAIN = 0.03
+
+
+def fill_hg_state_dict(sd: Dict[str, torch.Tensor], seed: int) -> Dict[str, torch.Tensor]:
+    """Weights for an `hg(K, num_stacks)` state_dict.  The hourglass has no BatchNorm behind a block's last conv, so He gains
+    everywhere let the residual stream grow with every one of its 112 blocks (the reference reaches 1e19 after 8 stacks).  The convs
+    that write into that stream — every block's last conv (`*.branch.6`), `proj_` and `heatmap_` — therefore take the small gain
+    HG_STREAM_GAIN, the heat-map convs 1.0 and every other conv the usual 2.0; BatchNorm statistics and biases as in
+    fill_pose_state_dict."""
+    out = {}
+    for k, v in sd.items():
+        shape = tuple(v.shape)
+        if k.endswith("num_batches_tracked"):
+            out[k] = torch.tensor(0, dtype=torch.long)
+        elif k.endswith("running_mean"):
+            out[k] = normal(seed, k, shape, std=0.1)
+        elif k.endswith("running_var"):
+            out[k] = uniform(seed, k, shape, 0.5, 1.5)
+        elif v.dim() == 4:
+            if ".branch.6." in k or k.startswith("proj_.") or k.startswith("heatmap_."):
+                gain = HG_STREAM_GAIN
+            else:
+                gain = 1.0 if k.startswith("heatmap.") else 2.0
+            out[k] = normal(seed, k, shape, std=float(np.sqrt(gain / _fan_in(k, shape, False))))
+        elif k.endswith(".weight"):  # BN gamma
+            out[k] = uniform(seed, k, shape, 0.5, 1.5)
+        elif k.endswith(".bias"):
+            out[k] = normal(seed, k, shape, std=0.1)
+        else:
+            raise KeyError(k)
+    return out
+
+
 def fill_flow_state_dict(sd: Dict[str, torch.Tensor], seed: int) -> Dict[str, torch.Tensor]:
     """He-scaled (LeakyReLU 0.1) conv / deconv weights and small biases for a FlowNet2* state_dict."""
     out = {}

@@ -512,6 +512,41 @@ int ft_scale_shift_act_nhwc_fwd(const void* x, void* y, int dtype, long long npi
                                 int y_cstride, int y_coff, const float* scale, const float* shift, int act, float slope,
                                 ft_stream_t stream);
 
+/* ---- Stacked hourglass (lib/pose/models/hourglass.py:110-121): the two seams of a level that are not convs ----
+ * Every block of the hourglass is pre-activation: it reads its raw input (the shortcut) and relu(bn(input)).  At the two
+ * memory-bound seams of a level the activated copies are written while the map is in registers.  Both kernels: NHWC, FT_F16 or
+ * FT_F32 in and out, `*_cstride` / `*_coff` channel views as above (channel c of a pixel at element pixel * cstride + coff + c;
+ * channels outside [coff, coff + C) of an output stay untouched), one thread per 16-byte channel group (8 fp16 / 4 fp32 channels):
+ * offsets and strides must be multiples of the group and every buffer 16-byte aligned; C is any positive number (a last partial
+ * group goes element by element).  No cap on N or on the map: the grid is capped and strides over the rest.  scale_*, shift_*:
+ * fp32 [C].  The affine + ReLU is ft_scale_shift_act_nhwc_fwd's with FT_ACT_RELU — one fma in fp32, the activation with the same
+ * values for non-finite inputs, one rounding on store — so each activated output carries the bits that kernel would write.
+ *
+ * ft_hourglass_down_fwd reads x [N, H, W, C] once and writes up to three outputs; each is optional (NULL), at least one is given:
+ *   pool  [N, H/2, W/2, C] = max over the 2x2 window (nn.MaxPool2d(2, stride=2): sizes round down, an odd last row or column
+ *                            takes no part); the stored value is one of the four inputs, a NaN in the window is kept
+ *   a_pool[N, H/2, W/2, C] = relu(fma(scale_pool[c], pool, shift_pool[c]))
+ *   a_full[N, H,   W,   C] = relu(fma(scale_full[c], x, shift_full[c])) for ALL pixels, an odd last row or column included
+ * FT_ERR_INVALID_ARG: x NULL, no output, a size <= 0, pool or a_pool with H < 2 or W < 2, an activated output without its scale
+ * and shift, a misaligned view, an unknown dtype, an output that shares bytes with x or with another output (disjoint channel
+ * windows of one buffer — same pointer and stride — do not).  FT_ERR_UNSUPPORTED: 2^31 or more channel groups in a row.
+ *
+ * ft_hourglass_up_fwd: skip [N, H, W, C], low [N, hl, wl, C]:
+ *   sum   = dtype(skip + bilerp_ac(low))      F.upsample(low, size=(H, W), mode='bilinear', align_corners=True) + skip, the
+ *                                             coordinate rule and the fp32 arithmetic of ft_upsample_bilinear_ac_fwd, one rounding
+ *   a_sum = relu(fma(scale[c], sum AS STORED, shift[c]))      optional (NULL): from the rounded value, so that it equals
+ *                                             ft_scale_shift_act_nhwc_fwd run on `sum`, bit for bit
+ * sum is required; it may be the very view `skip` (same pointer, stride and offset: in place), shares no bytes with it otherwise,
+ * and never any with `low`; a_sum shares none with any other view.  FT_ERR_INVALID_ARG as above; FT_ERR_UNSUPPORTED for a side
+ * above 2^24 and for 2^31 or more channel groups in an output row, as for ft_upsample_bilinear_ac_fwd. */
+int ft_hourglass_down_fwd(const void* x, int dtype, int N, int H, int W, int C, int x_cstride, int x_coff, void* pool,
+                          int pool_cstride, int pool_coff, void* a_pool, int apool_cstride, int apool_coff,
+                          const float* scale_pool, const float* shift_pool, void* a_full, int afull_cstride, int afull_coff,
+                          const float* scale_full, const float* shift_full, ft_stream_t stream);
+int ft_hourglass_up_fwd(const void* skip, const void* low, int dtype, int N, int C, int H, int W, int hl, int wl,
+                        int skip_cstride, int skip_coff, int low_cstride, int low_coff, void* sum, int sum_cstride, int sum_coff,
+                        void* a_sum, int asum_cstride, int asum_coff, const float* scale, const float* shift, ft_stream_t stream);
+
 /* ---- F4: Correlation forward ---------------------------------------------
  * Replaces Correlation_forward_cuda (correlation_package/src/correlation_cuda.c:11-93,
  * kernels correlation_cuda_kernel.cu:10-106).  Same parameters and output

@@ -1,5 +1,6 @@
 """Per-launch timing of a whole plan (dev tool): python tools/dev/net_bench.py FlowNet2C 16 384 512 fp16
-(pose nets: resnet50 = ResNet-50 + deconv head, fpn_resnet50 = ResNet-50 + FPN head, pose_resnet50 = ResNet-50 + lateral-deconv head)"""
+(pose nets: resnet50 = ResNet-50 + deconv head, fpn_resnet50 = ResNet-50 + FPN head, pose_resnet50 = ResNet-50 + lateral-deconv head,
+hg8 = 8 stacked hourglasses; NB_FUSE_SEAMS=0 records the hourglass's level seams unfused)"""
 import sys, os, types
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -7,7 +8,13 @@ import torch
 from flowtrack.pytorch_amd import synth
 name, B, H, W, dt = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), sys.argv[5]
 dtype = torch.float16 if dt == "fp16" else torch.float32
-if name.startswith(("resnet", "fpn_resnet", "pose_resnet")):      # resnet50 = the deconv head, fpn_resnet50 = the FPN head, pose_resnet50 = the lateral-deconv head
+if name.startswith("hg"):        # hg8 = models.hg(17, num_stacks=8)
+    from flowtrack.pytorch_amd.pose import models
+    m = models.hg(17, int(name[2:]))
+    m.fuse_seams = os.environ.get("NB_FUSE_SEAMS", "1") != "0"
+    m.load_state_dict(synth.fill_hg_state_dict(m.state_dict(), 1))
+    x = synth.pose_crops(1, B, H, W)
+elif name.startswith(("resnet", "fpn_resnet", "pose_resnet")):      # resnet50 = the deconv head, fpn_resnet50 = the FPN head, pose_resnet50 = the lateral-deconv head
     from flowtrack.pytorch_amd.pose import models
     m = models.fpn(name[4:], 17, False) if name.startswith("fpn_") else models.pose(name[5:], 17, False) if name.startswith("pose_") else models.deconv(name, 17, False)
     m.load_state_dict(synth.fill_pose_state_dict(m.state_dict(), 1))

@@ -97,6 +97,11 @@ def validate(model, batches, flip_test=False, adjust_coords=True, flip_pairs=COC
             model.flip_pairs = saved_pairs
 
 
+def _last_stack(output):
+    """A stacked model (models.hg) returns one heat-map tensor per stack: the prediction is the last (the reference reads [-1])."""
+    return output[-1] if isinstance(output, (list, tuple)) else output
+
+
 def _validate_loop(model, batches, flip_test, fused_flip, adjust_coords, flip_pairs, rank, world, device, on_gpu, preds_fn):
     from flowtrack.pytorch_amd import parallel
     all_preds, all_scores, all_idx = [], [], []
@@ -110,9 +115,9 @@ def _validate_loop(model, batches, flip_test, fused_flip, adjust_coords, flip_pa
             if fused_flip:
                 output = model.forward_flip(x)
             else:
-                output = model(x)
+                output = _last_stack(model(x))
             if flip_test and not fused_flip:
-                flipped = _flip_back(model(torch.flip(x, dims=[3])), flip_pairs)
+                flipped = _flip_back(_last_stack(model(torch.flip(x, dims=[3]))), flip_pairs)
                 output = (output + flipped) * 0.5
             preds, scores = preds_fn(output, center, scale, adjust_coords)
             rows = torch.from_numpy(np.concatenate((np.asarray(preds, np.float64), np.asarray(scores, np.float64)), axis=2))
@@ -144,11 +149,15 @@ def main(**kwargs):
     opt.work_dir = os.path.join(opt.checkpoint_path, opt.dataset, opt.exp_id)
     num_classes = num_joints[opt.dataset] + (1 if opt.with_bg else 0)
     print("==> creating model '{}', backbone = {}".format(opt.model, opt.backbone))
-    if opt.model not in ('deconv', 'fpn'):
-        raise ValueError("only model='deconv' (ResNet + 3-deconv head) and model='fpn' (ResNet + FPN head) are on the HIP path; "
-                         "got '{}'".format(opt.model))
-    model = getattr(models, opt.model)(opt.backbone, num_classes=num_classes, pretrained=opt.pretrained)
-    opt.model_name = '{}_{}'.format(opt.model, opt.backbone)
+    if opt.model not in ('deconv', 'fpn', 'hg'):
+        raise ValueError("only model='deconv' (ResNet + 3-deconv head), model='fpn' (ResNet + FPN head) and model='hg' (8 stacked "
+                         "hourglasses) are on the HIP path; got '{}'".format(opt.model))
+    if opt.model == 'hg':       # the reference's main.py:69-72: no backbone, 8 stacks
+        model = models.hg(num_classes=num_classes, num_stacks=8)
+        opt.model_name = 'hg'
+    else:
+        model = getattr(models, opt.model)(opt.backbone, num_classes=num_classes, pretrained=opt.pretrained)
+        opt.model_name = '{}_{}'.format(opt.model, opt.backbone)
     if not opt.use_gpu:
         raise ValueError('the HIP path needs use_gpu=True (CPU reference results: oracle/)')
     # one process per GPU under torchrun (RANK / LOCAL_RANK / WORLD_SIZE): the batches are sharded in validate()
