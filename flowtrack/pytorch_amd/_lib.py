@@ -165,6 +165,14 @@ _PROTOTYPES = {
     "ft_track_select": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float] + [c_int] * 5
                         + [c_void_p] * 8),
     "ft_track_place_rows": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p, c_void_p]),
+    "ft_box_nms_workspace_bytes": (ctypes.c_longlong, [c_int]),
+    "ft_box_nms": (c_int, [c_void_p, c_int, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ft_roi_pool_fwd": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_float, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "ft_roi_pool_bwd": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p, c_void_p]),
+    "ft_crop_and_resize_fwd": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_float, c_void_p, c_void_p]),
+    "ft_crop_and_resize_bwd": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p, c_void_p]),
+    "ft_roi_crop_nhwc_fwd": (c_int, [c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_float, c_int, c_int, c_void_p, c_void_p]),
+    "ft_rpn_decode_boxes": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p]),
 }
 
 # declared only under FT_EXPERIMENTAL in the header: measured alternatives the default plans do not record (tests / tools/dev reach them)

@@ -717,6 +717,70 @@ int ft_track_select(const float* dets, const float* kp_det, int n, const float* 
 int ft_track_place_rows(const float* rows, const float* boxes, const int32_t* prop_slot, const int32_t* nprop, int bucket,
                         int cap, int K, int h, int w, int rh, int rw, float* kps, ft_stream_t stream);
 
+/* ---- the detector's region stage (csrc/detect_ops.hip) --------------------------------------------------------
+ * What lies between the RPN's two output maps and the tensor layer4 consumes (reference lib/detection: nms/,
+ * layer_utils/roi_pooling, layer_utils/roi_align, model/bbox_transform.py, nets/network.py:93-121).  Every entry is
+ * asynchronous on `stream`, launches nothing on refused arguments, and returns FT_OK without a launch for zero boxes /
+ * RoIs.  FT_ERR_UNSUPPORTED when an element count (input, output or workspace) reaches 2^31.  All float arithmetic is
+ * fp32 with every operation rounded separately (no FMA contraction), IEEE division.  Indices read from device data (a
+ * RoI's batch index, box_ind, a stored arg-max) are range-checked in the kernels before they address anything. */
+
+/* ft_box_nms — greedy box NMS of dets float[n*5] = (x1, y1, x2, y2, score), ALREADY in score-descending order
+ * (nms/pth_nms.py:33-36 sorts first).  Step 1: the pairwise bit mask in 64 x 64 tiles on or above the diagonal, IoU as
+ * devIoU of nms/src/cuda/nms_kernel.cu:16-24 (+1 widths, Sa + Sb - inter in that order).  Step 2: the sweep of
+ * nms/src/nms_cuda.c:47-58 as one single-workgroup launch on the device (the reference copies the mask to the host):
+ * box i is kept iff no earlier kept box marked it; it stops after max_keep survivors (max_keep <= 0: no cap).
+ * inclusive = 0 suppresses on IoU > thresh (the CUDA path the reference's detector runs), 1 on IoU >= thresh
+ * (nms/src/nms.c:59; the same float expressions).  keep int32[n]: indices into dets in kept order, -1 past *count.
+ * workspace: ft_box_nms_workspace_bytes(n) bytes (0 for n outside [1, 16384]), contents undefined before and after.
+ * n = 0: FT_OK, nothing is written.  n > 16384: FT_ERR_UNSUPPORTED. */
+long long ft_box_nms_workspace_bytes(int n);
+int ft_box_nms(const float* dets, int n, float thresh, int inclusive, int max_keep, void* workspace, int32_t* keep,
+               int32_t* count, ft_stream_t stream);
+
+/* ft_roi_pool_fwd / _bwd — layer_utils/roi_pooling/src/cuda/roi_pooling_kernel.cu:15-75: features float[B,C,H,W],
+ * rois float[R*5] = (batch, x1, y1, x2, y2) in image pixels -> out float[R,C,ph,pw], argmax int32 of the same shape (may
+ * be NULL in fwd).  Corners are round(v * spatial_scale), half away from zero; a malformed RoI is 1 x 1; bins are clipped
+ * to the map; an empty bin gives 0 with arg-max -1; the max is a strict >, so the first occurrence in (h, w) row-major
+ * order wins; the arg-max is the index inside the image, (c*H + h)*W + w.  Two deliberate departures from the reference:
+ *   - a RoI whose batch index is outside [0, B) yields zeros / -1 (the reference reads out of bounds);
+ *   - backward routes each grad_out element to the arg-max element of the RoI's OWN image (the reference's `== index`
+ *     at :170 compares an in-image index with a global one and is right for image 0 only).
+ * Backward zero-fills grad_in float[B,C,H,W] and scatters with float atomics, one per pooled element (an arg-max outside
+ * [0, C*H*W) is skipped): sums of several RoIs on one element can differ in the last bits from run to run; it is
+ * bit-reproducible where every such sum is exact (one contribution, or integer-valued gradients). */
+int ft_roi_pool_fwd(const float* features, const float* rois, int B, int C, int H, int W, int R, float spatial_scale,
+                    int pooled_h, int pooled_w, float* out, int32_t* argmax, ft_stream_t stream);
+int ft_roi_pool_bwd(const float* grad_out, const float* rois, const int32_t* argmax, int B, int C, int H, int W, int R,
+                    int pooled_h, int pooled_w, float* grad_in, ft_stream_t stream);
+
+/* ft_crop_and_resize_fwd / _bwd — layer_utils/roi_align/src/cuda/crop_and_resize_kernel.cu:10-82, :84-165: image
+ * float[B,C,H,W], boxes float[R*4] = normalised (y1, x1, y2, x2), box_ind int32[R] -> out float[R,C,crop_h,crop_w].
+ * A crop dimension > 1 samples at y1*(H-1) + y*((y2-y1)*(H-1)/(crop_h-1)), a dimension of 1 at the centre
+ * 0.5*(y1+y2)*(H-1); extrapolation_value where a sample leaves [0, H-1] / [0, W-1]; floor / ceil neighbours;
+ * top + (bottom - top)*y_lerp with the x-lerps formed first; flipped boxes are allowed; a box whose box_ind is outside
+ * [0, B) yields an all-zero crop.  Backward is the image gradient only: the entry zero-fills grad_image float[B,C,H,W]
+ * and adds with float atomics, as the reference does: NOT bit-reproducible in general. */
+int ft_crop_and_resize_fwd(const float* image, const float* boxes, const int32_t* box_ind, int B, int C, int H, int W, int R,
+                           int crop_h, int crop_w, float extrapolation_value, float* out, ft_stream_t stream);
+int ft_crop_and_resize_bwd(const float* grad_out, const float* boxes, const int32_t* box_ind, int B, int C, int H, int W, int R,
+                           int crop_h, int crop_w, float* grad_image, ft_stream_t stream);
+
+/* ft_roi_crop_nhwc_fwd — the inference form of Network._crop_pool_layer (nets/network.py:93-121) on dense NHWC features
+ * [B,H,W,C], dtype FT_F16 or FT_F32, 16-byte aligned, C % 8 == 0 and H, W >= 2 (FT_ERR_INVALID_ARG otherwise):
+ * rois float[R*5] in image pixels, (int)rois[.][0] the image; x / feat_stride, then / (W-1) and / (H-1), then the
+ * crop arithmetic above at `pooled` (max_pool = 0; ResNet) or at 2*pooled followed by a 2 x 2 max (max_pool = 1; VGG),
+ * extrapolation value 0.  Interpolation and the max run in fp32, rounded once on the store.  out [R,pooled,pooled,C] in
+ * the input dtype: the N = R, Hi = Wi = pooled input of ft_conv2d_fwd.  An image index outside [0, B) yields zeros. */
+int ft_roi_crop_nhwc_fwd(int dtype, const void* features, const float* rois, int B, int H, int W, int C, int R,
+                         float feat_stride, int pooled, int max_pool, void* out, ft_stream_t stream);
+
+/* ft_rpn_decode_boxes — bbox_transform_inv + clip_boxes (model/bbox_transform.py:35-80) in one pass: anchors float[A*4],
+ * deltas float[A*4] (dx, dy, dw, dh) -> boxes float[A*4] clipped to [0, im_w - 1] x [0, im_h - 1]; expf, no fast-math
+ * form.  The three arrays are 16-byte aligned. */
+int ft_rpn_decode_boxes(const float* anchors, const float* deltas, int A, float im_h, float im_w, float* boxes,
+                        ft_stream_t stream);
+
 /* ---- experimental entry points (NOT part of the drop-in boundary) -------------------------------------------
  * Measured alternatives of the fused-block kernels that the default plans do not record (profiles/README.md has their
  * numbers).  They are exported by the library so that the tests and tools/dev can reach them, but they are declared only
