@@ -173,6 +173,11 @@ _PROTOTYPES = {
     "ft_crop_and_resize_bwd": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p, c_void_p]),
     "ft_roi_crop_nhwc_fwd": (c_int, [c_int, c_void_p, c_void_p] + [c_int] * 5 + [c_float, c_int, c_int, c_void_p, c_void_p]),
     "ft_rpn_decode_boxes": (c_int, [c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p]),
+    "ft_detect_blob_fwd": (c_int, [c_void_p, c_int, c_int, POINTER(c_double), c_int, c_int, c_double, c_double, c_void_p, c_void_p]),
+    "ft_rpn_softmax_fwd": (c_int, [c_int, c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ft_rcnn_mean_pool_fwd": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ft_rcnn_detections_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_float), POINTER(c_float), c_float, c_float,
+                                       c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 # declared only under FT_EXPERIMENTAL in the header: measured alternatives the default plans do not record (tests / tools/dev reach them)

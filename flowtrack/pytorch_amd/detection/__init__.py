@@ -1,2 +1,3 @@
-"""The person detector's region stage on the HIP path: box NMS, RoI pooling, crop_and_resize, the proposal layer."""
-from . import ops, proposal  # noqa: F401
+"""The person detector on the HIP path: the Faster R-CNN network (nets, test) and its region stage (box NMS, RoI pooling,
+crop_and_resize, the proposal layer)."""
+from . import nets, ops, proposal, test  # noqa: F401

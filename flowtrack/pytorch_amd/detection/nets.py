@@ -1,0 +1,401 @@
+"""The Faster R-CNN person detector of FlowTrack on the HIP path: the Caffe-strided ResNet-50/101/152 trunk, the RPN, the
+region head (layer4 on the RoI crops) and the two FCs, inference only.
+
+Drop-in surface (reference lib/detection: nets/resnet_v1.py: resnetv1, the inference half of nets/network.py: Network):
+    net = resnetv1(num_layers=50); net.create_architecture(num_classes, tag='default', anchor_scales, anchor_ratios)
+    net.state_dict() / load_state_dict(sd) / load_pretrained_cnn(sd) / .cuda() / .eval()
+    net.test_image(image[1,H,W,3] fp32 blob, im_info) -> (cls_score, cls_prob, bbox_pred, rois) as numpy; net._predictions
+    net.extract_head(image) -> net_conv [1,1024,h,w] fp32
+    net.compute_dtype = torch.float32 (the parity mode) / torch.float16, as the pose models switch
+forward(mode='TRAIN') and everything that needs targets or losses raise FlowtrackHipError.
+
+Two plans (hip_ops.Program launch lists, replayed as HIP graphs) per blob shape and dtype:
+    trunk + RPN   pack -> conv1 -> max-pool -> layer1..layer3 -> rpn_net -> the two RPN heads as ONE 1x1 GEMM with 6A outputs ->
+                  fp32 copies of the score and box channels -> ft_rpn_softmax_fwd
+    region head   ft_roi_crop_nhwc_fwd at post_nms_topN rows -> layer4 (N = rows) -> ft_rcnn_mean_pool_fwd -> cls_score_net and
+                  bbox_pred_net as ONE GEMM with 5 * num_classes fp32 outputs
+Between them: detection.proposal.proposal_layer (its one device -> host read: the kept count); rows past that count carry zero
+RoIs and are dropped.  Behind them: ft_rcnn_detections_fwd (class softmax, un-normalised deltas, and for im_detect the boxes).
+
+The blob has any height and width, so every map size follows (n + 2p - k) // s + 1 and odd maps occur at every stage.  The
+recorder below takes a fused form only where the library's query accepts the shape: ft_bottleneck_fwd / ft_bottleneck_stream_fwd
+for identity blocks (bottleneck_fusable), the K-concatenated conv3 + shortcut GEMM (FusedShortcutConv, asked through
+ft_conv_pack_geometry); everything else is plain ft_conv2d_fwd launches and ft_maxpool3x3s2_fwd.  The stem's fused max-pool and
+the stage-exit form have no query that covers odd maps and are not recorded here.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from .. import _lib
+from .._lib import FlowtrackHipError, check
+from ..engine import HipModule
+from ..hip_ops import (ActView, ConvDesc, ConvGeometry, FusedShortcutConv, Program, bottleneck_fusable, bottleneck_prefers_fused,
+                       current_stream_handle, new_act, new_rowpacked_act, record_bottleneck, record_maxpool, record_pack_input)
+from ..params import ActMarker, BatchNormParams, ConvParams, LinearParams
+from ..pose.models import Bottleneck
+from . import proposal
+
+__all__ = ["resnetv1", "BLOCKS", "BBOX_NORMALIZE_STDS", "BBOX_NORMALIZE_MEANS"]
+
+BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
+BBOX_NORMALIZE_STDS = (0.1, 0.1, 0.2, 0.2)      # model/config.py: TRAIN.BBOX_NORMALIZE_STDS
+BBOX_NORMALIZE_MEANS = (0.0, 0.0, 0.0, 0.0)     # TRAIN.BBOX_NORMALIZE_MEANS
+FEAT_STRIDE = 16
+RPN_CHANNELS = 512                               # model/config.py: RPN_CHANNELS
+
+
+def _conv_out(n: int, k: int, s: int, p: int) -> int:
+    return (n + 2 * p - k) // s + 1
+
+
+class _ResNet(nn.Module):
+    """Parameter layout of torchvision's ResNet without avgpool / fc (nets/resnet_v1.py:25-37)."""
+
+    def __init__(self, layers):
+        super().__init__()
+        self.conv1 = ConvParams(3, 64, 7, stride=2, padding=3, bias=False)
+        self.bn1 = BatchNormParams(64)
+        self.relu = ActMarker("relu")
+        self.maxpool = ActMarker("maxpool3x3s2")
+        inplanes = 64
+        for li, (planes, blocks) in enumerate(zip((64, 128, 256, 512), layers), start=1):
+            mods = [Bottleneck(inplanes, planes, 1 if li == 1 else 2)]
+            inplanes = planes * 4
+            mods += [Bottleneck(inplanes, planes) for _ in range(1, blocks)]
+            setattr(self, f"layer{li}", nn.Sequential(*mods))
+
+
+class _TrunkPlan:
+    def __init__(self):
+        self.runs = 0
+        self.heads = {}         # rows -> _HeadPlan
+
+
+class _HeadPlan:
+    def __init__(self):
+        self.runs = 0
+
+
+class resnetv1(HipModule):
+    #: fold each block-0 projection shortcut into its conv3 launch (FusedShortcutConv); FT_FUSE_SHORTCUT=0 / False keeps them apart
+    fuse_shortcut: bool = os.environ.get("FT_FUSE_SHORTCUT", "1") != "0"
+    #: identity blocks as one launch where the library takes the shape, recorded as a choice next to the three convs (the first-call
+    #: benchmark keeps one); FT_FUSE_BOTTLENECK=0 / False keeps three convs, "force" records the one-launch form alone (dev, tests)
+    fuse_bottleneck = os.environ.get("FT_FUSE_BOTTLENECK", "1") != "0"
+    #: overrides of cfg.TEST.RPN_PRE_NMS_TOP_N / RPN_POST_NMS_TOP_N / RPN_NMS_THRESH (None: 6000 / 300 / 0.7)
+    rpn_pre_nms_topN = None
+    rpn_post_nms_topN = None
+    rpn_nms_thresh = None
+
+    def __init__(self, num_layers: int = 50):
+        super().__init__()
+        self._feat_stride = [FEAT_STRIDE]
+        self._num_layers = num_layers
+        self._net_conv_channels = 1024
+        self._fc7_channels = 2048
+        self._predictions = {}
+
+    # -- construction (nets/network.py:286-317, nets/resnet_v1.py:116-129) ---------------------------------------------------
+    def create_architecture(self, num_classes, tag=None, anchor_scales=(8, 16, 32), anchor_ratios=(0.5, 1, 2)):
+        if self._num_layers not in BLOCKS:
+            raise NotImplementedError      # other depths are not supported, as in the reference
+        self._tag = tag
+        self._num_classes = int(num_classes)
+        self._anchor_scales, self._anchor_ratios = tuple(anchor_scales), tuple(anchor_ratios)
+        self._num_anchors = len(self._anchor_scales) * len(self._anchor_ratios)
+        self.resnet = _ResNet(BLOCKS[self._num_layers])
+        self.rpn_net = ConvParams(self._net_conv_channels, RPN_CHANNELS, 3, padding=1)
+        self.rpn_cls_score_net = ConvParams(RPN_CHANNELS, self._num_anchors * 2, 1)
+        self.rpn_bbox_pred_net = ConvParams(RPN_CHANNELS, self._num_anchors * 4, 1)
+        self.cls_score_net = LinearParams(self._fc7_channels, self._num_classes)
+        self.bbox_pred_net = LinearParams(self._fc7_channels, self._num_classes * 4)
+        self.init_weights()
+
+    def init_weights(self):
+        """nets/network.py:393-409: N(0, 0.01) for the head layers, N(0, 0.001) for bbox_pred_net, zero biases."""
+        with torch.no_grad():
+            for m, std in ((self.rpn_net, 0.01), (self.rpn_cls_score_net, 0.01), (self.rpn_bbox_pred_net, 0.01), (self.cls_score_net, 0.01),
+                           (self.bbox_pred_net, 0.001)):
+                m.weight.normal_(0, std)
+                m.bias.zero_()
+        self._invalidate()
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        """nets/network.py:481-487: exactly this net's keys are read, extra ones (an old checkpoint's resnet.fc.*) are ignored; a
+        missing one is a KeyError.  `strict` is accepted for nn.Module's signature and has no effect: the rule above is the reference's
+        and is always the strict load of exactly this net's keys."""
+        return super().load_state_dict({k: state_dict[k] for k in list(self.state_dict())}, strict=True)
+
+    def load_pretrained_cnn(self, state_dict):
+        self.resnet.load_state_dict({k: state_dict[k] for k in list(self.resnet.state_dict())})
+        self._invalidate()
+
+    # -- recording -------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _shortcut_fusable(blk, stride: int, dtype, t2: ActView, x: ActView, y: ActView) -> bool:
+        """True where the library takes blk's conv3 + shortcut as one K-concatenated GEMM for these views (ft_conv_pack_geometry);
+        asked before any weight of the fused layer is folded or packed."""
+        d = ConvDesc()
+        d.dtype = _lib.dtype_code(dtype)
+        d.N, d.Hi, d.Wi = t2.N, t2.H, t2.W
+        d.Cin, d.x_cstride, d.x_coff = blk.conv3.cin, t2.cstride, t2.coff
+        d.Cout, d.kh, d.kw, d.stride, d.pad, d.transposed = blk.conv3.cout, 1, 1, 1, 0, 0
+        d.Ho, d.Wo = t2.H, t2.W
+        d.y_cstride, d.y_coff, d.out_layout = y.cstride, y.coff, _lib.FT_LAYOUT_NHWC
+        d.act = _lib.FT_ACT_RELU
+        d.x2_cin, d.x2_hi, d.x2_wi, d.x2_cstride, d.x2_coff, d.x2_stride = blk.downsample[0].cin, x.H, x.W, x.cstride, x.coff, stride
+        return _lib.load().ft_conv_pack_geometry(ctypes.byref(d), ctypes.byref(ConvGeometry())) == 0
+
+    def _record_block(self, prog, name: str, blk, stride: int, cur: ActView, dtype, device, fallbacks: list) -> ActView:
+        """One Caffe-strided Bottleneck from view `cur`: conv1 and the shortcut carry `stride`, conv2 has stride 1
+        (nets/resnet_v1.py:30-35).  Returns the output view; `fallbacks` collects the blocks recorded as plain launches."""
+        N, mk = cur.N, dict(dtype=dtype, device=device)
+        planes = blk.conv1.cout
+        Ho, Wo = _conv_out(cur.H, 1, stride, 0), _conv_out(cur.W, 1, stride, 0)
+        c1 = self.fused(name + ".conv1", blk.conv1.weight, stride=stride, bn=blk.bn1.as_dict(), act="relu", **mk)
+        c2 = self.fused(name + ".conv2", blk.conv2.weight, stride=1, pad=1, bn=blk.bn2.as_dict(), act="relu", **mk)
+        c3 = self.fused(name + ".conv3", blk.conv3.weight, bn=blk.bn3.as_dict(), act="relu", **mk)
+        out = new_act(N, Ho, Wo, planes * 4, dtype, device)
+        t1 = new_act(N, Ho, Wo, planes, dtype, device)
+        t2 = new_act(N, Ho, Wo, planes, dtype, device)
+        if not len(blk.downsample):
+            def conv_form():
+                c1.record(prog, cur, t1)
+                c2.record(prog, t1, t2)
+                c3.record(prog, t2, out, residual=cur)
+            if self.fuse_bottleneck == "force" and bottleneck_fusable(c1, c2, c3, cur, out):
+                record_bottleneck(prog, c1, c2, c3, cur, out, name + ".fused", form="patch")
+            elif self.fuse_bottleneck and bottleneck_fusable(c1, c2, c3, cur, out):
+                forms = (("fused", lambda: record_bottleneck(prog, c1, c2, c3, cur, out, name + ".fused", form="patch")), ("convs", conv_form))
+                if not bottleneck_prefers_fused(cur, planes):
+                    forms = forms[::-1]
+                prog.begin_choice(f"bottleneck|{N},{cur.H},{cur.W},{cur.C},{planes},{cur.cstride},{out.cstride}")
+                for form_name, form in forms:
+                    prog.option(form_name)
+                    form()
+                prog.end_choice()
+            else:
+                if self.fuse_bottleneck and dtype == torch.float16:
+                    fallbacks.append(name)
+                conv_form()
+            return out
+        c1.record(prog, cur, t1)
+        c2.record(prog, t1, t2)
+        sc = None
+        if self.fuse_shortcut:
+            if self._shortcut_fusable(blk, stride, dtype, t2, cur, out):
+                key = (name + ".conv3+downsample", dtype, str(device))
+                sc = self._layers.get(key)
+                if sc is None:
+                    sc = self._layers[key] = FusedShortcutConv(blk.conv3.weight, blk.bn3.as_dict(), blk.downsample[0].weight,
+                                                               blk.downsample[1].as_dict(), stride, dtype=dtype, device=device, act="relu",
+                                                               label=name + ".conv3+downsample")
+            else:
+                fallbacks.append(name)
+        if sc is not None:
+            sc.record(prog, t2, cur, out)
+        else:
+            ds = self.fused(name + ".downsample", blk.downsample[0].weight, stride=stride, bn=blk.downsample[1].as_dict(), act=None, **mk)
+            res = new_act(N, Ho, Wo, planes * 4, dtype, device)
+            ds.record(prog, cur, res)
+            c3.record(prog, t2, out, residual=res)
+        return out
+
+    def _record_layer(self, prog, li: int, cur: ActView, dtype, device, fallbacks: list) -> ActView:
+        for bi, blk in enumerate(getattr(self.resnet, f"layer{li}")):
+            stride = 2 if (bi == 0 and li in (2, 3)) else 1          # layer4.0 has stride 1 throughout (resnet_v1.py:33-35)
+            cur = self._record_block(prog, f"resnet.layer{li}.{bi}", blk, stride, cur, dtype, device, fallbacks)
+        return cur
+
+    def _build_trunk(self, H: int, W: int, device, dtype) -> _TrunkPlan:
+        A, mk = self._num_anchors, dict(dtype=dtype, device=device)
+        plan = _TrunkPlan()
+        prog = plan.prog = Program(self._side_stream(device))
+        plan.x_static = torch.zeros((1, 3, H, W), dtype=torch.float32, device=device)
+        plan.fallbacks = []
+        a_in = new_rowpacked_act(1, H, W, 3, 3, dtype, device)
+        record_pack_input(prog, plan.x_static, a_in)
+        r = self.resnet
+        stem = self.fused("resnet.conv1", r.conv1.weight, stride=2, pad=3, bn=r.bn1.as_dict(), act="relu", **mk)
+        H1, W1 = _conv_out(H, 7, 2, 3), _conv_out(W, 7, 2, 3)
+        a1 = new_act(1, H1, W1, 64, dtype, device)
+        stem.record(prog, a_in, a1)
+        cur = new_act(1, _conv_out(H1, 3, 2, 1), _conv_out(W1, 3, 2, 1), 64, dtype, device)
+        record_maxpool(prog, a1, cur)
+        for li in (1, 2, 3):
+            cur = self._record_layer(prog, li, cur, dtype, device, plan.fallbacks)
+        if cur.H < 2 or cur.W < 2:
+            raise FlowtrackHipError(f"blob {H}x{W}: the {cur.H}x{cur.W} feature map is too small for the RoI crop (2x2 at least)")
+        plan.net_conv = cur
+        h, w = cur.H, cur.W
+        # RPN (nets/network.py:227-244): 3x3 + bias + ReLU, then both 1x1 heads as one GEMM: channels [0, 2A) scores, [2A, 6A) deltas
+        rpn = self.fused("rpn_net", self.rpn_net.weight, pad=1, bias=self.rpn_net.bias, act="relu", **mk)
+        a_rpn = new_act(1, h, w, RPN_CHANNELS, dtype, device)
+        rpn.record(prog, cur, a_rpn)
+        heads = self.fused("rpn_cls_score_net+rpn_bbox_pred_net", torch.cat((self.rpn_cls_score_net.weight, self.rpn_bbox_pred_net.weight), 0),
+                           bias=torch.cat((self.rpn_cls_score_net.bias, self.rpn_bbox_pred_net.bias), 0), act=None, **mk)
+        a_out = new_act(1, h, w, 6 * A, dtype, device)
+        heads.record(prog, a_rpn, a_out)
+        code = _lib.dtype_code(dtype)
+        plan.rpn_cls_score = torch.zeros((1, h, w, 2 * A), dtype=torch.float32, device=device)
+        plan.rpn_bbox_pred = torch.zeros((1, h, w, 4 * A), dtype=torch.float32, device=device)
+        plan.rpn_cls_prob = torch.zeros((1, h, w, 2 * A), dtype=torch.float32, device=device)
+        # the fp32 [h*w, C] copies the proposal layer reads: NHWC channel windows as "NCHW" of h*w images of one pixel
+        prog.add("ft_unpack_nhwc_to_nchw", a_out.t.data_ptr(), plan.rpn_cls_score.data_ptr(), h * w, 2 * A, 1, 1, a_out.cstride, 0, code,
+                 keep=(a_out.t, plan.rpn_cls_score))
+        prog.add("ft_unpack_nhwc_to_nchw", a_out.t.data_ptr(), plan.rpn_bbox_pred.data_ptr(), h * w, 4 * A, 1, 1, a_out.cstride, 2 * A, code,
+                 keep=(a_out.t, plan.rpn_bbox_pred))
+        prog.add("ft_rpn_softmax_fwd", code, a_out.t.data_ptr(), ctypes.c_longlong(h * w), A, a_out.cstride, 0, plan.rpn_cls_prob.data_ptr(),
+                 keep=(a_out.t, plan.rpn_cls_prob))
+        anchors, _ = proposal.generate_anchors_pre(h, w, FEAT_STRIDE, self._anchor_scales, self._anchor_ratios)
+        plan.anchors = torch.from_numpy(anchors).to(device)
+        return plan
+
+    def _build_head(self, trunk: _TrunkPlan, rows: int, device, dtype) -> _HeadPlan:
+        K, mk = self._num_classes, dict(dtype=dtype, device=device)
+        plan = _HeadPlan()
+        prog = plan.prog = Program(self._side_stream(device))
+        plan.fallbacks = []
+        plan.rois = torch.zeros((rows, 5), dtype=torch.float32, device=device)
+        feat = trunk.net_conv
+        pool5 = plan.pool5 = new_act(rows, proposal.POOLING_SIZE, proposal.POOLING_SIZE, feat.C, dtype, device)
+        if feat.cstride != feat.C or pool5.cstride != feat.C:
+            raise FlowtrackHipError("the RoI crop works on dense NHWC buffers")
+        prog.add("ft_roi_crop_nhwc_fwd", _lib.dtype_code(dtype), feat.t.data_ptr(), plan.rois.data_ptr(), 1, feat.H, feat.W, feat.C, rows,
+                 ctypes.c_float(FEAT_STRIDE), proposal.POOLING_SIZE, 0, pool5.t.data_ptr(), keep=(feat.t, plan.rois, pool5.t))
+        cur = self._record_layer(prog, 4, pool5, dtype, device, plan.fallbacks)
+        if cur.cstride != cur.C:
+            raise FlowtrackHipError("the mean pool works on dense NHWC buffers")
+        plan.layer4 = cur
+        fc7 = plan.fc7 = new_act(rows, 1, 1, cur.C, dtype, device)
+        prog.add("ft_rcnn_mean_pool_fwd", _lib.dtype_code(dtype), cur.t.data_ptr(), rows, cur.H, cur.C, fc7.t.data_ptr(), keep=(cur.t, fc7.t))
+        fc = self.fused("cls_score_net+bbox_pred_net", torch.cat((self.cls_score_net.weight, self.bbox_pred_net.weight), 0)[:, :, None, None],
+                        bias=torch.cat((self.cls_score_net.bias, self.bbox_pred_net.bias), 0), act=None, **mk)
+        plan.fc_out = torch.zeros((rows, 5 * K, 1, 1), dtype=torch.float32, device=device)
+        fc.record(prog, fc7, plan.fc_out)
+        return plan
+
+    # -- plans -----------------------------------------------------------------------------------------------------------------
+    def trunk_plan(self, H: int, W: int) -> _TrunkPlan:
+        """The trunk + RPN plan of one blob shape (and the current dtype / fuse switches); its x_static [1,3,H,W] fp32 is the staged
+        input ft_detect_blob_fwd writes."""
+        if not hasattr(self, "resnet"):
+            raise FlowtrackHipError("call create_architecture() first")
+        device, dtype = self._resolve()
+        key = (int(H), int(W), device, dtype, bool(self.fuse_shortcut), self.fuse_bottleneck)
+        plan = self._plans.get(key)
+        if plan is None:
+            with torch.no_grad():
+                plan = self._plans[key] = self._build_trunk(int(H), int(W), device, dtype)
+            plan.dtype, plan.device = dtype, device
+        return plan
+
+    def head_plan(self, trunk: _TrunkPlan, rows: int) -> _HeadPlan:
+        plan = trunk.heads.get(rows)
+        if plan is None:
+            with torch.no_grad():
+                plan = trunk.heads[rows] = self._build_head(trunk, rows, trunk.device, trunk.dtype)
+        return plan
+
+    def _run(self, plan) -> None:
+        self._run_plan(plan.prog, first=plan.runs == 0)
+        plan.runs += 1
+
+    # -- inference -------------------------------------------------------------------------------------------------------------
+    def _stage(self, image) -> _TrunkPlan:
+        """image: the reference's blob, [1,H,W,3] fp32 (numpy or tensor) -> its plan with x_static filled."""
+        t = torch.from_numpy(np.ascontiguousarray(image)) if isinstance(image, np.ndarray) else image
+        if t.dim() != 4 or t.shape[0] != 1 or t.shape[3] != 3:
+            raise FlowtrackHipError(f"expected a [1,H,W,3] blob (single image, as model/test.py:90), got {tuple(t.shape)}")
+        plan = self.trunk_plan(t.shape[1], t.shape[2])
+        plan.x_static.copy_(t.to(plan.x_static.device).permute(0, 3, 1, 2))
+        return plan
+
+    @torch.no_grad()
+    def detect_staged(self, plan: _TrunkPlan, im_info, frame_shape=None, keep_intermediates: bool = False) -> dict:
+        """Everything behind the staged input: fills and returns self._predictions (device tensors, fp32, the reference's layouts).
+        frame_shape (h, w) of the original frame adds `pred_boxes` [R,4K] (model/test.py:97-104)."""
+        self._check_eval()
+        K, A = self._num_classes, self._num_anchors
+        im_info = [float(v) for v in np.asarray(im_info, dtype=np.float64).reshape(-1)[:3]]
+        self._run(plan)
+        rois, _ = proposal.proposal_layer(plan.rpn_cls_prob, plan.rpn_bbox_pred, im_info, "TEST", self._feat_stride[0], plan.anchors, A,
+                                          pre_nms_topN=self.rpn_pre_nms_topN, post_nms_topN=self.rpn_post_nms_topN,
+                                          nms_thresh=self.rpn_nms_thresh)
+        p = self._predictions = {"rpn_cls_score": plan.rpn_cls_score.clone(), "rpn_cls_prob": plan.rpn_cls_prob.clone(),
+                                 "rpn_bbox_pred": plan.rpn_bbox_pred.clone(), "rois": rois}
+        if keep_intermediates:
+            p["net_conv"] = plan.net_conv.t[..., :plan.net_conv.C].permute(0, 3, 1, 2).float().contiguous()
+        p.update(self.region_head(plan, rois, im_info[2], frame_shape, keep_intermediates))
+        return p
+
+    @torch.no_grad()
+    def region_head(self, plan: _TrunkPlan, rois: torch.Tensor, im_scale: float = 1.0, frame_shape=None, keep_intermediates: bool = False) -> dict:
+        """The region head on `rois` [n,5] (blob pixels) against the plan's current net_conv: cls_score, cls_pred, cls_prob and the
+        un-normalised bbox_pred, (+ pred_boxes with frame_shape, + pool5 / fc7 with keep_intermediates)."""
+        K = self._num_classes
+        device = plan.device
+        n = int(rois.shape[0])
+        rows = max(RPN_POST_DEFAULT if self.rpn_post_nms_topN is None else int(self.rpn_post_nms_topN), n, 1)
+        hp = self.head_plan(plan, rows)
+        hp.rois.zero_()
+        hp.rois[:n].copy_(rois)
+        self._run(hp)
+        fc = hp.fc_out.view(rows, 5 * K)
+        out = {"cls_score": fc[:n, :K].contiguous(), "bbox_pred": torch.empty((n, 4 * K), dtype=torch.float32, device=device),
+               "cls_prob": torch.empty((n, K), dtype=torch.float32, device=device)}
+        raw = fc[:n, K:].contiguous()
+        boxes = torch.empty((n, 4 * K), dtype=torch.float32, device=device) if frame_shape is not None else None
+        fh, fw = (float(frame_shape[0]), float(frame_shape[1])) if frame_shape is not None else (1.0, 1.0)
+        rois_c = rois.contiguous()
+        with torch.cuda.device(device):
+            check(_lib.load().ft_rcnn_detections_fwd(out["cls_score"].data_ptr(), raw.data_ptr(), rois_c.data_ptr(), n, K,
+                                                     (ctypes.c_float * 4)(*BBOX_NORMALIZE_STDS), (ctypes.c_float * 4)(*BBOX_NORMALIZE_MEANS),
+                                                     float(im_scale), fh, fw, out["cls_prob"].data_ptr(), out["bbox_pred"].data_ptr(),
+                                                     boxes.data_ptr() if boxes is not None else None, current_stream_handle(device)),
+                  "ft_rcnn_detections_fwd")
+        out["cls_pred"] = out["cls_score"].argmax(1) if n else torch.empty(0, dtype=torch.long, device=device)
+        if boxes is not None:
+            out["pred_boxes"] = boxes
+        if keep_intermediates:
+            out["pool5"] = hp.pool5.t[:n].permute(0, 3, 1, 2).float().contiguous()
+            out["fc7"] = hp.fc7.t[:n, 0, 0, :].float().contiguous()
+        return out
+
+    def forward(self, image, im_info, gt_boxes=None, mode="TRAIN", keep_intermediates: bool = False):
+        if mode != "TEST" or gt_boxes is not None:
+            raise FlowtrackHipError("resnetv1: only mode='TEST' without gt_boxes runs on the HIP path (targets and losses are out of scope)")
+        self.detect_staged(self._stage(image), im_info, None, keep_intermediates)
+
+    def test_image(self, image, im_info, keep_intermediates: bool = False):
+        """nets/network.py:418-425: (cls_score [R,K], cls_prob [R,K], bbox_pred [R,4K], rois [R,5]) as numpy."""
+        self.eval()
+        self.forward(image, im_info, None, mode="TEST", keep_intermediates=keep_intermediates)
+        p = self._predictions
+        return tuple(p[k].cpu().numpy() for k in ("cls_score", "cls_prob", "bbox_pred", "rois"))
+
+    @torch.no_grad()
+    def extract_head(self, image) -> torch.Tensor:
+        """nets/network.py:413-415: net_conv [1,1024,h,w] fp32 of a [1,H,W,3] blob."""
+        self._check_eval()
+        plan = self._stage(image)
+        self._run(plan)
+        return plan.net_conv.t[..., :plan.net_conv.C].permute(0, 3, 1, 2).float().contiguous()
+
+    # -- what the HIP path does not have ---------------------------------------------------------------------------------------
+    def _no_training(self, *a, **k):
+        raise FlowtrackHipError("resnetv1: training steps, losses and summaries are out of scope on the HIP path")
+
+    train_step = train_step_with_summary = train_step_no_return = get_summary = _add_losses = _no_training
+
+    def delete_intermediate_states(self):
+        self._predictions = {}
+
+
+RPN_POST_DEFAULT = proposal.RPN_DEFAULTS["TEST"][1]

@@ -47,6 +47,20 @@ class ConvTransposeParams(_Holder):
         return f"{self.cin}, {self.cout}, k=4, s=2, p=1, bias={self.bias is not None}"
 
 
+class LinearParams(_Holder):
+    """Stands where nn.Linear sits in the reference (weight [out, in], bias [out])."""
+
+    def __init__(self, cin: int, cout: int):
+        super().__init__()
+        self.cin, self.cout = cin, cout
+        self.weight = nn.Parameter(torch.empty(cout, cin))
+        self.bias = nn.Parameter(torch.empty(cout))
+        _default_conv_init(self.weight, self.bias, cin)
+
+    def extra_repr(self):
+        return f"{self.cin}, {self.cout}"
+
+
 class BatchNormParams(_Holder):
     """Stands where nn.BatchNorm2d sits: weight, bias, running_mean, running_var, num_batches_tracked."""
 

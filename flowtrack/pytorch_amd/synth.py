@@ -165,6 +165,53 @@ def fill_hg_state_dict(sd: Dict[str, torch.Tensor], seed: int) -> Dict[str, torc
     return out
 
 
+#: gains of fill_detector_state_dict: the block-closing BatchNorms of the trunk, and the He-style gains (std = sqrt(gain / fan_in)) of
+#: the detector's head layers, chosen so that no softmax saturates and every box delta stays below 1 (tests/golden/make_detect_net_golden.py
+#: checks the conditions on the reference's own run)
+DET_BN_LAST = (0.1, 0.25)
+DET_HEAD_GAINS = {"rpn_net": 2.0, "rpn_cls_score_net": 1.0, "rpn_bbox_pred_net": 0.008, "cls_score_net": 8.0, "bbox_pred_net": 4.0}
+
+
+def fill_detector_state_dict(sd: Dict[str, torch.Tensor], seed: int) -> Dict[str, torch.Tensor]:
+    """Weights for a detection.nets.resnetv1 state_dict: the trunk as fill_pose_state_dict fills it, with smaller gains on the
+    BatchNorms that close a block (13 residual blocks feed net_conv with no normalisation behind them); the five head layers
+    (`rpn_*`, `cls_score_net`, `bbox_pred_net`; two of them Linear, whose 2-D weights are NOT BatchNorm gains) N(0, gain / fan_in)
+    with DET_HEAD_GAINS and small biases."""
+    out = {}
+    for k, v in sd.items():
+        shape = tuple(v.shape)
+        head = k.split(".")[0]
+        if k.endswith("num_batches_tracked"):
+            out[k] = torch.tensor(0, dtype=torch.long)
+        elif k.endswith("running_mean"):
+            out[k] = normal(seed, k, shape, std=0.1)
+        elif k.endswith("running_var"):
+            out[k] = uniform(seed, k, shape, 0.5, 1.5)
+        elif head in DET_HEAD_GAINS:
+            if k.endswith(".weight"):
+                out[k] = normal(seed, k, shape, std=float(np.sqrt(DET_HEAD_GAINS[head] / int(np.prod(shape[1:])))))
+            else:
+                out[k] = normal(seed, k, shape, std=0.05)
+        elif v.dim() == 4:
+            out[k] = normal(seed, k, shape, std=float(np.sqrt(2.0 / _fan_in(k, shape, False))))
+        elif k.endswith(".weight"):  # BN gamma
+            last = ".bn3." in k or ".downsample.1." in k
+            out[k] = uniform(seed, k, shape, *DET_BN_LAST) if last else uniform(seed, k, shape, 0.5, 1.5)
+        elif k.endswith(".bias"):
+            out[k] = normal(seed, k, shape, std=0.1)
+        else:
+            raise KeyError(k)
+    return out
+
+
+def detector_frame(seed: int, H: int, W: int) -> np.ndarray:
+    """uint8 [H,W,3] BGR: a smooth random texture (8 x 8 blocks, 70 %) under fine noise (30 %), as frame_pairs builds its frames."""
+    lo = uniform01(seed, "det_frame_lo", (H // 8 + 2, W // 8 + 2, 3))
+    base = np.kron(lo, np.ones((8, 8, 1)))[:H, :W]
+    fine = uniform01(seed, "det_frame_fine", (H, W, 3))
+    return np.clip(np.floor(255.0 * (0.7 * base + 0.3 * fine)), 0, 255).astype(np.uint8)
+
+
 def fill_flow_state_dict(sd: Dict[str, torch.Tensor], seed: int) -> Dict[str, torch.Tensor]:
     """He-scaled (LeakyReLU 0.1) conv / deconv weights and small biases for a FlowNet2* state_dict."""
     out = {}

@@ -781,6 +781,40 @@ int ft_roi_crop_nhwc_fwd(int dtype, const void* features, const float* rois, int
 int ft_rpn_decode_boxes(const float* anchors, const float* deltas, int A, float im_h, float im_w, float* boxes,
                         ft_stream_t stream);
 
+/* ---- the detector network's glue (reference lib/detection/model/test.py, nets/network.py, nets/resnet_v1.py) -----
+ * csrc/detect_net_ops.hip.  fp32 arithmetic with every operation rounded separately, expf, IEEE division.  A call with zero
+ * rows returns FT_OK without a launch; a refused call launches nothing. */
+
+/* ft_detect_blob_fwd — model/test.py:37-58 (_get_image_blob) + nets/network.py:378: frame u8[H,W,3] (BGR, on the device)
+ * -> blob float[1,3,Hb,Wb], the trunk's staged input.  means double[3] is read on the HOST at call time.  Per pixel and
+ * channel: (float)((double)u8 - mean) (the reference subtracts float64 means into a float32 image), then OpenCV's INTER_LINEAR rule for float images: per axis the source coordinate
+ * (d + 0.5) * scale - 0.5 (double, rounded to float; scale = 1 / f), floor, fraction; weight zeroed and index clamped at
+ * both borders; s0 * (1 - f) + s1 * f along x for the two rows, then along y.  scale 1 is the identity minus the means. */
+int ft_detect_blob_fwd(const uint8_t* frame, int H, int W, const double* means, int Hb, int Wb, double scale_y, double scale_x,
+                       float* blob, ft_stream_t stream);
+
+/* ft_rpn_softmax_fwd — nets/network.py:234-238: scores [rows, x_cstride] (FT_F16 or FT_F32; the 2A score channels start at
+ * x_coff) -> prob float[rows, 2A]: exp(x - max) / sum over each pair (a, a + A). */
+int ft_rpn_softmax_fwd(int dtype, const void* scores, long long rows, int A, int x_cstride, int x_coff, float* prob,
+                       ft_stream_t stream);
+
+/* ft_rcnn_mean_pool_fwd — nets/resnet_v1.py:113 (`.mean(3).mean(2)`): x [R,P,P,C] NHWC (FT_F16 or FT_F32, dense, 16-byte
+ * aligned, C % 8 == 0) -> out [R,C] in the same dtype: per row the sum over x in order divided by P, those means summed over
+ * y in order and divided by P, all in fp32, rounded once on the store. */
+int ft_rcnn_mean_pool_fwd(int dtype, const void* x, int R, int P, int C, void* out, ft_stream_t stream);
+
+/* ft_rcnn_detections_fwd — nets/network.py:270, :386-389 and model/test.py:97-104: cls_score float[R,K], bbox_pred
+ * float[R,4K], rois float[R,5] in blob pixels; stds / means float[4] are read on the HOST at call time.
+ *   cls_prob   float[R,K]   exp(x - max) / sum over the K classes
+ *   deltas     float[R,4K]  bbox_pred * stds + means (per class)
+ *   pred_boxes float[R,4K]  bbox_transform_inv of the deltas against rois[:,1:5] / im_scale, then _clip_boxes to the
+ *                           im_h x im_w frame: x1, y1 are only raised to 0, x2, y2 only lowered to im_w - 1 / im_h - 1
+ * Any K >= 1.  An output pointer may be NULL: that output is skipped (and the inputs only it reads may be NULL too).
+ * bbox_pred, deltas and pred_boxes are 16-byte aligned. */
+int ft_rcnn_detections_fwd(const float* cls_score, const float* bbox_pred, const float* rois, int R, int K, const float* stds,
+                           const float* means, float im_scale, float im_h, float im_w, float* cls_prob, float* deltas,
+                           float* pred_boxes, ft_stream_t stream);
+
 /* ---- experimental entry points (NOT part of the drop-in boundary) -------------------------------------------
  * Measured alternatives of the fused-block kernels that the default plans do not record (profiles/README.md has their
  * numbers).  They are exported by the library so that the tests and tools/dev can reach them, but they are declared only
