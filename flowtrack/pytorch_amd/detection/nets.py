@@ -18,9 +18,9 @@ Between them: detection.proposal.proposal_layer (its one device -> host read: th
 RoIs and are dropped.  Behind them: ft_rcnn_detections_fwd (class softmax, un-normalised deltas, and for im_detect the boxes).
 
 The blob has any height and width, so every map size follows (n + 2p - k) // s + 1 and odd maps occur at every stage.  The
-recorder below takes a fused form only where the library's query accepts the shape: ft_bottleneck_fwd / ft_bottleneck_stream_fwd
-for identity blocks (bottleneck_fusable), the K-concatenated conv3 + shortcut GEMM (FusedShortcutConv, asked through
-ft_conv_pack_geometry); everything else is plain ft_conv2d_fwd launches and ft_maxpool3x3s2_fwd.  The stem's fused max-pool and
+block recorder (resnet.record_block, shared with the pose trunks) takes a fused form only where the library's query accepts the
+shape: ft_bottleneck_fwd / ft_bottleneck_stream_fwd for identity blocks (bottleneck_fusable), the K-concatenated conv3 + shortcut
+GEMM (FusedShortcutConv.supported); everything else is plain ft_conv2d_fwd launches and ft_maxpool3x3s2_fwd.  The stem's fused max-pool and
 the stage-exit form have no query that covers odd maps and are not recorded here.
 """
 from __future__ import annotations
@@ -34,24 +34,18 @@ import torch.nn as nn
 
 from .. import _lib
 from .._lib import FlowtrackHipError, check
-from ..engine import HipModule
-from ..hip_ops import (ActView, ConvDesc, ConvGeometry, FusedShortcutConv, Program, bottleneck_fusable, bottleneck_prefers_fused,
-                       current_stream_handle, new_act, new_rowpacked_act, record_bottleneck, record_maxpool, record_pack_input)
+from ..engine import HipModule, Plan
+from ..hip_ops import ActView, Program, current_stream_handle, new_act, new_rowpacked_act, record_maxpool, record_pack_input
 from ..params import ActMarker, BatchNormParams, ConvParams, LinearParams
-from ..pose.models import Bottleneck
+from ..resnet import BLOCKS, Bottleneck, conv_out, record_block
 from . import proposal
 
 __all__ = ["resnetv1", "BLOCKS", "BBOX_NORMALIZE_STDS", "BBOX_NORMALIZE_MEANS"]
 
-BLOCKS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
 BBOX_NORMALIZE_STDS = (0.1, 0.1, 0.2, 0.2)      # model/config.py: TRAIN.BBOX_NORMALIZE_STDS
 BBOX_NORMALIZE_MEANS = (0.0, 0.0, 0.0, 0.0)     # TRAIN.BBOX_NORMALIZE_MEANS
 FEAT_STRIDE = 16
 RPN_CHANNELS = 512                               # model/config.py: RPN_CHANNELS
-
-
-def _conv_out(n: int, k: int, s: int, p: int) -> int:
-    return (n + 2 * p - k) // s + 1
 
 
 class _ResNet(nn.Module):
@@ -69,17 +63,6 @@ class _ResNet(nn.Module):
             inplanes = planes * 4
             mods += [Bottleneck(inplanes, planes) for _ in range(1, blocks)]
             setattr(self, f"layer{li}", nn.Sequential(*mods))
-
-
-class _TrunkPlan:
-    def __init__(self):
-        self.runs = 0
-        self.heads = {}         # rows -> _HeadPlan
-
-
-class _HeadPlan:
-    def __init__(self):
-        self.runs = 0
 
 
 class resnetv1(HipModule):
@@ -137,99 +120,33 @@ class resnetv1(HipModule):
         self._invalidate()
 
     # -- recording -------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def _shortcut_fusable(blk, stride: int, dtype, t2: ActView, x: ActView, y: ActView) -> bool:
-        """True where the library takes blk's conv3 + shortcut as one K-concatenated GEMM for these views (ft_conv_pack_geometry);
-        asked before any weight of the fused layer is folded or packed."""
-        d = ConvDesc()
-        d.dtype = _lib.dtype_code(dtype)
-        d.N, d.Hi, d.Wi = t2.N, t2.H, t2.W
-        d.Cin, d.x_cstride, d.x_coff = blk.conv3.cin, t2.cstride, t2.coff
-        d.Cout, d.kh, d.kw, d.stride, d.pad, d.transposed = blk.conv3.cout, 1, 1, 1, 0, 0
-        d.Ho, d.Wo = t2.H, t2.W
-        d.y_cstride, d.y_coff, d.out_layout = y.cstride, y.coff, _lib.FT_LAYOUT_NHWC
-        d.act = _lib.FT_ACT_RELU
-        d.x2_cin, d.x2_hi, d.x2_wi, d.x2_cstride, d.x2_coff, d.x2_stride = blk.downsample[0].cin, x.H, x.W, x.cstride, x.coff, stride
-        return _lib.load().ft_conv_pack_geometry(ctypes.byref(d), ctypes.byref(ConvGeometry())) == 0
-
-    def _record_block(self, prog, name: str, blk, stride: int, cur: ActView, dtype, device, fallbacks: list) -> ActView:
-        """One Caffe-strided Bottleneck from view `cur`: conv1 and the shortcut carry `stride`, conv2 has stride 1
-        (nets/resnet_v1.py:30-35).  Returns the output view; `fallbacks` collects the blocks recorded as plain launches."""
-        N, mk = cur.N, dict(dtype=dtype, device=device)
-        planes = blk.conv1.cout
-        Ho, Wo = _conv_out(cur.H, 1, stride, 0), _conv_out(cur.W, 1, stride, 0)
-        c1 = self.fused(name + ".conv1", blk.conv1.weight, stride=stride, bn=blk.bn1.as_dict(), act="relu", **mk)
-        c2 = self.fused(name + ".conv2", blk.conv2.weight, stride=1, pad=1, bn=blk.bn2.as_dict(), act="relu", **mk)
-        c3 = self.fused(name + ".conv3", blk.conv3.weight, bn=blk.bn3.as_dict(), act="relu", **mk)
-        out = new_act(N, Ho, Wo, planes * 4, dtype, device)
-        t1 = new_act(N, Ho, Wo, planes, dtype, device)
-        t2 = new_act(N, Ho, Wo, planes, dtype, device)
-        if not len(blk.downsample):
-            def conv_form():
-                c1.record(prog, cur, t1)
-                c2.record(prog, t1, t2)
-                c3.record(prog, t2, out, residual=cur)
-            if self.fuse_bottleneck == "force" and bottleneck_fusable(c1, c2, c3, cur, out):
-                record_bottleneck(prog, c1, c2, c3, cur, out, name + ".fused", form="patch")
-            elif self.fuse_bottleneck and bottleneck_fusable(c1, c2, c3, cur, out):
-                forms = (("fused", lambda: record_bottleneck(prog, c1, c2, c3, cur, out, name + ".fused", form="patch")), ("convs", conv_form))
-                if not bottleneck_prefers_fused(cur, planes):
-                    forms = forms[::-1]
-                prog.begin_choice(f"bottleneck|{N},{cur.H},{cur.W},{cur.C},{planes},{cur.cstride},{out.cstride}")
-                for form_name, form in forms:
-                    prog.option(form_name)
-                    form()
-                prog.end_choice()
-            else:
-                if self.fuse_bottleneck and dtype == torch.float16:
-                    fallbacks.append(name)
-                conv_form()
-            return out
-        c1.record(prog, cur, t1)
-        c2.record(prog, t1, t2)
-        sc = None
-        if self.fuse_shortcut:
-            if self._shortcut_fusable(blk, stride, dtype, t2, cur, out):
-                key = (name + ".conv3+downsample", dtype, str(device))
-                sc = self._layers.get(key)
-                if sc is None:
-                    sc = self._layers[key] = FusedShortcutConv(blk.conv3.weight, blk.bn3.as_dict(), blk.downsample[0].weight,
-                                                               blk.downsample[1].as_dict(), stride, dtype=dtype, device=device, act="relu",
-                                                               label=name + ".conv3+downsample")
-            else:
-                fallbacks.append(name)
-        if sc is not None:
-            sc.record(prog, t2, cur, out)
-        else:
-            ds = self.fused(name + ".downsample", blk.downsample[0].weight, stride=stride, bn=blk.downsample[1].as_dict(), act=None, **mk)
-            res = new_act(N, Ho, Wo, planes * 4, dtype, device)
-            ds.record(prog, cur, res)
-            c3.record(prog, t2, out, residual=res)
-        return out
-
-    def _record_layer(self, prog, li: int, cur: ActView, dtype, device, fallbacks: list) -> ActView:
+    def _record_layer(self, prog, li: int, cur: ActView, fallbacks: list) -> ActView:
+        """One stage of Caffe-strided Bottlenecks (conv1 and the shortcut carry the stride, nets/resnet_v1.py:30-35) in the forms this
+        host offers: the identity block's one-launch form (alone with fuse_bottleneck = "force"), the shortcut GEMM behind its query,
+        plain launches.  `fallbacks` collects the blocks recorded as plain launches where a fused form was offered."""
+        forms = ((("fused-only" if self.fuse_bottleneck == "force" else "fused"),) if self.fuse_bottleneck else ()) + \
+            (("shortcut-asked",) if self.fuse_shortcut else ())
         for bi, blk in enumerate(getattr(self.resnet, f"layer{li}")):
             stride = 2 if (bi == 0 and li in (2, 3)) else 1          # layer4.0 has stride 1 throughout (resnet_v1.py:33-35)
-            cur = self._record_block(prog, f"resnet.layer{li}.{bi}", blk, stride, cur, dtype, device, fallbacks)
+            cur = record_block(self, prog, f"resnet.layer{li}.{bi}", blk, cur, stride=stride, stride_on="conv1", forms=forms, fallbacks=fallbacks)
         return cur
 
-    def _build_trunk(self, H: int, W: int, device, dtype) -> _TrunkPlan:
+    def _build_trunk(self, H: int, W: int, device, dtype) -> Plan:
         A, mk = self._num_anchors, dict(dtype=dtype, device=device)
-        plan = _TrunkPlan()
-        prog = plan.prog = Program(self._side_stream(device))
+        prog = Program(self._side_stream(device))
+        plan = Plan(prog, dtype=dtype, device=device, fallbacks=[], heads={})         # heads: rows -> the region-head plan
         plan.x_static = torch.zeros((1, 3, H, W), dtype=torch.float32, device=device)
-        plan.fallbacks = []
         a_in = new_rowpacked_act(1, H, W, 3, 3, dtype, device)
         record_pack_input(prog, plan.x_static, a_in)
         r = self.resnet
         stem = self.fused("resnet.conv1", r.conv1.weight, stride=2, pad=3, bn=r.bn1.as_dict(), act="relu", **mk)
-        H1, W1 = _conv_out(H, 7, 2, 3), _conv_out(W, 7, 2, 3)
+        H1, W1 = conv_out(H, 7, 2, 3), conv_out(W, 7, 2, 3)
         a1 = new_act(1, H1, W1, 64, dtype, device)
         stem.record(prog, a_in, a1)
-        cur = new_act(1, _conv_out(H1, 3, 2, 1), _conv_out(W1, 3, 2, 1), 64, dtype, device)
+        cur = new_act(1, conv_out(H1, 3, 2, 1), conv_out(W1, 3, 2, 1), 64, dtype, device)
         record_maxpool(prog, a1, cur)
         for li in (1, 2, 3):
-            cur = self._record_layer(prog, li, cur, dtype, device, plan.fallbacks)
+            cur = self._record_layer(prog, li, cur, plan.fallbacks)
         if cur.H < 2 or cur.W < 2:
             raise FlowtrackHipError(f"blob {H}x{W}: the {cur.H}x{cur.W} feature map is too small for the RoI crop (2x2 at least)")
         plan.net_conv = cur
@@ -257,11 +174,10 @@ class resnetv1(HipModule):
         plan.anchors = torch.from_numpy(anchors).to(device)
         return plan
 
-    def _build_head(self, trunk: _TrunkPlan, rows: int, device, dtype) -> _HeadPlan:
+    def _build_head(self, trunk: Plan, rows: int, device, dtype) -> Plan:
         K, mk = self._num_classes, dict(dtype=dtype, device=device)
-        plan = _HeadPlan()
-        prog = plan.prog = Program(self._side_stream(device))
-        plan.fallbacks = []
+        prog = Program(self._side_stream(device))
+        plan = Plan(prog, fallbacks=[])
         plan.rois = torch.zeros((rows, 5), dtype=torch.float32, device=device)
         feat = trunk.net_conv
         pool5 = plan.pool5 = new_act(rows, proposal.POOLING_SIZE, proposal.POOLING_SIZE, feat.C, dtype, device)
@@ -269,7 +185,7 @@ class resnetv1(HipModule):
             raise FlowtrackHipError("the RoI crop works on dense NHWC buffers")
         prog.add("ft_roi_crop_nhwc_fwd", _lib.dtype_code(dtype), feat.t.data_ptr(), plan.rois.data_ptr(), 1, feat.H, feat.W, feat.C, rows,
                  ctypes.c_float(FEAT_STRIDE), proposal.POOLING_SIZE, 0, pool5.t.data_ptr(), keep=(feat.t, plan.rois, pool5.t))
-        cur = self._record_layer(prog, 4, pool5, dtype, device, plan.fallbacks)
+        cur = self._record_layer(prog, 4, pool5, plan.fallbacks)
         if cur.cstride != cur.C:
             raise FlowtrackHipError("the mean pool works on dense NHWC buffers")
         plan.layer4 = cur
@@ -282,33 +198,20 @@ class resnetv1(HipModule):
         return plan
 
     # -- plans -----------------------------------------------------------------------------------------------------------------
-    def trunk_plan(self, H: int, W: int) -> _TrunkPlan:
+    def trunk_plan(self, H: int, W: int) -> Plan:
         """The trunk + RPN plan of one blob shape (and the current dtype / fuse switches); its x_static [1,3,H,W] fp32 is the staged
         input ft_detect_blob_fwd writes."""
         if not hasattr(self, "resnet"):
             raise FlowtrackHipError("call create_architecture() first")
         device, dtype = self._resolve()
         key = (int(H), int(W), device, dtype, bool(self.fuse_shortcut), self.fuse_bottleneck)
-        plan = self._plans.get(key)
-        if plan is None:
-            with torch.no_grad():
-                plan = self._plans[key] = self._build_trunk(int(H), int(W), device, dtype)
-            plan.dtype, plan.device = dtype, device
-        return plan
+        return self._cached_plan(key, lambda: self._build_trunk(int(H), int(W), device, dtype))
 
-    def head_plan(self, trunk: _TrunkPlan, rows: int) -> _HeadPlan:
-        plan = trunk.heads.get(rows)
-        if plan is None:
-            with torch.no_grad():
-                plan = trunk.heads[rows] = self._build_head(trunk, rows, trunk.device, trunk.dtype)
-        return plan
-
-    def _run(self, plan) -> None:
-        self._run_plan(plan.prog, first=plan.runs == 0)
-        plan.runs += 1
+    def head_plan(self, trunk: Plan, rows: int) -> Plan:
+        return self._cached_plan(rows, lambda: self._build_head(trunk, rows, trunk.device, trunk.dtype), trunk.heads)
 
     # -- inference -------------------------------------------------------------------------------------------------------------
-    def _stage(self, image) -> _TrunkPlan:
+    def _stage(self, image) -> Plan:
         """image: the reference's blob, [1,H,W,3] fp32 (numpy or tensor) -> its plan with x_static filled."""
         t = torch.from_numpy(np.ascontiguousarray(image)) if isinstance(image, np.ndarray) else image
         if t.dim() != 4 or t.shape[0] != 1 or t.shape[3] != 3:
@@ -318,13 +221,13 @@ class resnetv1(HipModule):
         return plan
 
     @torch.no_grad()
-    def detect_staged(self, plan: _TrunkPlan, im_info, frame_shape=None, keep_intermediates: bool = False) -> dict:
+    def detect_staged(self, plan: Plan, im_info, frame_shape=None, keep_intermediates: bool = False) -> dict:
         """Everything behind the staged input: fills and returns self._predictions (device tensors, fp32, the reference's layouts).
         frame_shape (h, w) of the original frame adds `pred_boxes` [R,4K] (model/test.py:97-104)."""
         self._check_eval()
         K, A = self._num_classes, self._num_anchors
         im_info = [float(v) for v in np.asarray(im_info, dtype=np.float64).reshape(-1)[:3]]
-        self._run(plan)
+        self.run(plan)
         rois, _ = proposal.proposal_layer(plan.rpn_cls_prob, plan.rpn_bbox_pred, im_info, "TEST", self._feat_stride[0], plan.anchors, A,
                                           pre_nms_topN=self.rpn_pre_nms_topN, post_nms_topN=self.rpn_post_nms_topN,
                                           nms_thresh=self.rpn_nms_thresh)
@@ -336,7 +239,7 @@ class resnetv1(HipModule):
         return p
 
     @torch.no_grad()
-    def region_head(self, plan: _TrunkPlan, rois: torch.Tensor, im_scale: float = 1.0, frame_shape=None, keep_intermediates: bool = False) -> dict:
+    def region_head(self, plan: Plan, rois: torch.Tensor, im_scale: float = 1.0, frame_shape=None, keep_intermediates: bool = False) -> dict:
         """The region head on `rois` [n,5] (blob pixels) against the plan's current net_conv: cls_score, cls_pred, cls_prob and the
         un-normalised bbox_pred, (+ pred_boxes with frame_shape, + pool5 / fc7 with keep_intermediates)."""
         K = self._num_classes
@@ -346,7 +249,7 @@ class resnetv1(HipModule):
         hp = self.head_plan(plan, rows)
         hp.rois.zero_()
         hp.rois[:n].copy_(rois)
-        self._run(hp)
+        self.run(hp)
         fc = hp.fc_out.view(rows, 5 * K)
         out = {"cls_score": fc[:n, :K].contiguous(), "bbox_pred": torch.empty((n, 4 * K), dtype=torch.float32, device=device),
                "cls_prob": torch.empty((n, K), dtype=torch.float32, device=device)}
@@ -385,7 +288,7 @@ class resnetv1(HipModule):
         """nets/network.py:413-415: net_conv [1,1024,h,w] fp32 of a [1,H,W,3] blob."""
         self._check_eval()
         plan = self._stage(image)
-        self._run(plan)
+        self.run(plan)
         return plan.net_conv.t[..., :plan.net_conv.C].permute(0, 3, 1, 2).float().contiguous()
 
     # -- what the HIP path does not have ---------------------------------------------------------------------------------------

@@ -16,6 +16,15 @@ from . import _lib, hip_ops
 from .hip_ops import FlowtrackHipError, Program, require_gpu
 
 
+class Plan:
+    """What every model host keeps per input shape: the launch list and how often it ran (0: the next run is the eager, validating,
+    benchmarking and capturing one).  The hosts hang their own buffers on it (x_static, heatmaps, out, stages, heads, fallbacks ...)."""
+
+    def __init__(self, prog: Program, **attrs):
+        self.prog, self.runs = prog, 0
+        self.__dict__.update(attrs)
+
+
 class HipModule(nn.Module):
     #: set to torch.float16 / torch.float32 to override the dtype implied by the parameters
     compute_dtype: Optional[torch.dtype] = None
@@ -49,6 +58,17 @@ class HipModule(nn.Module):
         layer = self._layers.get(key)
         if layer is None:
             layer = self._layers[key] = FusedConv(weight, dtype=dtype, device=device, label=label, **kw)
+        return layer
+
+    def fused_shortcut(self, label: str, blk, stride_d: int, *, dtype, device, key_suffix: str = ""):
+        """FusedShortcutConv of `blk` (a resnet.Bottleneck with a projection shortcut read at stride `stride_d`), cached as fused()
+        caches; `key_suffix` tells apart two layers of one label (the stage-exit form reads its shortcut operand at stride 1)."""
+        from .hip_ops import FusedShortcutConv
+        key = (label + key_suffix, dtype, str(device))
+        layer = self._layers.get(key)
+        if layer is None:
+            layer = self._layers[key] = FusedShortcutConv(blk.conv3.weight, blk.bn3.as_dict(), blk.downsample[0].weight,
+                                                          blk.downsample[1].as_dict(), stride_d, dtype=dtype, device=device, act="relu", label=label)
         return layer
 
     def _apply(self, fn, *a, **k):
@@ -104,6 +124,19 @@ class HipModule(nn.Module):
             raise FlowtrackHipError(
                 f"{type(self).__name__}: only the inference path is implemented on HIP — call .eval() "
                 "(training-mode BatchNorm / multi-scale outputs are out of scope, SURVEY §8)")
+
+    def _cached_plan(self, key, build, cache: Optional[dict] = None) -> Plan:
+        """The plan under `key` in `cache` (self._plans unless given), built by build() under no_grad and stored on a miss."""
+        cache = self._plans if cache is None else cache
+        plan = cache.get(key)
+        if plan is None:
+            with torch.no_grad():
+                plan = cache[key] = build()
+        return plan
+
+    def run(self, plan: Plan) -> None:
+        self._run_plan(plan.prog, first=plan.runs == 0)
+        plan.runs += 1
 
     def _run_plan(self, prog: Program, first: bool) -> None:
         """First call: eager run (+ tile benchmark + graph capture) on the plan's private stream, ordered after / before

@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..engine import HipModule
+from ..engine import HipModule, Plan
 from ..hip_ops import (ActView, FlowtrackHipError, FusedConv, Program, act_stride, new_act, new_rowpacked_act,
                        record_upsample4x, round_up)
 from ..params import ActMarker, BatchNormParams, ConvParams, ConvTransposeParams
@@ -433,12 +433,6 @@ FUSE_MEAN_PACK = os.environ.get("FT_FUSE_MEAN_PACK", "0") == "1"
 MEAN_FOLD = os.environ.get("FT_MEAN_FOLD", "1") != "0"
 
 
-class _FlowPlan:
-    def __init__(self, prog, x_static, out):
-        self.prog, self.x_static, self.out = prog, x_static, out
-        self.runs = 0
-
-
 class _FlowBase(HipModule):
     """Shared forward / plan cache of the FlowNet2* wrappers."""
     rgb_max: float = 255.0
@@ -520,22 +514,17 @@ class _FlowBase(HipModule):
             return hook
         return view, hook_for
 
-    def _build_plan(self, B, H, W, device, dtype) -> _FlowPlan:  # pragma: no cover - abstract
+    def _build_plan(self, B, H, W, device, dtype) -> Plan:  # pragma: no cover - abstract
         raise NotImplementedError
 
-    def plan_for(self, B: int, H: int, W: int, replica: int = 0) -> _FlowPlan:
+    def plan_for(self, B: int, H: int, W: int, replica: int = 0) -> Plan:
         """`replica` > 0: an independent copy of the plan (own input / activation buffers and graph, same packed weights) for
         callers that keep several batches of one shape resident (bench.py's rotation; as DeconvResnet.plan_for)."""
         device, dtype = self._resolve()
         if H % 64 or W % 64:
             raise FlowtrackHipError(f"frame size {H}x{W}: FlowNet needs multiples of 64")
         key = (B, H, W, device, dtype) + ((replica,) if replica else ())
-        plan = self._plans.get(key)
-        if plan is None:
-            with torch.no_grad():
-                plan = self._build_plan(B, H, W, device, dtype)
-            self._plans[key] = plan
-        return plan
+        return self._cached_plan(key, lambda: self._build_plan(B, H, W, device, dtype))
 
     def static_input(self, B: int, H: int, W: int) -> torch.Tensor:
         """The plan's own input buffer [B,3,2,H,W] fp32 (the fixed address its graph reads): write the batch here and
@@ -554,16 +543,14 @@ class _FlowBase(HipModule):
             raise FlowtrackHipError("input and model are on different devices")
         if inputs.data_ptr() != plan.x_static.data_ptr():   # zero-copy when the caller filled static_input() in place
             plan.x_static.copy_(inputs)
-        self._run_plan(plan.prog, first=plan.runs == 0)
-        plan.runs += 1
+        self.run(plan)
         return plan.out.clone() if copy_output else plan.out
 
     @torch.no_grad()
-    def replay(self, plan: _FlowPlan) -> _FlowPlan:
+    def replay(self, plan: Plan) -> Plan:
         """Run a plan whose static input the caller filled in place (plan_for(...).x_static); the flow is plan.out."""
         self._check_eval()
-        self._run_plan(plan.prog, first=plan.runs == 0)
-        plan.runs += 1
+        self.run(plan)
         return plan
 
 
@@ -574,7 +561,7 @@ class FlowNet2S(FlowNetS, _FlowBase):
         self.rgb_max = float(args.rgb_max)
         self.div_flow = float(div_flow)
 
-    def _build_plan(self, B, H, W, device, dtype) -> _FlowPlan:
+    def _build_plan(self, B, H, W, device, dtype) -> Plan:
         prog = Program(self._side_stream(device))
         mk = dict(dtype=dtype, device=device, owner=self)
         x_static = torch.empty((B, 3, 2, H, W), dtype=torch.float32, device=device)
@@ -588,7 +575,7 @@ class FlowNet2S(FlowNetS, _FlowBase):
             flow2 = record_flownets(prog, self, x6, "", mk)
         out = torch.empty((B, 2, H, W), dtype=torch.float32, device=device)
         record_upsample4x(prog, flow2, out, self.div_flow)  # upsample1(flow2 * div_flow), models.py:292
-        return _FlowPlan(prog, x_static, out)
+        return Plan(prog, x_static=x_static, out=out)
 
     def _fold_supported(self, B: int, H: int, W: int, dtype, pad: int = 3) -> bool:
         """Whether conv1 on the padded view runs on the one kernel that takes a per-sample shift (fp16, large enough grids).
@@ -618,7 +605,7 @@ class FlowNet2C(FlowNetC, _FlowBase):
         self.rgb_max = float(args.rgb_max)
         self.div_flow = 20.0
 
-    def _build_plan(self, B, H, W, device, dtype) -> _FlowPlan:
+    def _build_plan(self, B, H, W, device, dtype) -> Plan:
         prog = Program(self._side_stream(device))
         mk = dict(dtype=dtype, device=device, owner=self)
         x_static = torch.empty((B, 3, 2, H, W), dtype=torch.float32, device=device)
@@ -626,7 +613,7 @@ class FlowNet2C(FlowNetC, _FlowBase):
         flow2 = record_flownetc(prog, self, x2b, "", mk)
         out = torch.empty((B, 2, H, W), dtype=torch.float32, device=device)
         record_upsample4x(prog, flow2, out, self.div_flow)
-        return _FlowPlan(prog, x_static, out)
+        return Plan(prog, x_static=x_static, out=out)
 
 
 class FlowNet2CS(_FlowBase):
@@ -643,7 +630,7 @@ class FlowNet2CS(_FlowBase):
         self.flownets_1 = FlowNetS(args, batchNorm=batchNorm)
         self.upsample2 = ActMarker("upsample_bilinear_x4")
 
-    def _build_plan(self, B, H, W, device, dtype) -> _FlowPlan:
+    def _build_plan(self, B, H, W, device, dtype) -> Plan:
         prog = Program(self._side_stream(device))
         mk = dict(dtype=dtype, device=device, owner=self)
         x_static = torch.empty((B, 3, 2, H, W), dtype=torch.float32, device=device)
@@ -658,7 +645,7 @@ class FlowNet2CS(_FlowBase):
         flow2s = record_flownets(prog, self.flownets_1, concat1, "flownets_1.", mk)
         out = torch.empty((B, 2, H, W), dtype=torch.float32, device=device)
         record_upsample4x(prog, flow2s, out, self.div_flow)             # models.py:406-407
-        return _FlowPlan(prog, x_static, out)
+        return Plan(prog, x_static=x_static, out=out)
 
 
 def record_upsample_nearest4x(prog: Program, x: torch.Tensor, y: torch.Tensor, mul: float) -> None:
@@ -684,7 +671,7 @@ class FlowNet2SD(FlowNetSD, _FlowBase):
         self.rgb_max = float(args.rgb_max)
         self.div_flow = float(div_flow)
 
-    def _build_plan(self, B, H, W, device, dtype) -> _FlowPlan:
+    def _build_plan(self, B, H, W, device, dtype) -> Plan:
         prog = Program(self._side_stream(device))
         mk = dict(dtype=dtype, device=device, owner=self)
         x_static = torch.empty((B, 3, 2, H, W), dtype=torch.float32, device=device)
@@ -692,7 +679,7 @@ class FlowNet2SD(FlowNetSD, _FlowBase):
         flow2 = record_flownetsd(prog, self, x6, "", mk)
         out = torch.empty((B, 2, H, W), dtype=torch.float32, device=device)
         record_upsample4x(prog, flow2, out, self.div_flow)
-        return _FlowPlan(prog, x_static, out)
+        return Plan(prog, x_static=x_static, out=out)
 
 
 class FlowNet2CSS(_FlowBase):
@@ -728,14 +715,14 @@ class FlowNet2CSS(_FlowBase):
         flow2s2 = record_flownets(prog, self.flownets_2, concat2, "flownets_2.", mk)
         return x6, flow2s2, extra
 
-    def _build_plan(self, B, H, W, device, dtype) -> _FlowPlan:
+    def _build_plan(self, B, H, W, device, dtype) -> Plan:
         prog = Program(self._side_stream(device))
         mk = dict(dtype=dtype, device=device, owner=self)
         x_static = torch.empty((B, 3, 2, H, W), dtype=torch.float32, device=device)
         _, flow2s2, _ = self._record_css(prog, x_static, B, H, W, dtype, device, mk)
         out = torch.empty((B, 2, H, W), dtype=torch.float32, device=device)
         record_upsample_nearest4x(prog, flow2s2, out, self.div_flow)                   # models.py:495-496
-        return _FlowPlan(prog, x_static, out)
+        return Plan(prog, x_static=x_static, out=out)
 
 
 class FlowNet2(FlowNet2CSS):
@@ -752,7 +739,7 @@ class FlowNet2(FlowNet2CSS):
         self.resample4 = ActMarker("resample2d")
         self.flownetfusion = FlowNetFusion(args, batchNorm=batchNorm)
 
-    def _build_plan(self, B, H, W, device, dtype) -> _FlowPlan:
+    def _build_plan(self, B, H, W, device, dtype) -> Plan:
         prog = Program(self._side_stream(device))
         mk = dict(dtype=dtype, device=device, owner=self)
         x_static = torch.empty((B, 3, 2, H, W), dtype=torch.float32, device=device)
@@ -767,4 +754,4 @@ class FlowNet2(FlowNet2CSS):
         prog.add("ft_flow_fusion_concat", x6.t.data_ptr(), flowsd.data_ptr(), flows2.data_ptr(), cat3.t.data_ptr(), B, H, W,
                  x6.lpad, x6.wpitch, cat3.lpad, cat3.wpitch, _lib.dtype_code(dtype), keep=(x6.t, flowsd, flows2, cat3.t))   # :134-168
         out = record_flownetfusion(prog, self.flownetfusion, cat3, "flownetfusion.", mk)
-        return _FlowPlan(prog, x_static, out)
+        return Plan(prog, x_static=x_static, out=out)

@@ -963,20 +963,35 @@ class FusedShortcutConv:
             hit = self._packed[key] = (w.to(device=self.device, dtype=self.dtype).contiguous(), shift.to(self.device))
         return hit
 
-    def record(self, prog: "Program", t2: ActView, x: ActView, y: ActView) -> None:
+    @staticmethod
+    def _desc_of(cin: int, cin2: int, cout: int, stride_d: int, code: int, act: int, t2: ActView, x: ActView, y: ActView) -> ConvDesc:
+        d = ConvDesc()
+        d.dtype = code
+        d.N, d.Hi, d.Wi = t2.N, t2.H, t2.W
+        d.Cin, d.x_cstride, d.x_coff = cin, t2.cstride, t2.coff
+        d.Cout, d.kh, d.kw, d.stride, d.pad, d.transposed = cout, 1, 1, 1, 0, 0
+        d.Ho, d.Wo = t2.H, t2.W
+        d.y_cstride, d.y_coff, d.out_layout = y.cstride, y.coff, FT_LAYOUT_NHWC
+        d.act, d.slope = act, 0.0
+        d.x2_cin, d.x2_hi, d.x2_wi, d.x2_cstride, d.x2_coff, d.x2_stride = cin2, x.H, x.W, x.cstride, x.coff, stride_d
+        return d
+
+    @classmethod
+    def supported(cls, cin: int, cin2: int, cout: int, stride_d: int, dtype, t2: ActView, x: ActView, y: ActView) -> bool:
+        """True where the library takes the K-concatenated GEMM for these views (ft_conv_pack_geometry).  Needs no instance: a host whose
+        maps may not fit (odd sizes) asks before any weight of the layer is folded or packed."""
+        d = cls._desc_of(cin, cin2, cout, stride_d, _lib.dtype_code(dtype), FT_ACT_RELU, t2, x, y)
+        return _lib.load().ft_conv_pack_geometry(ctypes.byref(d), ctypes.byref(ConvGeometry())) == 0
+
+    def _desc(self, t2: ActView, x: ActView, y: ActView) -> ConvDesc:
         if t2.C != self.cin or x.C != self.cin2 or y.C != self.cout:
             raise FlowtrackHipError(f"{self.label}: channel mismatch")
         if (x.N, (x.H - 1) // self.stride_d + 1, (x.W - 1) // self.stride_d + 1) != (t2.N, t2.H, t2.W) or (y.N, y.H, y.W) != (t2.N, t2.H, t2.W):
             raise FlowtrackHipError(f"{self.label}: shortcut / main / output sizes do not line up")
-        d = ConvDesc()
-        d.dtype = self.code
-        d.N, d.Hi, d.Wi = t2.N, t2.H, t2.W
-        d.Cin, d.x_cstride, d.x_coff = self.cin, t2.cstride, t2.coff
-        d.Cout, d.kh, d.kw, d.stride, d.pad, d.transposed = self.cout, 1, 1, 1, 0, 0
-        d.Ho, d.Wo = t2.H, t2.W
-        d.y_cstride, d.y_coff, d.out_layout = y.cstride, y.coff, FT_LAYOUT_NHWC
-        d.act, d.slope = self.act, 0.0
-        d.x2_cin, d.x2_hi, d.x2_wi, d.x2_cstride, d.x2_coff, d.x2_stride = self.cin2, x.H, x.W, x.cstride, x.coff, self.stride_d
+        return self._desc_of(self.cin, self.cin2, self.cout, self.stride_d, self.code, self.act, t2, x, y)
+
+    def record(self, prog: "Program", t2: ActView, x: ActView, y: ActView) -> None:
+        d = self._desc(t2, x, y)
         w, shift = self._packed_for(d)
         flops = float(self.lib.ft_conv_flops(ctypes.byref(d)))
         ws = _direct_stream(self, d, w, t2.t.device)

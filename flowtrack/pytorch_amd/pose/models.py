@@ -19,6 +19,7 @@ shape; the ~60 launches of one forward are replayed as a HIP graph.
 """
 from __future__ import annotations
 
+import functools
 import math
 import os
 from typing import List
@@ -26,42 +27,13 @@ from typing import List
 import torch
 import torch.nn as nn
 
-from ..engine import HipModule
-from ..hip_ops import (ActView, FlowtrackHipError, FusedConv, FusedLateralDeconv, FusedShortcutConv, Program, record_scale_shift_act, bottleneck_exit_fusable, bottleneck_fusable,
-                       bottleneck_entry_fusable, bottleneck_head_fusable, bottleneck_cluster_supported, bottleneck_strips_supported, bottleneck_head_stream_fusable, bottleneck_prefers_fused, new_act, new_rowpacked_act, record_bottleneck, record_bottleneck_entry, record_bottleneck_head, record_bottleneck_head_stream,
+from ..engine import HipModule, Plan
+from ..hip_ops import (ActView, FlowtrackHipError, FusedConv, FusedLateralDeconv, Program, record_scale_shift_act, bottleneck_exit_fusable, new_act, new_rowpacked_act,
                        record_bottleneck_exit, record_maxpool, record_pack_input, fold_scale_shift, record_upsample_ac, record_hourglass_down, record_hourglass_up)
 from ..params import ActMarker, BatchNormParams, ConvParams, ConvTransposeParams
+from ..resnet import BLOCKS, Bottleneck, record_block
 
-# depth -> blocks per stage; only Bottleneck nets are valid because the head hard-codes 2048
-# input channels (pose_deconv.py:20), see SURVEY §8 P1.
-resnet_dict = {50: [3, 4, 6, 3], 101: [3, 4, 23, 3], 152: [3, 8, 36, 3]}
-
-
-class Bottleneck(nn.Module):
-    """Parameter layout of blocks.py:83-103 (stride on the 3x3, torchvision-compatible)."""
-    expansion = 4
-
-    def __init__(self, inplanes: int, planes: int, stride: int = 1):
-        super().__init__()
-        self.stride = stride
-        self.conv1 = ConvParams(inplanes, planes, 1, bias=False)
-        self.bn1 = BatchNormParams(planes)
-        self.conv2 = ConvParams(planes, planes, 3, stride=stride, padding=1, bias=False)
-        self.bn2 = BatchNormParams(planes)
-        self.conv3 = ConvParams(planes, planes * 4, 1, bias=False)
-        self.bn3 = BatchNormParams(planes * 4)
-        self.relu = ActMarker("relu")
-        if stride != 1 or inplanes != planes * 4:
-            self.downsample = nn.Sequential(ConvParams(inplanes, planes * 4, 1, stride=stride, bias=False),
-                                            BatchNormParams(planes * 4))
-        else:
-            self.downsample = nn.Sequential()
-
-
-class _PosePlan:
-    def __init__(self, prog, x_static, heatmaps):
-        self.prog, self.x_static, self.heatmaps = prog, x_static, heatmaps
-        self.runs = 0
+resnet_dict = BLOCKS      # depth -> blocks per stage (resnet.py)
 
 
 class _Stages(dict):
@@ -220,7 +192,7 @@ class PoseResnet(HipModule):
         if H % 32 or W % 32:
             raise FlowtrackHipError(f"input {H}x{W}: height and width must be multiples of 32")
 
-    def _build_plan(self, B: int, H: int, W: int, device, dtype, perm=None) -> _PosePlan:
+    def _build_plan(self, B: int, H: int, W: int, device, dtype, perm=None) -> Plan:
         """The plan of one input shape: the staged input (and its mirrored half in a flip plan), the network's own launches
         (_record_net: what a model family overrides), then the flip merge / the key points / the exact-arg-max screen."""
         self._check_input_size(H, W)
@@ -238,7 +210,7 @@ class PoseResnet(HipModule):
             # of the merged maps — in place of the separate ft_heatmap_keypoint_rows launch
             K, hh, hw = self.num_classes, heatmaps.shape[2], heatmaps.shape[3]
             merged = torch.empty((B0, K, hh, hw), dtype=torch.float32, device=device)
-            plan = _PosePlan(prog, x_static[:B0], merged)
+            plan = Plan(prog, x_static=x_static[:B0], heatmaps=merged)
             plan.stages, plan.heatmaps_raw, plan.x_full = stages, heatmaps, x_static
             plan.flip_perm = torch.tensor(perm, dtype=torch.int32, device=device)
             plan.kp_idx = plan.kp_rows = None
@@ -252,7 +224,7 @@ class PoseResnet(HipModule):
                      int(bool(self.keypoints_in_plan)), merged.data_ptr(), plan.kp_idx.data_ptr() if plan.kp_idx is not None else None,
                      plan.kp_rows.data_ptr() if plan.kp_rows is not None else None, keep=tuple(keep))
             return plan
-        plan = _PosePlan(prog, x_static, heatmaps)
+        plan = Plan(prog, x_static=x_static, heatmaps=heatmaps)
         plan.stages = stages
         if self.keypoints_in_plan is not None:
             # max_preds (+ the 0.25 px nudge of final_preds) as the last launch of the plan: no extra stream work per call
@@ -323,30 +295,12 @@ class PoseResnet(HipModule):
                                                    "its output (the full map exists only if the first-call benchmark kept today's launches): for the "
                                                    "map, build the model with fuse_stage_exit = False (FT_FUSE_STAGE_EXIT=0)")
             if split and li == 1:
-                chain = []
-                hh, ww = cur.H, cur.W
-                for lj, lay in ((1, self.layer1), (2, self.layer2)):
-                    for bi, blk in enumerate(lay):
-                        hh, ww = hh // blk.stride, ww // blk.stride
-                        chain.append((f"layer{lj}.{bi}", blk, new_act(B, hh, ww, blk.conv1.cout * 4, dtype, device)))
-                prog.fork()
-                for half, (lo, hi) in enumerate(((0, B // 2), (B // 2, B))):
-                    c = cur.batch_slice(lo, hi)
-                    if half == 1:
-                        with prog.side():
-                            if split == 2:      # half a block of useful delay: the lanes' memory and matrix phases interleave
-                                stem.record(prog, a_in.batch_slice(lo, hi), cur.batch_slice(lo, hi), pool=True, x_nchw=xs(lo, hi))
-                            for name, blk, out_full in chain:
-                                o = out_full.batch_slice(lo, hi)
-                                self._record_block(prog, name, blk, c, o, dtype, device)
-                                c = o
-                    else:
-                        for name, blk, out_full in chain:
-                            o = out_full.batch_slice(lo, hi)
-                            self._record_block(prog, name, blk, c, o, dtype, device)
-                            c = o
-                prog.join()
-                cur = chain[-1][2]
+                # (split == 2: the side lane starts with its half of the stem: half a block of useful delay, the lanes' memory and
+                # matrix phases interleave)
+                side_stem = functools.partial(stem.record, prog, a_in.batch_slice(B // 2, B), cur.batch_slice(B // 2, B), pool=True,
+                                              x_nchw=xs(B // 2, B)) if split == 2 else None
+                cur = self._record_lanes(prog, [(f"layer{lj}.{bi}", blk) for lj, lay in ((1, self.layer1), (2, self.layer2)) for bi, blk in enumerate(lay)],
+                                         cur, side_stem)
                 continue
             if split and li == 2:
                 continue
@@ -355,27 +309,7 @@ class PoseResnet(HipModule):
                 # are the launch's ramp with the chip mostly idle: cd_phases.py shows 10-us workgroup lifetimes in 16-us kernels); two
                 # lanes fill each other's ramps, and halving the pixels halves the workgroups, not the weight bytes per workgroup.
                 # MEASURED (two interleaved bench runs): 56.37 / 55.82 -> 53.75 / 53.79 k crops/s: off.
-                chain = []
-                hh, ww = cur.H, cur.W
-                for bi, blk in enumerate(layer):
-                    hh, ww = hh // blk.stride, ww // blk.stride
-                    chain.append((f"layer4.{bi}", blk, new_act(B, hh, ww, blk.conv1.cout * 4, dtype, device)))
-                prog.fork()
-                for half, (lo, hi) in enumerate(((0, B // 2), (B // 2, B))):
-                    c = cur.batch_slice(lo, hi)
-
-                    def lane(c=c, lo=lo, hi=hi):
-                        for name, blk, out_full in chain:
-                            o = out_full.batch_slice(lo, hi)
-                            self._record_block(prog, name, blk, c, o, dtype, device)
-                            c = o
-                    if half == 1:
-                        with prog.side():
-                            lane()
-                    else:
-                        lane()
-                prog.join()
-                cur = chain[-1][2]
+                cur = self._record_lanes(prog, [(f"layer4.{bi}", blk) for bi, blk in enumerate(layer)], cur)
                 continue
             for bi, blk in enumerate(layer):
                 if bi == 0 and seam is not None:
@@ -387,12 +321,39 @@ class PoseResnet(HipModule):
                     seam = self._record_stage_exit(prog, name, blk, f"layer{li + 1}.0", trunk[li][0], cur, out, dtype, device)
                     if seam is not None:
                         continue
-                self._record_block(prog, name, blk, cur, out, dtype, device)
-                cur = out
+                cur = self._record_trunk_block(prog, name, blk, cur, out)
 
         stages["layer4"] = cur
         heatmaps = self._record_head(prog, stages, cur, dtype, device)
         return stages, heatmaps
+
+    def _record_lanes(self, prog, blocks, cur: ActView, side_first=None) -> ActView:
+        """The chain `blocks` = [(name, blk), ...] from view `cur` as two half-batch lanes (parallel graph branches): the first half
+        on the main lane, the second on the side lane, behind `side_first()` where given.  Returns the chain's full-batch output."""
+        B, chain = cur.N, []
+        hh, ww = cur.H, cur.W
+        for name, blk in blocks:
+            hh, ww = hh // blk.stride, ww // blk.stride
+            chain.append((name, blk, new_act(B, hh, ww, blk.conv1.cout * 4, cur.t.dtype, cur.t.device)))
+
+        def lane(lo, hi):
+            c = cur.batch_slice(lo, hi)
+            for name, blk, out_full in chain:
+                c = self._record_trunk_block(prog, name, blk, c, out_full.batch_slice(lo, hi))
+        prog.fork()
+        lane(0, B // 2)
+        with prog.side():
+            if side_first is not None:
+                side_first()
+            lane(B // 2, B)
+        prog.join()
+        return chain[-1][2]
+
+    def _record_trunk_block(self, prog, name: str, blk, cur: ActView, out: ActView) -> ActView:
+        """One trunk block (stride on its 3x3) in every form this model's switches offer: resnet.record_block."""
+        forms = (("fused", "entry", "head", "head2") if self.fuse_bottleneck else ()) + (("shortcut",) if self.fuse_shortcut else ()) + \
+            (("cluster",) if self.cluster_kernels else ()) + (("strips",) if self.strip_kernels else ())
+        return record_block(self, prog, name, blk, cur, out, stride=blk.stride, stride_on="conv2", forms=forms)
 
     def _record_stage_exit(self, prog, name: str, blk, nname: str, nblk, cur, out, dtype, device):
         """The seam between two stages: `blk` = the stage's last identity block (from `cur` into `out`), `nblk` = the stride-2 entry
@@ -401,7 +362,7 @@ class PoseResnet(HipModule):
         the first-call benchmark keeps one:
           "fused"  blk + nblk.conv1 as one launch that writes t1 and the even pixels of blk's output as a compact half-size map,
                    then nblk.conv2 and the K-concatenated conv3 + shortcut, which reads the compact map at stride 1;
-          "convs"  the launches _record_block gives the two blocks (nblk.conv1 a launch of its own).
+          "convs"  the launches resnet.record_block gives the two blocks (nblk.conv1 a launch of its own).
         Returns nblk's output view, or None when the exit form does not apply (nothing recorded then)."""
         if not (self.fuse_stage_exit and self.fuse_bottleneck and self.fuse_shortcut) or dtype != torch.float16:
             return None
@@ -420,12 +381,8 @@ class PoseResnet(HipModule):
             return None
         t2 = new_act(B, cur.H // 2, cur.W // 2, nplanes, dtype, device)
         nout = new_act(B, cur.H // 2, cur.W // 2, nplanes * 4, dtype, device)
-        key = (nname + ".conv3+downsample@even", dtype, str(device))
-        sc = self._layers.get(key)
-        if sc is None:      # the same GEMM as _record_block's, its shortcut operand read at stride 1 from the compact map
-            sc = self._layers[key] = FusedShortcutConv(nblk.conv3.weight, nblk.bn3.as_dict(), nblk.downsample[0].weight,
-                                                       nblk.downsample[1].as_dict(), 1, dtype=dtype, device=device, act="relu",
-                                                       label=nname + ".conv3+downsample")
+        # the same GEMM as the block recorder's, its shortcut operand read at stride 1 from the compact map
+        sc = self.fused_shortcut(nname + ".conv3+downsample", nblk, 1, key_suffix="@even", **mk)
 
         def exit_form():
             record_bottleneck_exit(prog, c1, c2, c3, n1, cur, y_even, t1, f"{name}.fused+{nname}.conv1", "even")
@@ -433,8 +390,8 @@ class PoseResnet(HipModule):
             sc.record(prog, t2, y_even, nout)
 
         def block_form():
-            self._record_block(prog, name, blk, cur, out, dtype, device)
-            self._record_block(prog, nname, nblk, out, nout, dtype, device)
+            self._record_trunk_block(prog, name, blk, cur, out)
+            self._record_trunk_block(prog, nname, nblk, out, nout)
         if self.fuse_stage_exit == "force":
             exit_form()
             return nout
@@ -447,100 +404,6 @@ class PoseResnet(HipModule):
         prog.end_choice()
         return nout
 
-    def _record_block(self, prog, name: str, blk, cur, out, dtype, device) -> None:
-        """One Bottleneck (blocks.py:83-120) from view `cur` into view `out` (both may be batch slices of larger buffers): the
-        fused / unfused forms are recorded as alternatives where both exist, the first-call benchmark keeps one."""
-        B = cur.N
-        mk = dict(dtype=dtype, device=device)
-        planes = blk.conv1.cout
-        s = blk.stride
-        Ho, Wo = cur.H // s, cur.W // s
-        c1 = self.fused(name + ".conv1", blk.conv1.weight, bn=blk.bn1.as_dict(), act="relu", **mk)
-        c2 = self.fused(name + ".conv2", blk.conv2.weight, stride=s, pad=1, bn=blk.bn2.as_dict(), act="relu", **mk)
-        c3 = self.fused(name + ".conv3", blk.conv3.weight, bn=blk.bn3.as_dict(), act="relu", **mk)
-        if self.fuse_bottleneck and not len(blk.downsample) and s == 1 and bottleneck_fusable(c1, c2, c3, cur, out):
-            # the whole block in one launch (t1 / t2 never leave LDS) or as three conv launches: which one is faster
-            # depends on how many workgroups the stage's pixels make (each streams the block's whole weight set),
-            # so both are recorded and the first-call benchmark keeps one (Program.tune_choices)
-            t1 = new_act(B, cur.H, cur.W, planes, dtype, device)
-            t2 = new_act(B, Ho, Wo, planes, dtype, device)
-
-            def fused_form():
-                record_bottleneck(prog, c1, c2, c3, cur, out, name + ".fused", form="patch")
-
-            def conv_form():
-                c1.record(prog, cur, t1)
-                c2.record(prog, t1, t2)
-                c3.record(prog, t2, out, residual=cur)
-            forms = (("fused", fused_form), ("convs", conv_form))
-            if not bottleneck_prefers_fused(cur, planes):
-                forms = forms[::-1]
-            if self.cluster_kernels and bottleneck_cluster_supported(cur, out, planes):
-                # round 5: the same block shared by a cluster of four workgroups per image (t1 / t2 exchanged inside the
-                # launch): a third recorded form, kept where the first-call benchmark measures it faster
-                forms = forms + (("cluster", lambda: record_bottleneck(prog, c1, c2, c3, cur, out, name + ".cluster", cluster=True)),)
-            if self.strip_kernels and planes == 64 and bottleneck_strips_supported(cur, out, planes):
-                # round 5: the 64-plane block on register-stationary strips (csrc/bottleneck_rstat.hip): 54 against 57.5 us alone
-                # and with warm caches, 59-63 against ~55 us behind a cold L2 (its prologue waits for 139 KB of weights before the
-                # first x load): recorded only with FT_STRIP_KERNELS=1 — the first-call benchmark times a group's later options
-                # behind warmer caches than its first, a bias larger than this form's margin
-                strips = (("strips", lambda: record_bottleneck(prog, c1, c2, c3, cur, out, name + ".strips", form="strips")),)
-                forms = strips + forms if os.environ.get("FT_STRIP_KERNELS") == "2" else forms + strips      # (2: the first choice, dev)
-            prog.begin_choice(f"bottleneck|{B},{cur.H},{cur.W},{cur.C},{planes},{cur.cstride},{out.cstride}")
-            for form_name, form in forms:
-                prog.option(form_name)
-                form()
-            prog.end_choice()
-            return
-        t2 = new_act(B, Ho, Wo, planes, dtype, device)
-        fused = None
-        if len(blk.downsample) and self.fuse_shortcut:
-            key = (name + ".conv3+downsample", dtype, str(device))
-            fused = self._layers.get(key)
-            if fused is None:
-                fused = self._layers[key] = FusedShortcutConv(
-                    blk.conv3.weight, blk.bn3.as_dict(), blk.downsample[0].weight, blk.downsample[1].as_dict(), s,
-                    dtype=dtype, device=device, act="relu", label=name + ".conv3+downsample")
-        whole = self.fuse_bottleneck and fused is not None and bottleneck_entry_fusable(c1, c2, fused, cur, out)
-        if whole:
-            # the 64-wide entry block whole (t1, t2 and the shortcut never leave the CU) or as head + K-concatenated
-            # conv3: both recorded, the first-call benchmark keeps one
-            prog.begin_choice(f"entry|{B},{cur.H},{cur.W},{cur.C},{planes},{cur.cstride},{out.cstride}")
-            prog.option("fused")
-            record_bottleneck_entry(prog, c1, c2, fused, cur, out, name + ".fused")
-            prog.option("head+exit")
-        if self.fuse_bottleneck and s == 1 and bottleneck_head_fusable(c1, c2, cur, t2):
-            record_bottleneck_head(prog, c1, c2, cur, t2, name + ".conv1+conv2")   # the 64-wide entry block: t1 in LDS only
-        else:
-            head2 = self.fuse_bottleneck and s == 2 and bottleneck_head_stream_fusable(c1, c2, cur, t2)
-            if head2:
-                # the 256-plane entry block's conv1 + stride-2 conv2 as one streamed-weights launch, or as two launches:
-                # both recorded, the first-call benchmark keeps one (the recorder's first choice: two launches)
-                prog.begin_choice(f"head2|{B},{cur.H},{cur.W},{cur.C},{planes},{cur.cstride},{t2.cstride}")
-                prog.option("convs")
-            t1 = new_act(B, cur.H, cur.W, planes, dtype, device)
-            c1.record(prog, cur, t1)
-            c2.record(prog, t1, t2)
-            if head2:
-                prog.option("fused")
-                record_bottleneck_head_stream(prog, c1, c2, cur, t2, name + ".conv1+conv2")
-                prog.end_choice()
-        if fused is not None:
-            # conv3 + bn3 and the projection shortcut as one GEMM over K = [t2 | block input] (blocks.py:104-119):
-            # the shortcut tensor never exists in HBM
-            fused.record(prog, t2, cur, out)
-        elif len(blk.downsample):
-            ds = self.fused(name + ".downsample", blk.downsample[0].weight, stride=s, bn=blk.downsample[1].as_dict(),
-                            act=None, **mk)
-            res = new_act(B, Ho, Wo, planes * 4, dtype, device)
-            ds.record(prog, cur, res)
-            c3.record(prog, t2, out, residual=res)
-        else:
-            c3.record(prog, t2, out, residual=cur)  # relu(bn3(conv3) + residual), blocks.py:114-119
-        if whole:
-            prog.end_choice()
-
-
     #: offer the cluster form of the 256-plane identity blocks (ft_bottleneck_cluster_fwd) to the first-call benchmark
     #: (FT_CLUSTER_KERNELS=1).  OFF by default: measured in situ at R50 batch 64 it takes 50-52 us per block against the strip
     #: form's 48 (each of its two in-launch hand-offs costs 4-5 us: profiles/README.md, round 5), and its workgroups wait for
@@ -548,25 +411,20 @@ class PoseResnet(HipModule):
     cluster_kernels: bool = os.environ.get("FT_CLUSTER_KERNELS", "0") == "1"
     strip_kernels: bool = os.environ.get("FT_STRIP_KERNELS", "0") in ("1", "2")      # the 64-plane block's register-stationary form as an option
 
-    def plan_for(self, B: int, H: int, W: int, replica: int = 0) -> _PosePlan:
+    def plan_for(self, B: int, H: int, W: int, replica: int = 0) -> Plan:
         """The plan (launch list + activation buffers + graph) of one input shape.  `replica` > 0 gives an independent copy
         with its own buffers — same packed weights, same tile picks — for callers that keep several batches of one shape
         in flight on different streams (tracking.PoseRunner per clip, tools/tracking/demo.run_clips)."""
         return self._plan_for(B, H, W, replica, self._flip_perm())
 
-    def _plan_for(self, B: int, H: int, W: int, replica: int = 0, perm=None) -> _PosePlan:
+    def _plan_for(self, B: int, H: int, W: int, replica: int = 0, perm=None) -> Plan:
         """plan_for() with the flip test stated by the caller: perm = None is the plain plan of the shape whatever flip_pairs says."""
         if self.exact_in_plan:
             self._check_exact_supported("exact_in_plan")
         device, dtype = self._resolve()
         key = (B, H, W, device, dtype, self.keypoints_in_plan) + (("exact", float(self.exact_argmax_rel_bound)) if self.exact_in_plan else ()) + \
             ((replica,) if replica else ()) + ((("flip",) + tuple(perm),) if perm is not None else ())
-        plan = self._plans.get(key)
-        if plan is None:
-            with torch.no_grad():
-                plan = self._build_plan(B, H, W, device, dtype, perm)
-            self._plans[key] = plan
-        return plan
+        return self._cached_plan(key, lambda: self._build_plan(B, H, W, device, dtype, perm))
 
     def static_input(self, B: int, H: int, W: int) -> torch.Tensor:
         """The plan's own input buffer [B,3,H,W] fp32 (the fixed address its graph reads).  A producer that writes its
@@ -598,18 +456,16 @@ class PoseResnet(HipModule):
             raise FlowtrackHipError("input and model are on different devices")
         if x.data_ptr() != plan.x_static.data_ptr():   # zero-copy when the caller filled static_input() in place
             plan.x_static.copy_(x)  # dtype cast + staging into the graph's fixed input address
-        self._run_plan(plan.prog, first=plan.runs == 0)
-        plan.runs += 1
+        self.run(plan)
         self._last_plan = plan
         return plan.heatmaps.clone() if copy_output else plan.heatmaps
 
     @torch.no_grad()
-    def replay(self, plan: "_PosePlan") -> "_PosePlan":
+    def replay(self, plan: Plan) -> Plan:
         """Run a plan whose static input the caller filled in place (plan_for(...).x_static): forward() without the second
         plan look-up and the shape checks — the per-call host cost matters to the tracking pass, one small batch per frame."""
         self._check_eval()
-        self._run_plan(plan.prog, first=plan.runs == 0)
-        plan.runs += 1
+        self.run(plan)
         self._last_plan = plan
         return plan
 
@@ -724,7 +580,7 @@ class PoseResnet(HipModule):
         return h
 
     @torch.no_grad()
-    def exact_submit_plan(self, plan: "_PosePlan") -> "_PosePlan":
+    def exact_submit_plan(self, plan: Plan) -> Plan:
         """exact_submit() for a caller that owns the plan (plan_for(..., replica) with `exact_in_plan` set, its x_static filled in
         place): ONE graph replay — network, key-point rows, screen, gather, header copy — and an event.  The plan's buffers are the
         step's state, so a plan must be finished (exact_finish_plan) before it is submitted again: callers that keep several steps
@@ -749,7 +605,7 @@ class PoseResnet(HipModule):
         return plan
 
     @torch.no_grad()
-    def exact_finish_plan(self, plan: "_PosePlan"):
+    def exact_finish_plan(self, plan: Plan):
         """(plan.kp_rows with the flagged crops' rows replaced by the fp32 parity mode's, number of crops re-run)."""
         from .. import _lib
         from ..hip_ops import check

@@ -176,6 +176,19 @@ def test_fp16_plan_structure(hip_lib):
     assert hnames[0] == "ft_roi_crop_nhwc_fwd" and hnames.count("ft_rcnn_mean_pool_fwd") == 1 and head.rois.shape == (300, 5)
 
 
+def test_even_maps_get_no_form_the_detector_does_not_offer(hip_lib):
+    """A 128x192 blob has even maps throughout (32x48, 16x24, 8x12), where the library's queries would also take the pose trunk's
+    entry / head forms (layer1.0 is 64 -> 64 -> 256 at stride 1): the shared block recorder must offer the detector only whole
+    identity blocks and the shortcut GEMM.  The plan is built, not run."""
+    from flowtrack.pytorch_amd import _lib
+    plan = _net(torch.float16).trunk_plan(128, 192)
+    descs = [c[1][0]._obj for c in plan.prog.calls if c[0].startswith("ft_bottleneck")]
+    assert len(descs) == 2 + 3 + 5 and all(isinstance(d, _lib.BottleneckDesc) and d.head_only == 0 and d.projection == 0 for d in descs)
+    keys = [c[1][0] for c in plan.prog.calls if c[0] == "__choice__"]
+    assert sum(k.startswith("bottleneck|") for k in keys) == 10 and not any(k.startswith(("entry|", "head2|", "bottleneck|exit")) for k in keys)
+    assert plan.fallbacks == [] and plan.runs == 0
+
+
 @pytest.mark.parametrize("dtype", DTYPES, ids=DTYPE_IDS)
 def test_plan_reuse_and_call_order(hip_lib, dtype):
     net = _new_net(dtype)

@@ -48,10 +48,10 @@ def frcnn(name, H, W, dt):
         return (time.perf_counter() - t0) / n * 1e3, out
     from flowtrack.pytorch_amd.detection import proposal
     t_blob, _ = timed(lambda: det_test.stage_frame(net, frame, **kw))
-    t_trunk, _ = timed(lambda: net._run(plan))
+    t_trunk, _ = timed(lambda: net.run(plan))
     t_prop, (rois, _) = timed(lambda: proposal.proposal_layer(plan.rpn_cls_prob, plan.rpn_bbox_pred, im_info, "TEST", 16, plan.anchors, net._num_anchors))
     t_head, _ = timed(lambda: net.region_head(plan, rois, float(im_info[2]), shape))
-    t_hplan, _ = timed(lambda: net._run(head))
+    t_hplan, _ = timed(lambda: net.run(head))
     t_all, _ = timed(lambda: det_test.detect_persons(net, frame, 1, 0.3, **kw))
     print(f"per image: ft_detect_blob_fwd {t_blob:.3f} ms, trunk + RPN plan (graph) {t_trunk:.3f} ms, proposal step {t_prop:.3f} ms, region head {t_head:.3f} ms "
           f"(its plan alone {t_hplan:.3f} ms; the rest: RoI staging + ft_rcnn_detections_fwd), detect_persons end to end {t_all:.3f} ms")
