@@ -62,6 +62,12 @@ class ConvGeometry(ctypes.Structure):
         return tuple(getattr(self, f) for f, _ in self._fields_)
 
 
+class ConvTile(ctypes.Structure):
+    """Mirror of `ft_conv_tile`: the fields of a `tile_hint` (`sk` is the slice count, not its code)."""
+
+    _fields_ = [("bp", c_int), ("bc", c_int), ("ks", c_int), ("sk", c_int), ("wide", c_int), ("halo", c_int)]
+
+
 _PROTOTYPES = {
     # name: (restype, argtypes)
     "ft_version": (c_int, []),
@@ -82,6 +88,8 @@ _PROTOTYPES = {
     "ft_memcpy_async": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
     "ft_conv_pack_geometry": (c_int, [POINTER(ConvDesc), POINTER(ConvGeometry)]),
     "ft_conv_tile_candidates": (c_int, [POINTER(ConvDesc), POINTER(c_int), c_int]),
+    "ft_conv_tile_decode": (c_int, [c_int, POINTER(ConvTile)]),
+    "ft_conv_tile_encode": (c_int, [POINTER(ConvTile)]),
     "ft_conv_workspace_bytes": (ctypes.c_size_t, [POINTER(ConvDesc)]),
     "ft_conv2d_fwd_ws": (c_int, [POINTER(ConvDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  ctypes.c_size_t, c_void_p]),

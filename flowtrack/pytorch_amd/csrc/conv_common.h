@@ -1,6 +1,7 @@
-// Shared pieces of the implicit-GEMM conv kernels (conv_igemm.hip: the tiled one-barrier-per-K-step kernels and the
-// host dispatch; conv_igemm8.hip: the 256 x 256 8-phase kernel): kernel parameter block, MFMA slice helpers and the
-// common epilogue (folded BN / bias, residual, activation, LDS-transposed 16-byte stores, fused tail 1x1 conv).
+// Shared device-side pieces of the conv kernels behind ft_conv2d_fwd (conv_igemm.hip: the tiled one-barrier-per-K-step
+// GEMM kernels; conv_igemm8.hip: the 256 x 256 8-phase kernel; conv_fewout.hip: the kernels for
+// <= 4 output channels): kernel parameter block, MFMA slice helpers and the common epilogue (folded BN / bias, residual,
+// activation, LDS-transposed 16-byte stores, fused tail 1x1 conv).  The host side (dispatch, launch entries): conv_dispatch.h.
 #pragma once
 #include <stdlib.h>
 
@@ -366,10 +367,5 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, float16_t (&a
     }
   }
 }
-
-// conv_igemm8.hip: the 256 x 256 tile on the 8-phase ping-pong schedule, persistent (fp16, Cin % 64 == 0, Cout_pad % 256 == 0,
-// no second input, no residual; output = NHWC fp16 in 8-channel-aligned views, the fused tail's map, or split-K partials);
-// p.kc / p.nk count 64-channel K-tiles, `tiles` = p.npt * p.nct * p.nph * p.sk; one workgroup of 512 threads per CU walks them.
-int launch_igemm8(const ConvParams& p, unsigned tiles, hipStream_t s);
 
 }  // namespace ft

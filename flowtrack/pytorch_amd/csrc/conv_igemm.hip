@@ -27,19 +27,18 @@
 //     global -> VGPR -> LDS, 2 stages, K runs over (tap, channel-group) pairs that may straddle taps.
 //   fp16 uses v_mfma_f32_32x32x16_f16 (fp32 accumulate); fp32 uses v_mfma_f32_32x32x2_f32 (exact fp32
 //   FMA chain) so the parity mode and the fast mode share every line of index arithmetic.
+// This unit: the two GEMM kernels, the split-K reduce, the dma tile table, and the halo and stem kernels.  The other families
+// (conv_igemm8.hip, conv_fewout.hip) and the dispatcher (conv_dispatch.hip) meet in conv_dispatch.h.
+// The halo and stem kernels stay HERE on purpose: each inlines a conv_epilogue instantiation that it shares with the dma kernels, and
+// in a unit of their own the compiler emits other instructions for conv_halo_kernel and conv_stem_kernel<.., 1> (checked with
+// tools/dev/isa_diff.py: a hoisted shift pair in the epilogue, other registers).  Moving them is a change to measure, not a refactor.
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "ft_common.h"
 
-#ifndef FT_DMA_BKB
-#define FT_DMA_BKB 64
-#endif
-#ifndef FT_DMA_STAGES
-#define FT_DMA_STAGES 3   // measured on R50 B=64: 2 -> 1.88 ms, 3 -> 1.90, 4 -> 1.98, 5 -> 2.22 (occupancy beats ring depth)
-#endif
-#include "conv_common.h"
+#include "conv_dispatch.h"
 
 namespace ft {
 
@@ -1768,568 +1767,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_pool_kernel(const ConvParams
 // this kernel in the network (same call): the 15 us the gather costs (FT_STEM_ABL=1) are not exposed latency — four workgroups per
 // CU already overlap one another's gathers — profiles/README.md, round 6.
 
-// ---- few-output-channel conv (FlowNet predict_flow: Cout = 2, K up to 9 * 1026) -----------------------
-// A GEMM tile would leave 30/32 MFMA columns idle and serialise a 9k-long K loop in a handful of
-// workgroups.  Instead: one wave per group of PIX consecutive output pixels, the 64 lanes split the
-// (tap, channel-group) axis with 16-byte coalesced loads, fp32 dot products (v_dot2_f32_f16 for fp16: no
-// explicit converts), a transpose-reduce butterfly (PIX*NCO values -> one per lane group), the (tiny) weight
-// set in LDS once per workgroup, each weight vector reused for PIX pixels from registers.
-// Uses the generic packed layout [Cout_pad][Kpad].
-typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float dot8(const uint4_t& a, const uint4_t& b, float c, half_t*) {
-  // whole-vector bit casts only (bit_cast of one vector element reads element 0, see mma_slice)
-  const half8_t ah = __builtin_bit_cast(half8_t, a), bh = __builtin_bit_cast(half8_t, b);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const half2_t a2 = {ah[2 * q], ah[2 * q + 1]}, b2 = {bh[2 * q], bh[2 * q + 1]};
-    c = __builtin_amdgcn_fdot2(a2, b2, c, false);
-  }
-  return c;
-}
-__device__ __forceinline__ float dot8(const uint4_t& a, const uint4_t& b, float c, float*) {
-  const float4_t af = __builtin_bit_cast(float4_t, a), bf = __builtin_bit_cast(float4_t, b);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) c += af[q] * bf[q];
-  return c;
-}
-
-template <typename T, int NCO, int PIX>
-__global__ __launch_bounds__(256) void conv_fewout_kernel(const ConvParams p, int ppb) {
-  constexpr int VEC = Elem<T>::VEC;
-  constexpr int NV = PIX * NCO;  // partial sums per lane
-  static_assert(NV == 8, "the reduction below folds exactly 8 values over the 64 lanes");
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nvec = p.kh * p.kw * p.cin_groups;   // 16-byte vectors along K per output pixel
-  // Round 5: no weight staging and no branches around the loads.  A wave makes ONE pass over its PIX pixels (ppb = 16 for every
-  // layer below 32 k pixels), so copying the weight set into LDS first bought nothing but a barrier; and the input loads sat
-  // each in its own divergent region behind a full wait (18 K steps x 4 dependent L2 round trips: 20 us for 28 MFLOP at
-  // FlowNet's predict_flow6).  Now: weights straight from L2 (every wave reads the same lines), inputs as buffer loads whose
-  // offset is out of range where the tap leaves the image, two K vectors per lane in flight = 12 independent loads per wait.
-  const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.x), 0, p.x_bytes, 0x00020000);
-  constexpr unsigned kOOB = 0x80000000u;
-  const int m_begin = blockIdx.x * ppb;
-  const int m_end = m_begin + ppb < p.M ? m_begin + ppb : p.M;
-  const int tap0 = lane / p.cin_groups;
-  const int cg0 = lane - tap0 * p.cin_groups;
-  for (int m = m_begin + wave * PIX; m < m_end; m += 4 * PIX) {
-    // decode PIX consecutive output pixels (one division pair, then carries)
-    int pn[PIX], py_[PIX], px_[PIX];
-    {
-      int n = m / p.HqWq;
-      const int rem = m - n * p.HqWq;
-      int oy = rem / p.Wq;
-      int ox = rem - oy * p.Wq;
-#pragma unroll
-      for (int i = 0; i < PIX; ++i) {
-        pn[i] = n; py_[i] = oy; px_[i] = ox;
-        if (++ox == p.Wq) { ox = 0; if (++oy * p.Wq == p.HqWq) { oy = 0; ++n; } }
-      }
-    }
-    float acc[NV];
-#pragma unroll
-    for (int c = 0; c < NV; ++c) acc[c] = 0.f;
-    int tap = tap0, cg = cg0;
-    constexpr int U = 2;
-    for (int v = lane; v < nvec; v += 64 * U) {
-      uint4_t wv[U][NCO], xv[U][PIX];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int vv = v + 64 * u;
-        const bool live = vv < nvec;
-        const int vc = live ? vv : 0;
-        const int ky = tap / p.kw, kx = tap - ky * p.kw;
-#pragma unroll
-        for (int c = 0; c < NCO; ++c) wv[u][c] = reinterpret_cast<const uint4_t*>(p.w + (size_t)c * p.Kpad * sizeof(T))[vc];
-#pragma unroll
-        for (int i = 0; i < PIX; ++i) {
-          const int iy = py_[i] * p.sy - p.pad + ky, ix = px_[i] * p.sy - p.pad_x + kx;
-          const bool ok = live && m + i < m_end && (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
-          const unsigned off = (unsigned)((((pn[i] * p.Hi + iy) * p.Wi + ix) * p.x_cstride + p.x_coff + cg * VEC) * (int)sizeof(T));
-          xv[u][i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc_x, ok ? off : kOOB, 0, 0);
-        }
-        cg += 64;
-        while (cg >= p.cin_groups) { cg -= p.cin_groups; ++tap; }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int i = 0; i < PIX; ++i)
-#pragma unroll
-          for (int c = 0; c < NCO; ++c) acc[i * NCO + c] = dot8(xv[u][i], wv[u][c], acc[i * NCO + c], (T*)nullptr);
-    }
-    // transpose-reduce: 8 values x 64 lanes -> value j summed over all lanes, held by lanes with (lane>>3)==j
-    float r4[4], r2[2], r1;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {   // offset 32: lower half keeps values 0..3, upper half 4..7
-      const float keep = lane & 32 ? acc[4 + j] : acc[j];
-      const float send = lane & 32 ? acc[j] : acc[4 + j];
-      r4[j] = keep + __shfl_xor(send, 32);
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {   // offset 16
-      const float keep = lane & 16 ? r4[2 + j] : r4[j];
-      const float send = lane & 16 ? r4[j] : r4[2 + j];
-      r2[j] = keep + __shfl_xor(send, 16);
-    }
-    {
-      const float keep = lane & 8 ? r2[1] : r2[0];
-      const float send = lane & 8 ? r2[0] : r2[1];
-      r1 = keep + __shfl_xor(send, 8);
-    }
-    r1 += __shfl_xor(r1, 4);
-    r1 += __shfl_xor(r1, 2);
-    r1 += __shfl_xor(r1, 1);
-    if ((lane & 7) == 0) {
-      const int vi = lane >> 3;            // which of the 8 values this lane group holds
-      const int i = vi / NCO, c = vi - i * NCO;
-      if (m + i < m_end && c < p.Cout) {
-        const size_t opix = ((size_t)pn[i] * p.Ho + py_[i]) * p.Wo + px_[i];
-        float v = r1;
-        if (p.scale) v *= p.scale[c];
-        if (p.shift) v += p.shift[c];
-        if (p.res) v += (float)reinterpret_cast<const T*>(p.res)[opix * p.res_cstride + p.res_coff + c];
-        v = apply_act(v, p.act, p.slope);
-        if (p.out_layout == FT_LAYOUT_NHWC)
-          reinterpret_cast<T*>(p.y)[opix * p.y_cstride + p.y_coff + c] = (T)v;
-        else
-          reinterpret_cast<float*>(p.y)[((size_t)pn[i] * p.Cout + c) * p.Ho * p.Wo + (size_t)py_[i] * p.Wo + px_[i]] = v;
-      }
-    }
-  }
-}
-
 // ---- host side ---------------------------------------------------------------------------------
-constexpr int kBKB = 64;       // generic kernel: bytes of K per tile row per step
-constexpr int kBP = 128;       // generic kernel: pixel tile
-// ---- predict_flow path (fp16): 3x3/s1/p1 conv to <= 2 output channels from an LDS-resident input patch ------
-// The few-output kernel above re-reads each input pixel for its 9 taps from L2; at 96x128 x 224 channels that is
-// ~0.8 GB of L2 traffic for 88 MB of input.  Here a workgroup owns an 8x16 (or 16x8) output patch: the 10x18 input
-// patch of a 64-channel chunk is DMA'd once into LDS (double-buffered over chunks, XOR-swizzled like the halo
-// kernel), thread (pixel, channel half) accumulates both outputs with v_dot2_f32_f16 against weights read as LDS
-// broadcasts, and the two channel halves are summed through LDS.  Uses the generic packed layout [Cout_pad][Kpad].
-template <int TW>
-__global__ __launch_bounds__(256, 3) void conv_pflow_kernel(const ConvParams p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int BP = 128, TH = BP / TW, NW = 4;
-  constexpr int PW = TW + 2, NPIX = (TH + 2) * PW;
-  constexpr int NPWW = (NPIX + 31) / 32;                 // patch wave-loads per wave per chunk (8 pixels per load, 4 waves)
-  constexpr int PB = NPWW * NW * 1024;
-  constexpr int WB = 9 * 2 * 128;                        // weights of one chunk: [tap][co][64 ch] fp16
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  char* const patch0 = smem;
-  char* const wts0 = smem + 2 * PB;
-  float* const red = reinterpret_cast<float*>(wts0 + 2 * WB);
-
-  int ptile;
-  {
-    const int total = p.npt;
-    const int b = blockIdx.x;
-    const int q = total >> 3, r = total & 7, xcd = b & 7, loc = b >> 3;
-    ptile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
-  const int tiles_per_img = p.h_ty * p.h_tx;
-  const int n = ptile / tiles_per_img;
-  const int trem = ptile - n * tiles_per_img;
-  const int tyi = trem / p.h_tx, txi = trem - tyi * p.h_tx;
-  const int qy0 = tyi * TH, qx0 = txi * TW;
-  const int iy_org = qy0 - 1, ix_org = qx0 - 1;
-
-  const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.x), 0, p.x_bytes, 0x00020000);
-  constexpr unsigned kOOB = 0x80000000u;
-  unsigned p_voff[NPWW];
-  {
-    const int ppl = lane >> 3, pos = lane & 7;
-#pragma unroll
-    for (int t = 0; t < NPWW; ++t) {
-      const int pp = (t * NW + wave) * 8 + ppl;
-      unsigned v = kOOB;
-      if (pp < NPIX) {
-        const int pr = pp / PW, pc = pp - pr * PW;
-        const int iy = iy_org + pr, ix = ix_org + pc;
-        if ((unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi)
-          v = (unsigned)((((n * p.Hi + iy) * p.Wi + ix) * p.x_cstride + p.x_coff) * 2 + ((pos ^ (pp & 7)) << 4));
-      }
-      p_voff[t] = v;
-    }
-  }
-  const int nchunks = (p.cin_groups + 7) >> 3;           // 64-channel chunks (cin_groups = 8-channel groups)
-  const int cin8 = p.cin_groups * 8;
-  auto load_patch = [&](int c) {
-#pragma unroll
-    for (int t = 0; t < NPWW; ++t)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (lds_ptr)(patch0 + (c & 1) * PB + (t * NW + wave) * 1024), 16, p_voff[t],
-                                               c * 128, 0, 0);
-  };
-  // weights of a chunk: 18 (tap, co) rows of 8 x 16 bytes; threads 0..143 carry one piece each
-  const int w_tapco = tid >> 3, w_piece = tid & 7;
-  const bool w_thread = tid < 144;
-  auto fetch_w = [&](int c) {
-    uint4_t v = {0u, 0u, 0u, 0u};
-    const int cg = c * 8 + w_piece, tap = w_tapco >> 1, co = w_tapco & 1;
-    if (w_thread && cg < p.cin_groups && co < p.Cout)
-      v = *reinterpret_cast<const uint4_t*>(p.w + ((size_t)co * p.Kpad + (size_t)tap * cin8 + cg * 8) * 2);
-    return v;
-  };
-  auto store_w = [&](int c, const uint4_t& v) {
-    if (w_thread) *reinterpret_cast<uint4_t*>(wts0 + (c & 1) * WB + w_tapco * 128 + w_piece * 16) = v;
-  };
-
-  const int m = tid & (BP - 1), half = tid >> 7;        // pixel of the patch, channel half of the chunk (wave-uniform)
-  const int r0 = (m / TW) * PW + (m % TW);
-  float acc0 = 0.f, acc1 = 0.f;
-
-  load_patch(0);
-  store_w(0, fetch_w(0));
-  for (int c = 0; c < nchunks; ++c) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    uint4_t wnext = {0u, 0u, 0u, 0u};
-    const bool more = c + 1 < nchunks;
-    if (more) {
-      load_patch(c + 1);
-      wnext = fetch_w(c + 1);
-    }
-    const char* pb = patch0 + (c & 1) * PB;
-    const char* wb = wts0 + (c & 1) * WB + half * 64;
-#pragma unroll 1
-    for (int tap = 0; tap < 9; ++tap) {     // not unrolled: the scheduler would hoist all 108 fragment reads and spill
-      const int r = r0 + (tap / 3) * PW + (tap % 3);
-      const char* rowp = pb + r * 128;
-      const int sw = r & 7;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const uint4_t xv = *reinterpret_cast<const uint4_t*>(rowp + (((half * 4 + k) ^ sw) << 4));
-        const uint4_t w0 = *reinterpret_cast<const uint4_t*>(wb + (tap * 2 + 0) * 128 + k * 16);
-        const uint4_t w1 = *reinterpret_cast<const uint4_t*>(wb + (tap * 2 + 1) * 128 + k * 16);
-        acc0 = dot8(xv, w0, acc0, (half_t*)nullptr);
-        acc1 = dot8(xv, w1, acc1, (half_t*)nullptr);
-      }
-    }
-    if (more) store_w(c + 1, wnext);
-  }
-  // sum the two channel halves, then bias / activation and the store
-  if (half == 1) {
-    red[m * 2] = acc0;
-    red[m * 2 + 1] = acc1;
-  }
-  __syncthreads();
-  if (half == 0) {
-    const int oy = qy0 + m / TW, ox = qx0 + m % TW;
-    if (oy < p.Ho && ox < p.Wo) {
-      float v[2] = {acc0 + red[m * 2], acc1 + red[m * 2 + 1]};
-#pragma unroll
-      for (int co = 0; co < 2; ++co) {
-        if (co < p.Cout) {
-          if (p.scale) v[co] *= p.scale[co];
-          if (p.shift) v[co] += p.shift[co];
-          v[co] = apply_act(v[co], p.act, p.slope);
-        }
-      }
-      if (p.out_layout == FT_LAYOUT_NHWC) {
-        half_t* yp = reinterpret_cast<half_t*>(p.y) + (((size_t)n * p.Ho + oy) * p.Wo + ox) * p.y_cstride + p.y_coff;
-        yp[0] = (half_t)v[0];
-        if (p.Cout > 1) yp[1] = (half_t)v[1];
-      } else {
-        float* yp = reinterpret_cast<float*>(p.y);
-        const size_t hw = (size_t)p.Ho * p.Wo, pix = (size_t)oy * p.Wo + ox;
-        yp[((size_t)n * p.Cout) * hw + pix] = v[0];
-        if (p.Cout > 1) yp[((size_t)n * p.Cout + 1) * hw + pix] = v[1];
-      }
-    }
-  }
-#endif
-}
-
-// ---- predict_flow on the matrix pipe (fp16): the 3x3 conv to <= 2 channels as ONE 1x1 GEMM to 18 (tap, co) rows per INPUT
-// pixel + a 9-term shift-and-add.  conv_pflow_kernel above still reads every input fragment nine times from LDS and runs the
-// dot products on the vector ALU (45 us at 96x128x16 x 194 channels against an 11-us byte floor); here a workgroup takes the
-// 14 x 18 input patch of a 12 x 16 output tile (252 pixels = 8 MFMA pixel tiles, two per wave), streams it ONCE through a
-// 4-deep ring of 32-channel chunks (LDS-DMA, 64-byte pixel rows, chunk key (pixel / 4) & 3: conflict-free fragment reads),
-// multiplies each chunk by the [32 x 16] weight fragments (rows tap * 2 + co, 18 live; all chunks resident in LDS in fragment
-// order), parks the fp32 [pixel][18] partials in LDS and lets 192 threads add the nine neighbours of their output pixel.
-// MFMA work: 16 instructions per 32 channels per workgroup — the kernel is a stream over its input (1.31x with the halo).
-// fp32 summation order differs from the other two kernels (channels inside a tap first), well inside the fp16 tolerance.
-__global__ __launch_bounds__(256, 2) void conv_pflow_mfma_kernel(const ConvParams p, int nchunks) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  constexpr int TW = 16, TH = 12, PW = TW + 2, NPIX = (TH + 2) * PW;   // 252
-  constexpr int NW = 4, RING = 4, CHB = 16384;                       // 256 pixel slots x 64 bytes per chunk
-  constexpr int SP = 20;                                             // floats per pixel of the partial tile (18 + pad: 16-byte rows)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l31 = lane & 31, lhi = lane >> 5;
-  char* const ring = smem;
-  char* const wts = smem + RING * CHB;                               // nchunks x 2 slices x 1 KiB
-  float* const part = reinterpret_cast<float*>(smem);                // aliases the ring once the last chunk has been read
-
-  int ptile;
-  {
-    const int total = p.npt;
-    const int b = blockIdx.x;
-    const int q = total >> 3, r = total & 7, xcd = b & 7, loc = b >> 3;
-    ptile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-  }
-  const int tiles_per_img = p.h_ty * p.h_tx;
-  const int n = ptile / tiles_per_img;
-  const int trem = ptile - n * tiles_per_img;
-  const int tyi = trem / p.h_tx, txi = trem - tyi * p.h_tx;
-  const int qy0 = tyi * TH, qx0 = txi * TW;
-
-  // ---- weights: piece (slice s, k half, row co') = 8 consecutive channels of one (tap, co); ordinary loads, before any DMA --
-  {
-    const int cin8 = p.cin_groups * 8;
-    const int npieces = nchunks * 2 * 64;
-    for (int i = tid; i < npieces; i += 256) {
-      const int sl = i >> 6, l = i & 63, row = l & 31, cg = sl * 2 + (l >> 5);
-      const int tap = row >> 1, co = row & 1;
-      uint4_t v = {0u, 0u, 0u, 0u};
-      if (row < 18 && cg < p.cin_groups && co < p.Cout)
-        v = *reinterpret_cast<const uint4_t*>(p.w + ((size_t)co * p.Kpad + (size_t)tap * cin8 + cg * 8) * 2);
-      *reinterpret_cast<uint4_t*>(wts + i * 16) = v;
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-
-  const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.x), 0, p.x_bytes, 0x00020000);
-  constexpr unsigned kOOB = 0x80000000u;
-  unsigned p_voff[4];            // 16 pixels per wave-load (4 lanes x 16 bytes each), 4 wave-loads per wave per chunk
-  {
-    const int ppl = lane >> 2, pos = lane & 3;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int pp = (t * NW + wave) * 16 + ppl;
-      unsigned v = kOOB;
-      if (pp < NPIX) {
-        const int pr = pp / PW, pc = pp - pr * PW;
-        const int iy = qy0 - 1 + pr, ix = qx0 - 1 + pc;
-        if ((unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi)
-          v = (unsigned)((((n * p.Hi + iy) * p.Wi + ix) * p.x_cstride + p.x_coff) * 2 + ((pos ^ ((pp >> 2) & 3)) << 4));
-      }
-      p_voff[t] = v;
-    }
-  }
-  auto load_chunk = [&](int c) {       // past the last chunk: out-of-range loads (zeros into a slot nobody reads) keep vmcnt uniform
-    const bool live = c < nchunks;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_b, (lds_ptr)(ring + (c & (RING - 1)) * CHB + (t * NW + wave) * 1024), 16,
-                                               live ? p_voff[t] : kOOB, live ? c * 64 : 0, 0, 0);
-  };
-  load_chunk(0);
-  load_chunk(1);
-  load_chunk(2);
-
-  float16_t acc[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-  int b_off[2];
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int pp = (wave * 2 + t) * 32 + l31;
-    b_off[t] = pp * 64 + ((lhi ^ ((pp >> 2) & 3)) << 4);
-  }
-  const int a_off = lane * 16;
-
-  for (int c = 0; c < nchunks; ++c) {
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");       // chunk c has landed (this wave's pieces); chunks c+1, c+2 may fly
-    FT_LDS_BARRIER();                                       // ... everyone's pieces; and every read of chunk c-1 is done
-    load_chunk(c + 3);
-    const char* cb = ring + (c & (RING - 1)) * CHB;
-    const char* wb = wts + c * 2048 + a_off;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const uint4_t fa = *reinterpret_cast<const uint4_t*>(wb + k * 1024);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const uint4_t fb = *reinterpret_cast<const uint4_t*>(cb + (b_off[t] ^ (k << 5)));
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, fa), __builtin_bit_cast(half8_t, fb), acc[t], 0, 0, 0);
-      }
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   // the dummy tail loads too: the ring becomes the partial tile
-  FT_LDS_BARRIER();
-  // ---- partials [pixel][18]: accumulator register r of lane (pixel, half) is row 8 * (r / 4) + 4 * half + r % 4 -------------
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int pp = (wave * 2 + t) * 32 + l31;
-#pragma unroll
-    for (int g = 0; g < 3; ++g) {
-      const int row0 = g * 8 + lhi * 4;
-      if (row0 < 18)
-        *reinterpret_cast<float4_t*>(part + pp * SP + row0) = float4_t{acc[t][g * 4], acc[t][g * 4 + 1], acc[t][g * 4 + 2], acc[t][g * 4 + 3]};
-    }
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  FT_LDS_BARRIER();
-  if (tid < TW * TH) {
-    const int oy_l = tid / TW, ox_l = tid - oy_l * TW;
-    const int oy = qy0 + oy_l, ox = qx0 + ox_l;
-    float v[2] = {0.f, 0.f};
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      const float2 s2 = *reinterpret_cast<const float2*>(part + ((oy_l + tap / 3) * PW + ox_l + tap % 3) * SP + tap * 2);
-      v[0] += s2.x;
-      v[1] += s2.y;
-    }
-    if (oy < p.Ho && ox < p.Wo) {
-#pragma unroll
-      for (int co = 0; co < 2; ++co) {
-        if (co < p.Cout) {
-          if (p.scale) v[co] *= p.scale[co];
-          if (p.shift) v[co] += p.shift[co];
-          v[co] = apply_act(v[co], p.act, p.slope);
-        }
-      }
-      if (p.out_layout == FT_LAYOUT_NHWC) {
-        half_t* yp = reinterpret_cast<half_t*>(p.y) + (((size_t)n * p.Ho + oy) * p.Wo + ox) * p.y_cstride + p.y_coff;
-        yp[0] = (half_t)v[0];
-        if (p.Cout > 1) yp[1] = (half_t)v[1];
-      } else {
-        float* yp = reinterpret_cast<float*>(p.y);
-        const size_t hw = (size_t)p.Ho * p.Wo, pix = (size_t)oy * p.Wo + ox;
-        yp[((size_t)n * p.Cout) * hw + pix] = v[0];
-        if (p.Cout > 1) yp[((size_t)n * p.Cout + 1) * hw + pix] = v[1];
-      }
-    }
-  }
-#endif
-}
-
-constexpr int kDmaBKB = FT_DMA_BKB;        // dma kernel: bytes of K per tile row per step (64 -> 32 fp16 / 16 fp32 channels)
-constexpr int kDmaStages = FT_DMA_STAGES;  // dma kernel: LDS ring depth
-
-static int validate(const ft_conv_desc* d) {
-  if (!d) return FT_ERR_INVALID_ARG;
-  if (d->dtype != FT_F16 && d->dtype != FT_F32) return FT_ERR_INVALID_ARG;
-  if (d->N <= 0 || d->Hi <= 0 || d->Wi <= 0 || d->Cin <= 0 || d->Cout <= 0) return FT_ERR_INVALID_ARG;
-  if (d->x_wpitch > 0) {  // row-packed input
-    if (d->transposed || d->x_coff != 0 || d->x_cstride % 4 || d->x_cstride < d->Cin) return FT_ERR_INVALID_ARG;
-    if (d->x_lpad < d->pad || d->x_wpitch < d->x_lpad + d->Wi) return FT_ERR_INVALID_ARG;
-  } else {
-    if (d->x_wpitch < 0 || d->x_lpad != 0) return FT_ERR_INVALID_ARG;
-    if (d->x_cstride % 8 || d->x_coff % 8 || d->x_coff < 0) return FT_ERR_INVALID_ARG;
-    if (d->x_cstride < d->x_coff + round_up(d->Cin, 8)) return FT_ERR_INVALID_ARG;
-  }
-  if (d->transposed) {
-    if (d->kh != 4 || d->kw != 4 || d->stride != 2 || d->pad != 1) return FT_ERR_UNSUPPORTED;
-    if (d->Ho != 2 * d->Hi || d->Wo != 2 * d->Wi) return FT_ERR_INVALID_ARG;
-  } else {
-    if (d->kh <= 0 || d->kw <= 0 || d->stride <= 0 || d->pad < 0) return FT_ERR_INVALID_ARG;
-    if (d->Ho != (d->Hi + 2 * d->pad - d->kh) / d->stride + 1) return FT_ERR_INVALID_ARG;
-    if (d->Wo != (d->Wi + 2 * d->pad - d->kw) / d->stride + 1) return FT_ERR_INVALID_ARG;
-  }
-  if (d->out_layout == FT_LAYOUT_NHWC) {
-    if (d->y_cstride % 4 || d->y_coff % 4 || d->y_coff < 0) return FT_ERR_INVALID_ARG;
-    if (d->y_cstride < d->y_coff + (d->tail_cout > 0 ? d->tail_cout : d->Cout)) return FT_ERR_INVALID_ARG;
-  } else if (d->out_layout != FT_LAYOUT_NCHW_F32) {
-    return FT_ERR_INVALID_ARG;
-  }
-  if (d->has_residual) {
-    if (d->res_cstride % 4 || d->res_coff % 4 || d->res_coff < 0) return FT_ERR_INVALID_ARG;
-    if (d->res_cstride < d->res_coff + d->Cout) return FT_ERR_INVALID_ARG;
-  }
-  if (d->act < FT_ACT_NONE || d->act > FT_ACT_LEAKY) return FT_ERR_INVALID_ARG;
-  if (d->tail_cout < 0 || d->tail_cout > 32) return FT_ERR_INVALID_ARG;
-  if (d->tail_cout > 0) {   // fused tail 1x1 conv: the whole channel dimension of a pixel tile must sit in one workgroup
-    if (d->dtype != FT_F16 || d->has_residual || d->x2_cin != 0 || !(d->Cout == 64 || d->Cout == 128 || d->Cout == 256))
-      return FT_ERR_UNSUPPORTED;
-  }
-  if (d->pool != 0 && d->pool != 1) return FT_ERR_INVALID_ARG;
-  if (d->x2_cin < 0) return FT_ERR_INVALID_ARG;
-  if (d->x2_cin > 0) {   // second input (K-concat): 1x1 / stride 1 or transposed 4x4 / stride 2 main conv, no residual, plain NHWC views
-    if (!d->transposed && (d->kh != 1 || d->kw != 1 || d->stride != 1 || d->pad != 0)) return FT_ERR_UNSUPPORTED;
-    if (d->has_residual || d->x_wpitch > 0) return FT_ERR_UNSUPPORTED;
-    if (d->x2_stride <= 0 || d->x2_hi <= 0 || d->x2_wi <= 0 || d->x2_cstride % 8 || d->x2_coff % 8 || d->x2_coff < 0)
-      return FT_ERR_INVALID_ARG;
-    if (d->x2_cstride < d->x2_coff + round_up(d->x2_cin, 8)) return FT_ERR_INVALID_ARG;
-    // behind a transposed conv x2 is given at the output geometry: every phase reads it at its own output pixels
-    if (d->transposed && (d->x2_stride != 1 || d->x2_hi != d->Ho || d->x2_wi != d->Wo)) return FT_ERR_INVALID_ARG;
-    if (d->Ho != (d->x2_hi - 1) / d->x2_stride + 1 || d->Wo != (d->x2_wi - 1) / d->x2_stride + 1) return FT_ERR_INVALID_ARG;
-  }
-  return FT_OK;
-}
-
-// Packed-weight layout + kernel choice. Everything here depends only on (dtype, Cin, Cout, kernel,
-// transposed, x_cstride - x_coff): NOT on the batch / spatial size, so weights are packed once per layer.
-struct Geometry {
-  int nphases, ntaps, cin_pad, cout_pad, kpad;
-  int run_taps, run_cpad;         // row-packed: kernel columns per K-run and their channel stride; else 1, cin_pad
-  int dma;                        // 1: conv_igemm_dma_kernel, 0: generic conv_igemm_kernel
-  int rowpack;
-  int nk, cin_groups, vec, kc;    // K-loop bookkeeping of the chosen kernel
-  int cin2_pad, kc2;              // second input (K-concat): its padded K-run and K-steps
-};
-
-static int geometry(const ft_conv_desc* d, Geometry* g) {
-  int st = validate(d);
-  if (st != FT_OK) return st;
-  const int esz = d->dtype == FT_F16 ? 2 : 4;
-  g->vec = 16 / esz;
-  g->nphases = d->transposed ? 4 : 1;
-  g->ntaps = d->transposed ? 4 : d->kh * d->kw;
-  const int bk = kDmaBKB / esz;
-  g->rowpack = 0;
-  g->cin2_pad = g->kc2 = 0;
-  if (d->x_wpitch > 0) {
-    // one K-run = one kernel row: kw taps x x_cstride channels, padded to whole K-steps with zero weights
-    if (d->Cout <= 32 || d->kh > 32) return FT_ERR_UNSUPPORTED;
-    const int run = round_up(d->kw * d->x_cstride, bk);
-    if ((long long)128 * d->kh * run * esz >= (1LL << 31)) return FT_ERR_UNSUPPORTED;
-    g->rowpack = g->dma = 1;
-    g->ntaps = d->kh;
-    g->cin_pad = run;
-    g->cout_pad = round_up(d->Cout, d->Cout % 128 == 0 ? 128 : 64);
-    g->kc = run / bk;
-    g->nk = g->ntaps * g->kc;
-    g->kpad = g->ntaps * run;
-    g->cin_groups = 0;
-    g->run_taps = d->kw;
-    g->run_cpad = d->x_cstride;
-    return FT_OK;
-  }
-  const int cin_bk = round_up(d->Cin, bk);
-  const long long wbytes = (long long)128 * g->ntaps * cin_bk * esz;  // one co tile of packed weights
-  // Cout <= 32 runs on the generic kernel (a 64-wide channel tile would idle half of it) — except 3x3/s1 layers with
-  // 16..32 outputs at high resolution (FlowNetFusion inter_conv0/1): channel-aligned layout + LDS-patch (halo) kernel
-  // cut their operand traffic so much that the idle half does not matter (inter_conv1: 680 -> 324 us before the patch)
-  // (the transposed 16..32-output layers were tried too: fusion deconv0 578 -> 514 us, deconv1 91 -> 103 us: left alone)
-  const bool small_3x3 = d->Cout >= 16 && !d->transposed && d->kh == 3 && d->kw == 3 && d->stride == 1;
-  g->dma = (d->Cout > 32 || small_3x3) && g->ntaps <= 32 && d->x_cstride >= d->x_coff + cin_bk && wbytes < (1LL << 31);
-  if (d->x2_cin > 0) {     // K-concat needs the channel-aligned kernel for both inputs
-    const int cin2_bk = round_up(d->x2_cin, bk);
-    if (!g->dma || d->x2_cstride < d->x2_coff + cin2_bk || cin_bk / bk < 2) return FT_ERR_UNSUPPORTED;
-    g->cin2_pad = cin2_bk;
-    g->kc2 = cin2_bk / bk;
-  }
-  if (g->dma) {
-    g->cin_pad = cin_bk;
-    g->cout_pad = round_up(d->Cout, d->Cout % 128 == 0 ? 128 : 64);
-    g->kc = cin_bk / bk;
-    g->nk = g->ntaps * g->kc + g->kc2;
-    g->kpad = g->ntaps * cin_bk + g->cin2_pad;
-    g->cin_groups = 0;
-  } else {
-    g->cin_pad = round_up(d->Cin, 8);
-    const int bc = d->Cout <= 32 ? 32 : (d->Cout % 128 == 0 ? 128 : 64);
-    g->cout_pad = round_up(d->Cout, bc);
-    g->cin_groups = g->cin_pad / g->vec;
-    const int ch = kBKB / 16;
-    g->nk = ceil_div(g->ntaps * g->cin_groups, ch);
-    g->kpad = g->nk * ch * g->vec;
-    g->kc = 0;
-  }
-  g->run_taps = 1;
-  g->run_cpad = g->cin_pad;
-  return FT_OK;
-}
-
 template <typename T, int BC, int WGP, int WGC>
 static void launch_generic(const ConvParams& p, dim3 grid, hipStream_t s) {
   constexpr size_t lds = 2 * (size_t)(BC + kBP) * kBKB + (size_t)kBP * 8;  // 2 stages + per-row output offsets
@@ -2357,12 +1795,6 @@ static int launch_dma(const ConvParams& p, dim3 grid, hipStream_t s) {
   return launch_dma_r<T, BP, BC, WGP, WGC, false, KS, BKB, S>(p, grid, s);
 }
 
-// "wide-K" variants (fp16): 128 bytes of K per tile row per step = whole 128-byte lines per row from L2, half the
-// barriers and K-steps; twice the LDS per stage, so fewer stages / workgroups per CU.  Offered to the tile benchmark
-// for the layers whose K-loop is latency-bound (few workgroups, long K).
-constexpr int kHintWideShift = 28;   // tile_hint bits 28-29: wide-K level w, BKB = 64 << w
-
-// Tile variants the dma kernel is instantiated for (ft_conv_tile_candidates / ft_conv_desc.tile_hint).
 #ifndef FT_HALO_CCH
 #define FT_HALO_CCH 32   // channels per resident patch chunk of the 3x3 variant (same-box A/B vs 64: +2.4 % R50, +0.8 % FlowNet2S)
 #endif
@@ -2403,7 +1835,7 @@ static bool stem_persist_plan(const ft_conv_desc* d, const Geometry& g, int* pw_
   return true;
 }
 
-static int launch_stem(ConvParams p, const ft_conv_desc* d, const Geometry& g, hipStream_t s) {
+int launch_stem(ConvParams p, const ft_conv_desc* d, const Geometry& g, hipStream_t s) {
   const int runb = g.cin_pad * 2, cpb = d->x_cstride * 2;
   const int ph = 7 * d->stride + d->kh;
   // super-tile = nt tiles of 8x16 outputs side by side share one pass over the weights.  Measured (in situ, us):
@@ -2463,10 +1895,8 @@ static int launch_stem(ConvParams p, const ft_conv_desc* d, const Geometry& g, h
   return FT_OK;
 }
 
-static bool stem_ok(const ft_conv_desc* d, const Geometry& g);
-
 // ft_conv_desc.pool: the pose stem with its max-pool fused (conv_stem_pool_kernel)
-static int launch_stem_pool(ConvParams p, const ft_conv_desc* d, const Geometry& g, hipStream_t s) {
+int launch_stem_pool(ConvParams p, const ft_conv_desc* d, const Geometry& g, hipStream_t s) {
   const int runb = g.cin_pad * 2, cpb = d->x_cstride * 2;
   if (!stem_ok(d, g) || d->kh != 7 || runb != 64 || d->act != FT_ACT_RELU || d->Ho % 2 || d->Wo % 2 || d->x_lpad < d->pad + 2 ||
       ((d->x_lpad - d->pad - 2) * cpb) % 16 != 0)
@@ -2491,7 +1921,7 @@ static int launch_stem_pool(ConvParams p, const ft_conv_desc* d, const Geometry&
   return FT_OK;
 }
 
-static int launch_halo(ConvParams p, const ft_conv_desc* d, const Geometry& g, int bc, hipStream_t s) {
+int launch_halo(ConvParams p, const ft_conv_desc* d, const Geometry& g, int bc, hipStream_t s) {
   if (g.rowpack) return launch_stem(p, d, g, s);
   const int Hq = p.HqWq / p.Wq, Wq = p.Wq;
   const int kq = d->transposed ? 2 : 3;                      // taps per dimension of one phase
@@ -2528,11 +1958,7 @@ static int launch_halo(ConvParams p, const ft_conv_desc* d, const Geometry& g, i
   return FT_OK;
 }
 
-constexpr int kHintHalo = 1 << 30;   // tile_hint bit 30: LDS-resident input patch (conv_halo_kernel)
-
-// conv_halo_kernel: fp16, 3x3 / stride 1 or the 2x2-tap phases of ConvTranspose2d(4,2,1), NHWC fp16 8-aligned output,
-// no residual, channel-aligned (dma) weight layout
-static bool stem_ok(const ft_conv_desc* d, const Geometry& g) {
+bool stem_ok(const ft_conv_desc* d, const Geometry& g) {
   if (!g.rowpack || d->dtype != FT_F16 || d->has_residual || d->Cout != 64 || d->x_coff != 0) return false;
   if (!((d->kh == 7 && d->stride == 2) || (d->kh == 3 && d->stride == 1))) return false;
   const int runb = g.cin_pad * 2;
@@ -2541,7 +1967,9 @@ static bool stem_ok(const ft_conv_desc* d, const Geometry& g) {
   return d->out_layout == FT_LAYOUT_NHWC && d->y_coff % 8 == 0 && d->y_cstride % 8 == 0;
 }
 
-static bool halo_ok(const ft_conv_desc* d, const Geometry& g) {
+// conv_halo_kernel: fp16, 3x3 / stride 1 or the 2x2-tap phases of ConvTranspose2d(4,2,1), NHWC fp16 8-aligned output,
+// no residual, channel-aligned (dma) weight layout
+bool halo_ok(const ft_conv_desc* d, const Geometry& g) {
   if (g.rowpack) return stem_ok(d, g);
   if (!g.dma || d->dtype != FT_F16 || d->has_residual) return false;
   if (!(d->transposed || (d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1))) return false;
@@ -2549,7 +1977,7 @@ static bool halo_ok(const ft_conv_desc* d, const Geometry& g) {
 }
 
 // ft_conv_desc.shift_nstride: the persistent row-packed 7x7 / stride 2 fp16 stem only
-static bool shift_n_ok(const ft_conv_desc* d, const Geometry& g) {
+bool shift_n_ok(const ft_conv_desc* d, const Geometry& g) {
   if (d->shift_nstride < d->Cout || d->shift_nstride % 4 || d->pool || d->tail_cout > 0 || d->x2_cin > 0 || d->kh != 7 || d->stride != 2)
     return false;
   if (!stem_ok(d, g)) return false;
@@ -2559,542 +1987,8 @@ static bool shift_n_ok(const ft_conv_desc* d, const Geometry& g) {
   return stem_persist_plan(d, g, &pw, &npww, &lds, &ntiles);
 }
 
-extern "C" int ft_conv_shift_nstride_supported(const ft_conv_desc* d) {
-  Geometry g;
-  const int st = geometry(d, &g);
-  if (st != FT_OK) return st;
-  return shift_n_ok(d, g) ? FT_OK : FT_ERR_UNSUPPORTED;
-}
-
-constexpr int kHintSkShift = 21;     // tile_hint bits 21-23: the cross-workgroup K split (needs a workspace): codes 0..3 = 1, 2, 4, 8
-                                     // slices (log2, as before); 4..7 = 3, 5, 6, 7 slices (8-phase kernel only: 48 tiles x 5 = 240
-                                     // workgroups fill 256 CUs where x 4 leaves a quarter of them idle)
-__host__ __device__ constexpr int hint_sk(int code) { return code < 4 ? 1 << code : (code == 4 ? 3 : code + 0); }   // 5, 6, 7 are themselves
-constexpr int sk_code(int sk) { return sk == 1 ? 0 : sk == 2 ? 1 : sk == 4 ? 2 : sk == 8 ? 3 : sk == 3 ? 4 : sk; }
-
-constexpr int kWide8 = 3;           // tile_hint bits 28-29 == 3: the 256 x 256 tile on the 8-phase schedule (conv_igemm8.hip)
-
-// conv_igemm8_kernel: fp16, channel-aligned layout, 64-channel K-tiles (cin_pad % 64 == 0), all-256-channel tiles, no second input
-static bool igemm8_ok(const ft_conv_desc* d, const Geometry& g) {
-  if (!(g.dma && !g.rowpack && d->dtype == FT_F16 && g.kc2 == 0 && g.kc % 2 == 0 && g.cout_pad % 256 == 0 && g.nk / 2 >= 2)) return false;
-  if (d->has_residual) return false;     // results leave straight from the accumulator registers: no residual pick-up
-  if ((unsigned long long)g.nphases * g.cout_pad * g.kpad * 2 >= (1ull << 31)) return false;   // one buffer descriptor over all weights
-  if (g.cout_pad > 1024) return false;   // folded-BN scale / shift of every output channel sit in 8 KiB of LDS
-  if (d->tail_cout > 0) return d->Cout == 256 && d->tail_cout <= 24;   // (the channel halves exchange 12 registers = 24 outputs)
-  if (!(d->out_layout == FT_LAYOUT_NHWC && d->Cout % 8 == 0 && d->y_coff % 8 == 0 && d->y_cstride % 8 == 0)) return false;
-  return (unsigned long long)d->N * d->Ho * d->Wo * d->y_cstride * 2 < (1ull << 31);
-}
-
-static bool tile_valid(const ft_conv_desc* d, const Geometry& g, int bp, int bc, int ks, int wide = 0, bool halo = false,
-                       int sk = 1) {
-  if (!g.dma) return false;
-  if (wide == kWide8) {
-    if (!igemm8_ok(d, g) || bp != 256 || bc != 256 || ks != 1 || halo) return false;
-    if (sk != 1) {     // every K slice = ceil(K-tiles / sk) but the last, which must still hold two K-tiles (the kernel's tile hand-over)
-      const int nk8 = g.nk / 2, per = (nk8 + sk - 1) / sk;
-      if (sk < 2 || sk > 8 || d->tail_cout > 0 || per < 4 || nk8 - (sk - 1) * per < 2) return false;
-    }
-    return true;
-  }
-  if (sk != 1) {     // split-K across workgroups: fp32 partial tiles in a workspace + a reduce launch
-    if (!(sk == 2 || sk == 4 || sk == 8) || ks != 1 || halo || g.kc2 > 0 || d->tail_cout > 0 || g.rowpack || bp > 128) return false;
-    if ((g.nk >> wide) / sk < 4) return false;
-  }
-  if (g.kc2 > 0) {   // K-concat runs in the lean loop only: no split-K, no halo; wide-K needs whole wide steps of both runs
-    if (ks != 1 || halo) return false;
-    if (wide && (g.kc2 % 2 != 0 || (g.kc >> 1) < 2)) return false;
-  }
-  if (halo) return halo_ok(d, g) && bp == 128 && (bc == 64 || (bc == 128 && !g.rowpack)) && g.cout_pad % bc == 0 && ks == 1 && wide == 0;
-  if (wide < 0 || wide > 1) return false;   // (BKB = 256 was benchmarked too: never the fastest on any layer)
-  if (wide && !(d->dtype == FT_F16 && g.kc % (1 << wide) == 0)) return false;
-  if (wide && ks > 1) return false;         // (wide + split-K likewise)
-  if (bc == 256) {   // all-256-channel tiles (8 waves at 128 pixels, 4 at 64): the pixel tile is loaded once per 256 outputs
-    if (!(d->dtype == FT_F16 && (bp == 64 || bp == 128 || bp == 256) && ks == 1 && sk == 1 && g.cout_pad % 256 == 0)) return false;
-    if (bp == 256 && wide != 1) return false;   // 256 x 256 (8 waves, half the operand bytes per MAC of 128 x 128): wide-K form only
-    return true;
-  }
-  if (!((bp == 64 || bp == 128 || bp == 256) && (bc == 64 || bc == 128) && (ks == 1 || ks == 2 || ks == 4))) return false;
-  if (g.cout_pad % bc != 0) return false;
-  if (bp == 256 && !(bc == 128 && d->dtype == FT_F16 && ks == 1)) return false;
-  if (ks > 1) {
-    if (d->dtype != FT_F16 || (bp == 128 && bc == 64) || (ks == 4 && bp == 128)) return false;
-    if ((g.nk >> wide) < 2 * ks) return false;
-    if ((size_t)ks * kDmaStages * (bc + bp) * (kDmaBKB << wide) + 2048 + (size_t)bp * 8 > 160 * 1024) return false;
-  }
-  return true;
-}
-
-}  // namespace ft
-
-using namespace ft;
-
-extern "C" int ft_conv_tile_candidates(const ft_conv_desc* d, int* hints, int max) {
-  Geometry g;
-  int st = geometry(d, &g);
-  if (st != FT_OK) return -st;
-  if (!hints || max <= 0) return -FT_ERR_INVALID_ARG;
-  if (d->pool) return 0;            // one kernel
-  if (d->tail_cout > 0) {           // pixel tile x ALL channels: the 128-pixel 8-wave tile (the default) or the 8-phase 256 x 256 tile
-    if (max < 2 || d->Cout != 256 || !tile_valid(d, g, 256, 256, 1, kWide8)) return 0;
-    hints[0] = 128 | (256 << 12) | (1 << 24);
-    hints[1] = 256 | (256 << 12) | (1 << 24) | (kWide8 << kHintWideShift);
-    return 2;
-  }
-  static const int kTiles[5][2] = {{256, 128}, {128, 128}, {128, 64}, {64, 128}, {64, 64}};
-  int n = 0;
-  for (const auto& t : kTiles)
-    for (int ks = 1; ks <= 4; ks <<= 1)
-      if (n < max && tile_valid(d, g, t[0], t[1], ks)) hints[n++] = t[0] | (t[1] << 12) | (ks << 24);
-  for (const auto& t : kTiles)
-    if (n < max && tile_valid(d, g, t[0], t[1], 1, 1)) hints[n++] = t[0] | (t[1] << 12) | (1 << 24) | (1 << kHintWideShift);
-  for (int bp = 256; bp >= 64; bp >>= 1)
-    for (int wide = 0; wide <= 1; ++wide)
-      if (n < max && tile_valid(d, g, bp, 256, 1, wide)) hints[n++] = bp | (256 << 12) | (1 << 24) | (wide << kHintWideShift);
-  // the 8-phase 256 x 256 tile, and its cross-workgroup split-K forms where the layer has fewer such tiles than CUs
-  if (n < max && tile_valid(d, g, 256, 256, 1, kWide8)) {
-    hints[n++] = 256 | (256 << 12) | (1 << 24) | (kWide8 << kHintWideShift);
-    const int Hq8 = d->transposed ? d->Hi : d->Ho, Wq8 = d->transposed ? d->Wi : d->Wo;
-    const long long nblk8 = (long long)ceil_div(d->N * Hq8 * Wq8, 256) * (g.cout_pad / 256) * g.nphases;
-    for (int lg = 1; lg <= 3; ++lg)
-      if (n < max && nblk8 <= 160 && (nblk8 << lg) <= 640 && tile_valid(d, g, 256, 256, 1, kWide8, false, 1 << lg))
-        hints[n++] = 256 | (256 << 12) | (1 << 24) | (kWide8 << kHintWideShift) | (lg << kHintSkShift);
-    // odd splits where they bring the workgroup count closer to one round of 256 CUs than the neighbouring powers of two
-    // (deconv.0 of the pose head at batch 64: 48 tiles x 5 slices = 240 workgroups; x 4 = 192, x 8 = 384)
-    for (int sk = 3; sk <= 7; ++sk) {
-      if (sk == 4) continue;
-      if (n < max && nblk8 <= 160 && nblk8 * sk > 160 && nblk8 * sk <= 272 && tile_valid(d, g, 256, 256, 1, kWide8, false, sk))
-        hints[n++] = 256 | (256 << 12) | (1 << 24) | (kWide8 << kHintWideShift) | (sk_code(sk) << kHintSkShift);
-    }
-  }
-  // cross-workgroup split-K where the layer has less than ~one workgroup per CU even on 64-wide tiles (long K, few
-  // pixels: layer4 / FlowNet conv5..6 / every deep layer at small batch).  Needs ft_conv2d_fwd_ws.
-  {
-    const int Hq = d->transposed ? d->Hi : d->Ho, Wq = d->transposed ? d->Wi : d->Wo;
-    const long long M = (long long)d->N * Hq * Wq;
-    static const int kSkTiles[3][2] = {{128, 128}, {64, 128}, {64, 64}};
-    constexpr int sk_max_blocks = 256;
-    for (const auto& t : kSkTiles) {
-      if (g.cout_pad % t[1] != 0) continue;
-      const long long nblk = (long long)ceil_div((int)M, t[0]) * (g.cout_pad / t[1]) * g.nphases;
-      const int wide = tile_valid(d, g, t[0], t[1], 1, 1) ? 1 : 0;
-      for (int lg = 1; lg <= 3; ++lg)
-        if (n < max && nblk <= sk_max_blocks && (nblk << lg) <= 4 * sk_max_blocks + 512 && tile_valid(d, g, t[0], t[1], 1, wide, false, 1 << lg))
-          hints[n++] = t[0] | (t[1] << 12) | (1 << 24) | (wide << kHintWideShift) | (lg << kHintSkShift);
-    }
-  }
-  for (int bc = 128; bc >= 64; bc >>= 1)
-    if (n < max && tile_valid(d, g, 128, bc, 1, 0, true)) hints[n++] = 128 | (bc << 12) | (1 << 24) | kHintHalo;
-  return n;
-}
-
-extern "C" int ft_conv_pack_geometry(const ft_conv_desc* d, ft_conv_geometry* out) {
-  Geometry g;
-  int st = geometry(d, &g);
-  if (st != FT_OK) return st;
-  if (!out) return FT_ERR_INVALID_ARG;
-  out->nphases = g.nphases;
-  out->ntaps = g.ntaps;
-  out->cin_pad = g.cin_pad;
-  out->cout_pad = g.cout_pad;
-  out->kpad = g.kpad;
-  out->run_taps = g.run_taps;
-  out->run_cpad = g.run_cpad;
-  out->cin2_pad = g.cin2_pad;
-  return FT_OK;
-}
-
-extern "C" int ft_conv_tap_source(const ft_conv_desc* d, int phase, int tap, int sub, int* ky, int* kx) {
-  Geometry g;
-  int st = geometry(d, &g);
-  if (st != FT_OK) return st;
-  if (phase < 0 || phase >= g.nphases || tap < 0 || tap >= g.ntaps || sub < 0 || sub >= g.run_taps || !ky || !kx)
-    return FT_ERR_INVALID_ARG;
-  if (g.rowpack) {
-    *ky = tap;
-    *kx = sub;
-  } else if (d->transposed) {
-    // out[2q+p] takes in[q + p - t] * W[k],  k = (p == 0) ? 1 + 2t : 2t   
-    const int py = phase >> 1, px = phase & 1, ty = tap >> 1, tx = tap & 1;
-    *ky = py == 0 ? 1 + 2 * ty : 2 * ty;
-    *kx = px == 0 ? 1 + 2 * tx : 2 * tx;
-  } else {
-    *ky = tap / d->kw;
-    *kx = tap % d->kw;
-  }
-  return FT_OK;
-}
-
-extern "C" double ft_conv_flops(const ft_conv_desc* d) {
-  if (validate(d) != FT_OK) return 0.0;
-  const double taps = d->transposed ? 4.0 : (double)d->kh * d->kw;  // per output pixel
-  return 2.0 * d->N * (double)d->Ho * d->Wo * d->Cout * ((double)d->Cin * taps + (double)d->x2_cin + (double)d->tail_cout);
-}
-
-extern "C" size_t ft_conv_workspace_bytes(const ft_conv_desc* d) {
-  int hints[64];     // every form the enumeration can produce (15 + 5 + 6 + 4 + 9 + 2 = 41): nothing truncated, max_sk is the true maximum
-  const int n = ft_conv_tile_candidates(d, hints, 64);
-  int max_sk = 1;
-  for (int i = 0; i < n; ++i) {
-    const int sk = hint_sk((hints[i] >> kHintSkShift) & 7);
-    if (sk > max_sk) max_sk = sk;
-  }
-  if (max_sk == 1) return 0;                 // no split-K variant is offered for this layer
-  Geometry g;
-  if (geometry(d, &g) != FT_OK) return 0;
-  const int Hq = d->transposed ? d->Hi : d->Ho, Wq = d->transposed ? d->Wi : d->Wo;
-  return (size_t)max_sk * g.nphases * d->N * Hq * Wq * g.cout_pad * sizeof(float);
-}
-
-static int conv2d_fwd_impl(const ft_conv_desc* d, const void* x, const void* w_packed, const float* scale, const float* shift,
-                           const void* residual, void* y, void* workspace, size_t workspace_bytes, ft_stream_t stream);
-
-extern "C" int ft_conv2d_fwd(const ft_conv_desc* d, const void* x, const void* w_packed,
-                             const float* scale, const float* shift, const void* residual, void* y,
-                             ft_stream_t stream) {
-  return conv2d_fwd_impl(d, x, w_packed, scale, shift, residual, y, nullptr, 0, stream);
-}
-
-extern "C" int ft_conv2d_fwd_ws(const ft_conv_desc* d, const void* x, const void* w_packed,
-                                const float* scale, const float* shift, const void* residual, void* y,
-                                void* workspace, size_t workspace_bytes, ft_stream_t stream) {
-  if (workspace && (reinterpret_cast<uintptr_t>(workspace) & 15)) return FT_ERR_INVALID_ARG;
-  return conv2d_fwd_impl(d, x, w_packed, scale, shift, residual, y, workspace, workspace_bytes, stream);
-}
-
-static int conv2d_fwd_impl(const ft_conv_desc* d, const void* x, const void* w_packed, const float* scale, const float* shift,
-                           const void* residual, void* y, void* workspace, size_t workspace_bytes, ft_stream_t stream) {
-  Geometry g;
-  int st = geometry(d, &g);
-  if (st != FT_OK) return st;
-  if (!x || !w_packed || !y) return FT_ERR_INVALID_ARG;
-  if (d->has_residual && !residual) return FT_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w_packed) |
-       reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(residual) |
-       reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift)) & 15)
-    return FT_ERR_INVALID_ARG;
-
-  ConvParams p;
-  p.x = static_cast<const char*>(x);
-  p.w = static_cast<const char*>(w_packed);
-  p.scale = scale;
-  p.shift = shift;
-  p.res = d->has_residual ? static_cast<const char*>(residual) : nullptr;
-  p.y = static_cast<char*>(y);
-  const int Hq = d->transposed ? d->Hi : d->Ho;
-  const int Wq = d->transposed ? d->Wi : d->Wo;
-  p.M = d->N * Hq * Wq;
-  p.HqWq = Hq * Wq;
-  p.Wq = Wq;
-  p.Hi = d->Hi;
-  p.Wi = d->Wi;
-  p.sy = d->transposed ? 1 : d->stride;
-  p.x_cstride = d->x_cstride;
-  p.x_coff = d->x_coff;
-  p.kh = d->transposed ? 2 : d->kh;
-  p.kw = d->transposed ? 2 : d->kw;
-  p.dmul = d->transposed ? -1 : 1;
-  p.pad = d->pad;
-  p.pad_x = d->pad;
-  p.transposed = d->transposed;
-  if (g.rowpack) {      // the kernel sees a (kh x 1)-tap conv over the physically padded rows
-    p.kw = 1;
-    p.Wi = d->x_wpitch;
-    p.pad_x = d->pad - d->x_lpad;
-  }
-  p.cin_groups = g.cin_groups;
-  p.kc = g.kc;
-  p.nk = g.nk;
-  p.sk = 1;
-  p.ws = nullptr;
-  p.tail_w = nullptr;
-  p.tail_cout = 0;
-  p.x2 = nullptr;
-  p.kc2 = g.kc2;
-  if (g.kc2 > 0) {
-    if (!residual) return FT_ERR_INVALID_ARG;
-    const unsigned long long x2b = (unsigned long long)d->N * d->x2_hi * d->x2_wi * d->x2_cstride * dtype_size(d->dtype);
-    if (x2b >= (1ull << 31)) return FT_ERR_UNSUPPORTED;
-    p.x2 = static_cast<const char*>(residual);
-    p.x2_bytes = (unsigned)x2b;
-    p.x2_hi = d->x2_hi; p.x2_wi = d->x2_wi; p.x2_cstride = d->x2_cstride; p.x2_coff = d->x2_coff; p.x2_stride = d->x2_stride;
-  }
-  p.Kpad = g.kpad;
-  p.Cout = d->Cout;
-  p.Cout_pad = g.cout_pad;
-  p.Ho = d->Ho;
-  p.Wo = d->Wo;
-  p.omul = d->transposed ? 2 : 1;
-  p.y_cstride = d->y_cstride;
-  p.y_coff = d->y_coff;
-  p.out_layout = d->out_layout;
-  p.res_cstride = d->res_cstride;
-  p.res_coff = d->res_coff;
-  p.act = d->act;
-  p.slope = d->slope;
-  p.nph = g.nphases;
-  static const int dbg = dev_env_int("FT_CONV_DBG", 0);
-  p.dbg = dbg;
-  p.shift_n = d->shift_nstride;
-  p.x_planar = 0;
-  p.x_lpad = d->x_lpad;
-  p.x_w = d->Wi;
-  p.x_c = d->Cin;
-  if (d->x_nchw_f32 != 0 && (!d->pool || !g.rowpack || d->x_cstride != 4 || d->Cin > 3 || d->dtype != FT_F16)) return FT_ERR_UNSUPPORTED;
-  p.epi_lds = d->dtype == FT_F16 && d->out_layout == FT_LAYOUT_NHWC && d->Cout % 8 == 0 && d->y_coff % 8 == 0 &&
-              d->y_cstride % 8 == 0 && (!d->has_residual || (d->res_coff % 8 == 0 && d->res_cstride % 8 == 0));
-  hipStream_t s = as_stream(stream);
-  const size_t esz = dtype_size(d->dtype);
-  const unsigned long long x_bytes =
-      (unsigned long long)d->N * d->Hi * (d->x_wpitch > 0 ? d->x_wpitch : d->Wi) * d->x_cstride * esz;
-
-  if (d->shift_nstride != 0) {      // per-sample shift: straight to the persistent stem, the one kernel that reads it
-    if (!shift || !shift_n_ok(d, g)) return FT_ERR_UNSUPPORTED;
-    p.x_bytes = (unsigned)x_bytes;
-    return launch_stem(p, d, g, s);
-  }
-  if (d->pool) {            // stem + max-pool: y is the pooled [N, Ho/2, Wo/2, Cout] map
-    if (!g.rowpack || x_bytes >= (1ull << 31) || d->tail_cout > 0 || d->x2_cin > 0 || d->has_residual) return FT_ERR_UNSUPPORTED;
-    p.x_bytes = (unsigned)x_bytes;
-    p.x_planar = d->x_nchw_f32 != 0;
-    if (p.x_planar) {       // the buffer descriptor then covers the fp32 planes
-      const unsigned long long pb = (unsigned long long)d->N * d->Cin * d->Hi * d->Wi * 4;
-      if (pb >= (1ull << 31)) return FT_ERR_UNSUPPORTED;
-      p.x_bytes = (unsigned)pb;
-    }
-    return launch_stem_pool(p, d, g, s);
-  }
-  if (d->tail_cout > 0) {   // conv + fused tail 1x1 conv: 128 pixels x all Cout channels per workgroup
-    if (!g.dma || g.rowpack || x_bytes >= (1ull << 31) || g.cout_pad != d->Cout) return FT_ERR_UNSUPPORTED;
-    if (!residual) return FT_ERR_INVALID_ARG;
-    p.x_bytes = (unsigned)x_bytes;
-    p.tail_w = static_cast<const char*>(residual);
-    p.tail_cout = d->tail_cout;
-    p.epi_lds = 1;
-    // the 128-pixel tile (two workgroups per CU) unless the hint asks for the 8-phase 256 x 256 tile; a 256-pixel wide-K dma tile
-    // was tried and was slower: profiles/HISTORY.md
-    const bool want8 = ((d->tile_hint >> kHintWideShift) & 3) == kWide8;
-    if (want8 && d->Cout == 256 && tile_valid(d, g, 256, 256, 1, kWide8)) {
-      p.npt = ceil_div(p.M, 256);
-      p.nct = 1;
-      p.kc = g.kc >> 1;
-      p.nk = g.nk >> 1;
-      if ((long long)p.npt * p.nph > 0x7fffffffLL) return FT_ERR_UNSUPPORTED;
-      p.y_bytes = 0;     // (the tail writes through plain pointers)
-      p.w_bytes = (unsigned)((unsigned long long)g.nphases * g.cout_pad * g.kpad * 2);
-      const int rc8 = launch_igemm8(p, (unsigned)(p.npt * p.nph), s);
-      if (rc8 != FT_OK) return rc8;
-      FT_LAUNCH_CHECK("conv_igemm8_kernel (tail)");
-      return FT_OK;
-    }
-    p.npt = ceil_div(p.M, 128);
-    p.nct = 1;
-    if ((long long)p.npt * p.nph > 0x7fffffffLL) return FT_ERR_UNSUPPORTED;
-    dim3 grid(p.npt * p.nph);
-    const int rc = d->Cout == 256 ? launch_dma<half_t, 128, 256, 2, 4>(p, grid, s)
-                   : d->Cout == 128 ? launch_dma<half_t, 128, 128, 2, 2>(p, grid, s) : launch_dma<half_t, 128, 64, 2, 2>(p, grid, s);
-    if (rc != FT_OK) return rc;
-    FT_LAUNCH_CHECK("conv_igemm_dma_kernel (tail)");
-    return FT_OK;
-  }
-  if (g.dma && x_bytes < (1ull << 31)) {
-    p.x_bytes = (unsigned)x_bytes;
-    // tile choice (launch-time only; the packed layout does not depend on it): fill the 256 CUs
-    int bc = d->Cout % 128 == 0 ? 128 : 64;
-    int bp = 128;
-    auto blocks = [&](int bp_, int bc_) { return (long long)ceil_div(p.M, bp_) * (g.cout_pad / bc_) * g.nphases; };
-    // The K-loop is bound by operand delivery L2 -> LDS (~10 TB/s chip-wide measured, same as the best GEMMs of
-    // the hardware guide): bytes per MAC = (1/BP + 1/BC) * esz, so the largest tile that still fills the chip wins.
-    if (d->dtype == FT_F16 && bc == 128 && g.ntaps * g.cin_pad > 512 && blocks(256, 128) >= 2 * 256) bp = 256;
-    if (blocks(bp, bc) < 384) bp = 64;
-    if (blocks(bp, bc) < 384 && bc == 128) bc = 64;
-    // short-K layers (1x1 bottleneck exits) are HBM-bound: smaller pixel tiles = more workgroups per CU =
-    // more bytes in flight (measured on MI355X, R50 shapes: 64x128 beats 128x128 by 10-18 % for K <= 512)
-    if (g.ntaps * g.cin_pad <= 512 && bc == 128) bp = 64;
-    // intra-workgroup split-K (fp16): few tiles + long K => take the missing waves from K, as long as every
-    // workgroup still fits on the chip in ONE round (each K-group brings its own LDS ring)
-    int ks = 1;
-    if (d->dtype == FT_F16 && bp <= 128 && !(bp == 128 && bc == 64)) {
-      const long long nblk = blocks(bp, bc);
-      const long long per_cu = (nblk + 255) / 256;
-      const size_t ring = (size_t)kDmaStages * (bc + bp) * kDmaBKB;
-      for (int cand = 4; cand >= 2; cand >>= 1) {
-        if (cand == 4 && bp == 128) continue;
-        if (per_cu * (cand * ring + 2048) <= 160 * 1024 && per_cu * cand * 4 <= 32 && g.nk >= 8 * cand && nblk <= 768) {
-          ks = cand;
-          break;
-        }
-      }
-    }
-    // few workgroups + long K: the K-loop is latency-bound (one barrier per step, <= 2 waves per SIMD), so take
-    // 128 bytes of K per step instead of splitting K (measured in situ on R50 / FlowNet2S: 15-25 % on those layers)
-    int wide = 0, sk = 1;
-    bool halo = false;
-    if (d->dtype == FT_F16 && bp <= 128 && g.kc % 2 == 0 && g.ntaps * g.cin_pad >= 512 && blocks(bp, bc) <= 768) {
-      wide = 1;
-      ks = 1;
-    }
-    if (g.kc2 > 0) {   // K-concat: lean loop only
-      ks = 1;
-      if (wide && !tile_valid(d, g, bp, bc, 1, wide)) wide = 0;
-    }
-    const int hint = d->tile_hint;       // explicit choice: the caller's benchmarked hint
-    if (hint) {
-      const int hbp = hint & 0xfff, hbc = (hint >> 12) & 0x1ff, hks = (hint >> 24) & 0xf;
-      const int hwide = (hint >> kHintWideShift) & 3;
-      const bool hhalo = (hint & kHintHalo) != 0;
-      const int hsk = hint_sk((hint >> kHintSkShift) & 7);
-      const int nbp = hbp ? hbp : bp, nbc = hbc ? hbc : bc, nks = hks ? hks : (hbp || hbc ? 1 : ks);
-      if (tile_valid(d, g, nbp, nbc, nks, hwide, hhalo, hsk)) { bp = nbp; bc = nbc; ks = nks; wide = hwide; halo = hhalo; sk = hsk; }
-    }
-    if (sk > 1 && (!workspace || workspace_bytes < (size_t)sk * g.nphases * p.M * g.cout_pad * sizeof(float))) sk = 1;
-    if (halo) return launch_halo(p, d, g, bc, s);
-    if (wide == kWide8) {
-      p.kc = g.kc >> 1;
-      p.nk = g.nk >> 1;
-      p.npt = ceil_div(p.M, 256);
-      p.nct = g.cout_pad / 256;
-      if ((long long)p.npt * p.nct * p.nph * sk > 0x7fffffffLL) return FT_ERR_UNSUPPORTED;
-      p.y_bytes = (unsigned)((unsigned long long)d->N * d->Ho * d->Wo * d->y_cstride * 2);
-      p.w_bytes = (unsigned)((unsigned long long)g.nphases * g.cout_pad * g.kpad * 2);
-      if (sk > 1) {
-        p.sk = sk;
-        p.ws = static_cast<float*>(workspace);
-      }
-      const int rc8 = launch_igemm8(p, (unsigned)(p.npt * p.nct * p.nph * sk), s);
-      if (rc8 != FT_OK) return rc8;
-      FT_LAUNCH_CHECK("conv_igemm8_kernel");
-      if (sk > 1) {
-        const size_t total = (size_t)p.nph * p.M * (p.Cout_pad / 4);
-        const unsigned rgrid = (unsigned)(total / 256 + 1 > 4096 ? 4096 : total / 256 + 1);
-        hipLaunchKernelGGL(conv_splitk_reduce_kernel<half_t>, dim3(rgrid), dim3(256), 0, s, p);
-        FT_LAUNCH_CHECK("conv_splitk_reduce_kernel");
-      }
-      return FT_OK;
-    }
-    if (wide) {
-      p.kc = g.kc >> wide;
-      p.kc2 = g.kc2 >> wide;
-      p.nk = g.nk >> wide;
-    }
-    p.npt = ceil_div(p.M, bp);
-    p.nct = g.cout_pad / bc;
-    if ((long long)p.npt * p.nct * p.nph * sk > 0x7fffffffLL) return FT_ERR_UNSUPPORTED;
-    dim3 grid(p.npt * p.nct * p.nph * sk);
-    const char* const res_saved = p.res;
-    if (sk > 1) {          // partial tiles only: the residual belongs to the reduce launch
-      p.sk = sk;
-      p.ws = static_cast<float*>(workspace);
-      p.res = nullptr;
-    }
-    int rc;
-    if (bc == 256) {
-      if (wide == 1 && bp == 256) rc = launch_dma<half_t, 256, 256, 4, 2, 1, 128, 2>(p, grid, s);
-      else if (wide == 1) rc = bp == 128 ? launch_dma<half_t, 128, 256, 2, 4, 1, 128, 2>(p, grid, s) : launch_dma<half_t, 64, 256, 1, 4, 1, 128, 2>(p, grid, s);
-      else rc = bp == 128 ? launch_dma<half_t, 128, 256, 2, 4>(p, grid, s) : launch_dma<half_t, 64, 256, 1, 4>(p, grid, s);
-    } else if (wide == 1) {
-      if (bp == 256) rc = launch_dma<half_t, 256, 128, 4, 2, 1, 128, 2>(p, grid, s);
-      else if (bp == 128 && bc == 128) rc = launch_dma<half_t, 128, 128, 2, 2, 1, 128, 2>(p, grid, s);
-      else if (bp == 128) rc = launch_dma<half_t, 128, 64, 2, 2, 1, 128, 3>(p, grid, s);
-      else if (bc == 128) rc = launch_dma<half_t, 64, 128, 2, 2, 1, 128, 3>(p, grid, s);
-      else rc = launch_dma<half_t, 64, 64, 2, 2, 1, 128, 3>(p, grid, s);
-    } else if (d->dtype == FT_F16) {
-      if (bp == 256) rc = launch_dma<half_t, 256, 128, 4, 2>(p, grid, s);
-      else if (bp == 128 && bc == 128)
-        rc = ks == 2 ? launch_dma<half_t, 128, 128, 2, 2, 2>(p, grid, s) : launch_dma<half_t, 128, 128, 2, 2>(p, grid, s);
-      else if (bp == 128) rc = launch_dma<half_t, 128, 64, 2, 2>(p, grid, s);
-      else if (bc == 128)
-        rc = ks == 4   ? launch_dma<half_t, 64, 128, 2, 2, 4>(p, grid, s)
-             : ks == 2 ? launch_dma<half_t, 64, 128, 2, 2, 2>(p, grid, s)
-                       : launch_dma<half_t, 64, 128, 2, 2>(p, grid, s);
-      else
-        rc = ks == 4   ? launch_dma<half_t, 64, 64, 2, 2, 4>(p, grid, s)
-             : ks == 2 ? launch_dma<half_t, 64, 64, 2, 2, 2>(p, grid, s)
-                       : launch_dma<half_t, 64, 64, 2, 2>(p, grid, s);
-    } else {
-      if (bp == 128 && bc == 128) rc = launch_dma<float, 128, 128, 2, 2>(p, grid, s);
-      else if (bp == 128) rc = launch_dma<float, 128, 64, 2, 2>(p, grid, s);
-      else if (bc == 128) rc = launch_dma<float, 64, 128, 2, 2>(p, grid, s);
-      else rc = launch_dma<float, 64, 64, 2, 2>(p, grid, s);
-    }
-    if (rc != FT_OK) return rc;
-    FT_LAUNCH_CHECK("conv_igemm_dma_kernel");
-    if (sk > 1) {
-      p.res = res_saved;
-      const size_t total = (size_t)p.nph * p.M * (p.Cout_pad / 4);
-      const unsigned rgrid = (unsigned)(total / 256 + 1 > 4096 ? 4096 : total / 256 + 1);
-      if (d->dtype == FT_F16) hipLaunchKernelGGL(conv_splitk_reduce_kernel<half_t>, dim3(rgrid), dim3(256), 0, s, p);
-      else hipLaunchKernelGGL(conv_splitk_reduce_kernel<float>, dim3(rgrid), dim3(256), 0, s, p);
-      FT_LAUNCH_CHECK("conv_splitk_reduce_kernel");
-    }
-    return FT_OK;
-  }
-  if (g.dma) return FT_ERR_UNSUPPORTED;  // packed for the dma layout but the activation buffer is >= 2 GiB
-
-  if (!d->transposed && d->Cout <= 2 && d->dtype == FT_F16 && d->kh == 3 && d->kw == 3 && d->stride == 1 &&
-      d->pad == 1 && !d->has_residual && d->x_wpitch == 0 && d->x_cstride % 8 == 0 && d->x_coff % 8 == 0 && x_bytes < (1ull << 31)) {
-    p.x_bytes = (unsigned)x_bytes;
-    {
-      // the matrix-pipe form (12 x 16 output tiles, input streamed once) where it applies; else the dot-product kernel
-      const int nchunks = ceil_div(g.cin_groups, 4);                 // 32-channel chunks
-      const int ty = ceil_div(d->Ho, 12), tx = ceil_div(d->Wo, 16);
-      const size_t lds = (size_t)4 * 16384 + (size_t)nchunks * 2048;
-      if ((long long)d->N * ty * tx >= 256 && lds <= 160 * 1024 &&
-          (long long)ty * 12 * tx * 16 * 100 <= (long long)d->Ho * d->Wo * 125) {     // ragged edges waste < 25 % of the tiles
-        p.h_ty = ty;
-        p.h_tx = tx;
-        p.npt = d->N * ty * tx;
-        auto k = conv_pflow_mfma_kernel;
-        if (lds > 64 * 1024) FT_RAISE_LDS(k, 160 * 1024);
-        hipLaunchKernelGGL(k, dim3(p.npt), dim3(256), lds, s, p, nchunks);
-        FT_LAUNCH_CHECK("conv_pflow_mfma_kernel");
-        return FT_OK;
-      }
-    }
-    const long long t16 = (long long)ceil_div(d->Ho, 8) * ceil_div(d->Wo, 16), t8 = (long long)ceil_div(d->Ho, 16) * ceil_div(d->Wo, 8);
-    const int tw = t16 <= t8 ? 16 : 8, th = 128 / tw;
-    p.h_ty = ceil_div(d->Ho, th);
-    p.h_tx = ceil_div(d->Wo, tw);
-    p.npt = d->N * p.h_ty * p.h_tx;
-    // one patch per workgroup walks ALL channels serially: only worth it with at least one patch per CU (measured on
-    // FlowNet2S: predict_flow2/3 75 -> 49 us, 37 -> 28 us; the deep low-resolution predict_flow4..6 stay on the
-    // few-output kernel below, which splits K over the lanes)
-    if (p.npt >= 256) {
-      const size_t lds = 2 * (size_t)6 * 4 * 1024 + 2 * 9 * 2 * 128 + 128 * 2 * 4;
-      dim3 grid(p.npt);
-      if (tw == 16) hipLaunchKernelGGL(conv_pflow_kernel<16>, grid, dim3(256), lds, s, p);
-      else hipLaunchKernelGGL(conv_pflow_kernel<8>, grid, dim3(256), lds, s, p);
-      FT_LAUNCH_CHECK("conv_pflow_kernel");
-      return FT_OK;
-    }
-  }
-  if (!d->transposed && d->Cout <= 4) {
-    const int nco = d->Cout <= 2 ? 2 : 4;
-    if (x_bytes < (1ull << 31) && g.cout_pad >= nco) {
-      p.x_bytes = (unsigned)x_bytes;
-      // pixels per workgroup: enough workgroups to fill the chip; a wave takes PIX = 8 / nco pixels per pass
-      int ppb = ceil_div(p.M, 2048);
-      ppb = ppb < 16 ? 16 : (ppb > 128 ? 128 : ppb);
-      ppb = round_up(ppb, 16);
-      dim3 grid(ceil_div(p.M, ppb));
-#define FT_FEWOUT(T, N, P)                                          \
-  do {                                                              \
-    auto k = conv_fewout_kernel<T, N, P>;                           \
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, s, p, ppb);           \
-  } while (0)
-      if (d->dtype == FT_F16) { if (nco == 2) FT_FEWOUT(half_t, 2, 4); else FT_FEWOUT(half_t, 4, 2); }
-      else { if (nco == 2) FT_FEWOUT(float, 2, 4); else FT_FEWOUT(float, 4, 2); }
-#undef FT_FEWOUT
-      FT_LAUNCH_CHECK("conv_fewout_kernel");
-      return FT_OK;
-    }
-  }
-
-  const int bc = g.cout_pad % 128 == 0 && d->Cout > 64 ? 128 : (d->Cout <= 32 ? 32 : 64);
-  p.npt = ceil_div(p.M, kBP);
-  p.nct = g.cout_pad / bc;
-  if ((long long)p.npt * p.nct * p.nph > 0x7fffffffLL) return FT_ERR_UNSUPPORTED;
-  dim3 grid(p.npt * p.nct * p.nph);
-  if (d->dtype == FT_F16) {
+int launch_generic(const ConvParams& p, int dtype, int bc, dim3 grid, hipStream_t s) {
+  if (dtype == FT_F16) {
     if (bc == 128) launch_generic<half_t, 128, 2, 2>(p, grid, s);
     else if (bc == 64) launch_generic<half_t, 64, 2, 2>(p, grid, s);
     else launch_generic<half_t, 32, 4, 1>(p, grid, s);
@@ -3106,3 +2000,66 @@ static int conv2d_fwd_impl(const ft_conv_desc* d, const void* x, const void* w_p
   FT_LAUNCH_CHECK("conv_igemm_kernel");
   return FT_OK;
 }
+
+int launch_splitk_reduce(const ConvParams& p, int dtype, hipStream_t s) {
+  const size_t total = (size_t)p.nph * p.M * (p.Cout_pad / 4);
+  const unsigned rgrid = (unsigned)(total / 256 + 1 > 4096 ? 4096 : total / 256 + 1);
+  if (dtype == FT_F16) hipLaunchKernelGGL(conv_splitk_reduce_kernel<half_t>, dim3(rgrid), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(conv_splitk_reduce_kernel<float>, dim3(rgrid), dim3(256), 0, s, p);
+  FT_LAUNCH_CHECK("conv_splitk_reduce_kernel");
+  return FT_OK;
+}
+
+// ---- the dma tile table: every tile conv_igemm_dma_kernel is instantiated for -----------------------------------------
+// find_dma_tile is the only way to a launch; tile_valid (conv_dispatch.hip) asks it whether a tile exists, and
+// ft_conv_tile_candidates offers the rows in this order.
+template <typename T, int BP, int BC, int WGP, int WGC, int KS = 1, int BKB = kDmaBKB, int S = kDmaStages>
+constexpr DmaTile dma_tile(int wide = 0) {
+  return {sizeof(T) == 2 ? FT_F16 : FT_F32, BP, BC, KS, wide, (unsigned)(KS * S * (BC + BP) * BKB), launch_dma<T, BP, BC, WGP, WGC, KS, BKB, S>};
+}
+
+constexpr int kNumDmaTiles = 24;
+constexpr DmaTile kDmaTiles[kNumDmaTiles] = {
+    // 64-byte K-steps, 64 / 128 channels; KS = 2, 4: intra-workgroup split-K (fp16)
+    dma_tile<half_t, 256, 128, 4, 2>(),
+    dma_tile<half_t, 128, 128, 2, 2>(), dma_tile<half_t, 128, 128, 2, 2, 2>(),
+    dma_tile<half_t, 128, 64, 2, 2>(),
+    dma_tile<half_t, 64, 128, 2, 2>(), dma_tile<half_t, 64, 128, 2, 2, 2>(), dma_tile<half_t, 64, 128, 2, 2, 4>(),
+    dma_tile<half_t, 64, 64, 2, 2>(), dma_tile<half_t, 64, 64, 2, 2, 2>(), dma_tile<half_t, 64, 64, 2, 2, 4>(),
+    dma_tile<float, 128, 128, 2, 2>(), dma_tile<float, 128, 64, 2, 2>(), dma_tile<float, 64, 128, 2, 2>(), dma_tile<float, 64, 64, 2, 2>(),
+    // wide-K (fp16): 128-byte K-steps on a 2- or 3-deep ring (BKB = 256 was benchmarked too: never the fastest on any layer)
+    dma_tile<half_t, 256, 128, 4, 2, 1, 128, 2>(1),
+    dma_tile<half_t, 128, 128, 2, 2, 1, 128, 2>(1),
+    dma_tile<half_t, 128, 64, 2, 2, 1, 128, 3>(1),
+    dma_tile<half_t, 64, 128, 2, 2, 1, 128, 3>(1),
+    dma_tile<half_t, 64, 64, 2, 2, 1, 128, 3>(1),
+    // all-256-channel tiles (fp16; 8 waves at 128 and 256 pixels, 4 at 64): the pixel tile is loaded once per 256 outputs.
+    // 256 x 256 (half the operand bytes per MAC of 128 x 128): wide-K form only
+    dma_tile<half_t, 256, 256, 4, 2, 1, 128, 2>(1),
+    dma_tile<half_t, 128, 256, 2, 4>(), dma_tile<half_t, 128, 256, 2, 4, 1, 128, 2>(1),
+    dma_tile<half_t, 64, 256, 1, 4>(), dma_tile<half_t, 64, 256, 1, 4, 1, 128, 2>(1),
+};
+
+constexpr bool dma_tiles_fit() {
+  // a workgroup's rings + row table + 2 KiB of slack within the CU's 160 KiB, and no (dtype, tile) listed twice
+  for (int i = 0; i < kNumDmaTiles; ++i) {
+    const DmaTile& t = kDmaTiles[i];
+    if ((size_t)t.ring + 2048 + (size_t)t.bp * 8 > 160 * 1024) return false;
+    for (int j = 0; j < i; ++j) {
+      const DmaTile& u = kDmaTiles[j];
+      if (u.dtype == t.dtype && u.bp == t.bp && u.bc == t.bc && u.ks == t.ks && u.wide == t.wide) return false;
+    }
+  }
+  return true;
+}
+static_assert(dma_tiles_fit(), "dma tile table");
+
+const DmaTile* dma_tile_at(int i) { return i >= 0 && i < kNumDmaTiles ? &kDmaTiles[i] : nullptr; }
+
+const DmaTile* find_dma_tile(int dtype, int bp, int bc, int ks, int wide) {
+  for (const DmaTile& t : kDmaTiles)
+    if (t.dtype == dtype && t.bp == bp && t.bc == bc && t.ks == ks && t.wide == wide) return &t;
+  return nullptr;
+}
+
+}  // namespace ft

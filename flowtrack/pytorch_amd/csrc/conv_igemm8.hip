@@ -35,7 +35,7 @@
 //     activated accumulators ARE the MFMA B operand of a [32 x 128] x [128 x 64 pixel] product per wave (the tail weights'
 //     K order is permuted to match), the two channel halves of the workgroup meet through a 32-KiB LDS slab.
 // Padding taps, ragged pixel tiles and K-tiles past the end are out-of-range buffer offsets (zeros).
-#include "conv_common.h"
+#include "conv_dispatch.h"
 
 namespace ft {
 

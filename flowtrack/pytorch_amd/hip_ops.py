@@ -578,10 +578,8 @@ class Program:
             _TILE_CACHE[keys[k]] = cands[k][best]
             changed += best != 0
             if verbose:
-                h = cands[k][best]
                 print(f"[tile benchmark] {self.conv_records[k][0]:28s} heuristic {times[k][0] * 1e3:7.1f} us  best {times[k][best] * 1e3:7.1f} us"
-                      f"  -> bp {h & 0xfff} bc {(h >> 12) & 0x1ff} ks {(h >> 24) & 0xf} wide {(h >> 28) & 3}{' halo' if (h >> 30) & 1 else ''}"
-                      f"{' splitK x%d' % ((1, 2, 4, 8, 3, 5, 6, 7)[(h >> 21) & 7]) if (h >> 21) & 7 else ''}", file=sys.stderr)
+                      f"  -> {tile_str(cands[k][best])}", file=sys.stderr)
         _save_tile_cache()
         return changed
 
@@ -596,6 +594,29 @@ class Program:
 # --------------------------------------------------------------------------------------------
 # fused conv / transposed conv
 # --------------------------------------------------------------------------------------------
+WIDE8 = 3     # ft_conv_tile.wide of the 256 x 256 tile on the 8-phase schedule
+
+
+def decode_tile(h: int) -> _lib.ConvTile:
+    """The fields of a conv `tile_hint` (ft_conv_tile_decode; bit layout: include/flowtrack_hip.h)."""
+    t = _lib.ConvTile()
+    check(_lib.load().ft_conv_tile_decode(int(h), ctypes.byref(t)), "ft_conv_tile_decode")
+    return t
+
+
+def encode_tile(bp: int = 0, bc: int = 0, ks: int = 0, sk: int = 1, wide: int = 0, halo: int = 0) -> int:
+    """The `tile_hint` of these fields (ft_conv_tile_encode); a field left 0 is the heuristic's."""
+    h = _lib.load().ft_conv_tile_encode(ctypes.byref(_lib.ConvTile(bp, bc, ks, sk, wide, halo)))
+    if h < 0:
+        check(-h, "ft_conv_tile_encode")
+    return h
+
+
+def tile_str(h: int) -> str:
+    t = decode_tile(h)
+    return f"bp {t.bp} bc {t.bc} ks {t.ks} wide {t.wide}{' halo' if t.halo else ''}{' splitK x%d' % t.sk if t.sk > 1 else ''}"
+
+
 def conv_geometry(d: ConvDesc) -> ConvGeometry:
     g = ConvGeometry()
     check(_lib.load().ft_conv_pack_geometry(ctypes.byref(d), ctypes.byref(g)), "ft_conv_pack_geometry")

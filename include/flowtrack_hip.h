@@ -125,7 +125,17 @@ typedef struct ft_conv_desc {
   /* 0 = let the library choose the workgroup tile; else one of the values ft_conv_tile_candidates()
    * returned for this descriptor (the pick of a plan-build-time benchmark, the counterpart of the
    * reference's `cudnn.benchmark = True`, tools/pose/main.py:59).  Only the speed depends on it, never
-   * the packed-weight layout; an inapplicable value falls back to the heuristic. */
+   * the packed-weight layout; an inapplicable value falls back to the heuristic.
+   * Bit layout (ft_conv_tile_decode / ft_conv_tile_encode below are the codec; a field left 0 is the heuristic's):
+   *   bits  0-11  bp    pixels per workgroup tile
+   *   bits 12-20  bc    output channels per workgroup tile
+   *   bits 21-23  sk    cross-workgroup K split (needs ft_conv2d_fwd_ws), as a code: 0..3 = 1, 2, 4, 8 slices,
+   *                     4..7 = 3, 5, 6, 7 slices (8-phase kernel only)
+   *   bits 24-27  ks    intra-workgroup K split (K-groups of waves, each with its own LDS ring): 1, 2 or 4
+   *   bits 28-29  wide  0 = 64 bytes of K per tile row and step, 1 = 128 ("wide-K", fp16), 3 = the 256 x 256 tile on the
+   *                     8-phase schedule
+   *   bit  30     halo  the LDS-resident input patch kernels (3x3 / stride 1, transposed phases, row-packed stems)
+   *   bit  31     0 */
   int tile_hint;
   /* Optional SECOND input summed into the same accumulator ("K-concat"):
    *   y = act(scale .* (W1 . x + W2 . x2[n, q*x2_stride]) + shift),   W = [W1 | W2] packed along K (K-run 1 = Cin
@@ -214,6 +224,13 @@ size_t ft_conv_workspace_bytes(const ft_conv_desc* d);
  * the implicit-GEMM kernel) into hints[] and returns their count (0: the layer runs on a kernel without
  * tile variants); negative = error status. */
 int ft_conv_tile_candidates(const ft_conv_desc* d, int* hints, int max);
+/* The fields of a `tile_hint` (layout: ft_conv_desc.tile_hint).  `sk` is the slice count 1..8, not its code. */
+typedef struct ft_conv_tile { int bp, bc, ks, sk, wide, halo; } ft_conv_tile;
+/* FT_OK, or FT_ERR_INVALID_ARG for out == NULL or a negative hint. */
+int ft_conv_tile_decode(int hint, ft_conv_tile* out);
+/* The hint, or -FT_ERR_INVALID_ARG for a field that does not fit its bits (bp > 4095, bc > 511, ks > 15, sk outside 1..8,
+ * wide > 3, halo > 1, anything negative).  Whether the tile applies to a layer is ft_conv_tile_candidates' business. */
+int ft_conv_tile_encode(const ft_conv_tile* t);
 /* algorithmic FLOPs (2*MACs, unpadded) of one ft_conv2d_fwd call */
 double ft_conv_flops(const ft_conv_desc* d);
 

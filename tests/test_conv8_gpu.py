@@ -11,20 +11,17 @@ import torch
 import torch.nn.functional as F
 
 from flowtrack.pytorch_amd import synth
-from flowtrack.pytorch_amd.hip_ops import ActView, FusedConv, act_stride, new_act
+from flowtrack.pytorch_amd.hip_ops import WIDE8, ActView, FusedConv, act_stride, decode_tile, encode_tile, new_act
 from test_conv_gpu import _reference
 from util import make_program, nchw_to_view, run_program, view_to_nchw
 
 pytestmark = pytest.mark.gpu
 
-WIDE8 = 3
-
-
 def hints8(hip_lib, d):
     hints = (ctypes.c_int * 64)()
     n = hip_lib.ft_conv_tile_candidates(ctypes.byref(d), hints, 64)
     assert n >= 0
-    return [int(h) for h in hints[:n] if (int(h) >> 28) & 3 == WIDE8], [int(h) for h in hints[:n]]
+    return [int(h) for h in hints[:n] if decode_tile(h).wide == WIDE8], [int(h) for h in hints[:n]]
 
 
 CASES8 = [
@@ -73,11 +70,11 @@ def test_igemm8_matches_oracle(hip_lib, case):
     mine, _ = hints8(hip_lib, d)
     assert mine, f"{name}: the 8-phase tile is not offered"
     if wants_sk:
-        assert any((h >> 21) & 7 for h in mine), f"{name}: no split-K form of the 8-phase tile offered"
+        assert any(decode_tile(h).sk > 1 for h in mine), f"{name}: no split-K form of the 8-phase tile offered"
         # the odd K splits (codes 4..7 = 3, 5, 6, 7 slices: offered only where they fill one round of CUs better than a power of
         # two, e.g. deconv.0 at batch 64 = 48 tiles x 5) forced onto these small cases as well
-        base = next(h for h in mine if not (h >> 21) & 7)
-        mine = mine + [base | (code << 21) for code in (4, 5, 6, 7)]
+        assert any(decode_tile(h).sk == 1 for h in mine)
+        mine = mine + [encode_tile(bp=256, bc=256, ks=1, wide=WIDE8, sk=sk) for sk in (3, 5, 6, 7)]
     scale = max(1.0, want.abs().max().item())
     for h in mine:
         d.tile_hint = h
@@ -88,7 +85,7 @@ def test_igemm8_matches_oracle(hip_lib, case):
             outs.append(yv.t.clone())
         assert all(torch.equal(outs[0], o) for o in outs[1:]), f"{name} hint {h:#x}: runs differ"
         err = (view_to_nchw(yv) - want).abs().max().item()
-        assert err <= 2e-2 * scale, f"{name} hint {h:#x} (split-K code {(h >> 21) & 7}): max abs err {err:.3e} (scale {scale:.2f})"
+        assert err <= 2e-2 * scale, f"{name} hint {h:#x} (split-K x{decode_tile(h).sk}): max abs err {err:.3e} (scale {scale:.2f})"
     if "coff" in name:
         assert torch.all(yv.t[..., :24] == 3.0) and torch.all(yv.t[..., 24 + Cout:] == 3.0), "wrote outside its channel slice"
 

@@ -36,8 +36,7 @@ def _hints(hip_lib, d):
 
 
 def _hint_str(h):
-    return (f"hint {h:#x} (bp {h & 0xfff} bc {(h >> 12) & 0x1ff} splitK code {(h >> 21) & 7} ks {(h >> 24) & 0xf} wide {(h >> 28) & 3} "
-            f"halo {(h >> 30) & 1})")
+    return f"hint {h:#x} ({hip_ops.tile_str(h)})"
 
 
 def _use_direct(monkeypatch, mode):
@@ -151,14 +150,14 @@ def test_every_tile_variant_is_exact(hip_lib, c, dtype, monkeypatch):
     hints = _hints(hip_lib, d)
     assert len(hints) >= 2, f"{name}: only {len(hints)} tile variants offered"
     if "splitk" in name:
-        assert any((h >> 21) & 7 for h in hints), f"{name}: no split-K variant offered"
+        assert any(hip_ops.decode_tile(h).sk > 1 for h in hints), f"{name}: no split-K variant offered"
     if c.get("odd_splits") or name == "1x1_128_two_ktiles":
-        mine = [h for h in hints if (h >> 28) & 3 == 3]
+        mine = [h for h in hints if hip_ops.decode_tile(h).wide == hip_ops.WIDE8]
         assert mine or dtype != F16, f"{name}: the 8-phase tile is not offered"
         if c.get("odd_splits") and mine:      # the odd K splits (3, 5, 6, 7 slices) forced onto the 8-phase tile, as test_conv8_gpu.py does
-            assert any((h >> 21) & 7 for h in mine), f"{name}: no split-K form of the 8-phase tile offered"
-            base = next(h for h in mine if not (h >> 21) & 7)
-            hints = hints + [base | (code << 21) for code in (4, 5, 6, 7)]
+            assert any(hip_ops.decode_tile(h).sk > 1 for h in mine), f"{name}: no split-K form of the 8-phase tile offered"
+            assert any(hip_ops.decode_tile(h).sk == 1 for h in mine)
+            hints = hints + [hip_ops.encode_tile(bp=256, bc=256, ks=1, wide=hip_ops.WIDE8, sk=sk) for sk in (3, 5, 6, 7)]
     for h in [0] + hints:
         d.tile_hint = h
         yv.t.fill_(ec.Y_POISON)
@@ -258,7 +257,7 @@ def test_fused_tail_is_exact(hip_lib, case, nchw, monkeypatch):
     assert d.tail_cout == nt
     hints = _hints(hip_lib, d)
     if Cout == 256:
-        assert len(hints) == 2 and sum((h >> 28) & 3 == 3 for h in hints) == 1, "a 256-channel tail layer offers the 128-pixel default and the 8-phase tile"
+        assert len(hints) == 2 and sum(hip_ops.decode_tile(h).wide == hip_ops.WIDE8 for h in hints) == 1, "a 256-channel tail layer offers the 128-pixel default and the 8-phase tile"
     for h in [0] + hints:
         d.tile_hint = h
         (y if nchw else y.t).fill_(5.0 if nchw else ec.Y_POISON)
@@ -290,7 +289,7 @@ def test_fused_shortcut_conv_is_exact(hip_lib, case, dtype, monkeypatch):
     hints = _hints(hip_lib, d)
     assert len(hints) >= 2
     for h in [0] + hints:
-        assert h == 0 or ((h >> 24) & 0xf == 1 and not (h >> 30) & 1), "K-concat offers no split-K / halo variants"
+        assert h == 0 or (hip_ops.decode_tile(h).ks == 1 and not hip_ops.decode_tile(h).halo), "K-concat offers no split-K / halo variants"
         d.tile_hint = h
         yv.t.fill_(ec.Y_POISON)
         run_program(prog)

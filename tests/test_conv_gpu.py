@@ -6,7 +6,7 @@ import torch
 import torch.nn.functional as F
 
 from flowtrack.pytorch_amd import synth
-from flowtrack.pytorch_amd.hip_ops import ActView, FlowtrackHipError, FusedConv, act_stride
+from flowtrack.pytorch_amd.hip_ops import ActView, FlowtrackHipError, FusedConv, act_stride, decode_tile, encode_tile, tile_str
 from util import make_program, nchw_to_view, run_program, view_to_nchw
 
 pytestmark = pytest.mark.gpu
@@ -279,7 +279,7 @@ def test_every_tile_variant_matches_oracle(hip_lib, case, dtype):
     n = hip_lib.ft_conv_tile_candidates(ctypes.byref(d), hints, 64)
     assert n >= 2, f"{name}: only {n} tile variants offered"
     if "splitk" in name:
-        assert any((int(v) >> 21) & 7 for v in hints[:n]), f"{name}: no split-K variant offered"
+        assert any(decode_tile(v).sk > 1 for v in hints[:n]), f"{name}: no split-K variant offered"
     tol = 2e-4 if dtype == torch.float32 else 2e-2
     scale = max(1.0, want.abs().max().item())
     for h in [0] + [int(v) for v in hints[:n]]:
@@ -288,9 +288,61 @@ def test_every_tile_variant_matches_oracle(hip_lib, case, dtype):
         torch.cuda.synchronize()      # the fill runs on torch's stream, the program on its own
         run_program(prog)
         err = (view_to_nchw(yv) - want).abs().max().item()
-        assert err <= tol * scale, (f"{name} {dtype} tile bp {h & 0xfff} bc {(h >> 12) & 0x1ff} splitK {(1, 2, 4, 8, 3, 5, 6, 7)[(h >> 21) & 7]} ks {(h >> 24) & 0xf} "
-                                    f"wide {(h >> 28) & 3} halo {(h >> 30) & 1}: max abs err {err:.3e}")
+        assert err <= tol * scale, f"{name} {dtype} tile {tile_str(h)}: max abs err {err:.3e}"
     assert torch.all(yv.t[..., Cout:] == 3.0) or act_stride(Cout) == Cout
+
+
+def _bn_relu_layer(name, N, Cin, H, W, Cout, k, pad, dtype, dev):
+    """One recorded conv + BN + ReLU on synthetic data: (program, its descriptor, the output view)."""
+    w = synth.normal(6, name + ".w", (Cout, Cin, k, k), std=(2.0 / (Cin * k * k)) ** 0.5)
+    bn = {"weight": synth.uniform(6, name + ".g", (Cout,), 0.5, 1.5), "bias": synth.normal(6, name + ".be", (Cout,), 0.1),
+          "running_mean": synth.normal(6, name + ".m", (Cout,), 0.1), "running_var": synth.uniform(6, name + ".v", (Cout,), 0.5, 1.5),
+          "eps": 1e-5}
+    layer = FusedConv(w, dtype=dtype, device=dev, stride=1, pad=pad, bn=bn, act="relu", label=name)
+    xv = nchw_to_view(synth.normal(6, name + ".x", (N, Cin, H, W)), dtype, dev, cstride=act_stride(Cin))
+    yv = ActView(torch.zeros((N, H, W, act_stride(Cout)), dtype=dtype, device=dev), Cout, 0)
+    prog = make_program()
+    layer.record(prog, xv, yv)
+    prog.resolve_choices()
+    assert prog.calls[0][0] == "ft_conv2d_fwd_ws", prog.calls[0][0]
+    return prog, prog.conv_records[0][3], yv
+
+
+def test_inapplicable_hints_fall_back(hip_lib, monkeypatch):
+    """A hint for a tile that does not exist, or that the call cannot take, runs what the call runs without it - bit for bit - and
+    never another instantiation: a 256 x 256 tile without wide-K, in-workgroup split-K x4 on 128 x 64, wide-K together with
+    in-workgroup split-K, wide-K in fp32; and a cross-workgroup split-K tile without a workspace runs the same tile unsplit."""
+    import ctypes
+    from flowtrack.pytorch_amd import hip_ops
+    monkeypatch.setattr(hip_ops, "CONV_DIRECT", False)     # the second layer stays on ft_conv2d_fwd
+    dev = torch.device("cuda:0")
+    for dtype, tiles in ((torch.float16, [dict(bp=256, bc=256, ks=1, wide=0), dict(bp=128, bc=64, ks=4), dict(bp=64, bc=64, ks=2, wide=1)]),
+                         (torch.float32, [dict(bp=64, bc=64, wide=1)])):
+        prog, d, yv = _bn_relu_layer("fallback_3x3", 1, 64, 8, 6, 256, 3, 1, dtype, dev)
+        d.tile_hint = 0
+        run_program(prog)                                  # (raises on any status but FT_OK)
+        ref = yv.t.clone()
+        assert ref.abs().max().item() > 0
+        for t in tiles:
+            d.tile_hint = encode_tile(**t)
+            yv.t.fill_(3.0)
+            run_program(prog)
+            assert torch.equal(yv.t, ref), f"{dtype} hint {d.tile_hint:#x} ({tile_str(d.tile_hint)}) changed the result"
+    prog, d, yv = _bn_relu_layer("fallback_1x1", 1, 1024, 6, 8, 1024, 1, 0, torch.float16, dev)
+    hints = (ctypes.c_int * 64)()
+    n = hip_lib.ft_conv_tile_candidates(ctypes.byref(d), hints, 64)
+    split = next((decode_tile(h) for h in hints[:max(n, 0)] if decode_tile(h).sk == 2), None)
+    assert split is not None, "no split-K x2 tile offered"
+    args, outs = prog.calls[0][1], []
+    for sk in (2, 1):
+        d.tile_hint = encode_tile(split.bp, split.bc, split.ks, sk, split.wide, split.halo)
+        yv.t.fill_(3.0)
+        torch.cuda.synchronize()
+        assert hip_lib.ft_conv2d_fwd(*args[:7], prog.stream_handle) == 0      # no workspace
+        prog.stream.synchronize()
+        outs.append(yv.t.clone())
+    assert torch.equal(outs[0], outs[1]), f"split-K x2 of {tile_str(d.tile_hint)} without a workspace is not the unsplit tile"
+    assert outs[0][..., :1024].abs().max().item() > 0
 
 
 # ---- conv3 + projection shortcut as one K-concatenated GEMM (ft_conv_desc.x2_*, FusedShortcutConv) -----------
@@ -338,7 +390,7 @@ def test_fused_shortcut_conv_matches_oracle(hip_lib, case, dtype):
     tol = 2e-4 if dtype == torch.float32 else 3e-2
     scale = max(1.0, want.abs().max().item())
     for h in [0] + [int(v) for v in hints[:n]]:
-        assert h == 0 or ((h >> 24) & 0xf == 1 and not (h >> 30) & 1), "K-concat offers no split-K / halo variants"
+        assert h == 0 or (decode_tile(h).ks == 1 and not decode_tile(h).halo), "K-concat offers no split-K / halo variants"
         d.tile_hint = h
         yv.t.fill_(3.0)
         run_program(prog)
@@ -423,9 +475,9 @@ def test_patch_kernels_are_deterministic_when_workgroups_are_recycled(hip_lib, c
     d = prog.conv_records[0][3]
     hints = (ctypes.c_int * 64)()
     n = hip_lib.ft_conv_tile_candidates(ctypes.byref(d), hints, 64)
-    halo = [int(h) for h in hints[:n] if (int(h) >> 30) & 1]
+    halo = [int(h) for h in hints[:n] if decode_tile(h).halo]
     assert halo, "no LDS-patch variant offered"
-    d.tile_hint = next(int(h) for h in hints[:n] if not (int(h) >> 30) & 1)
+    d.tile_hint = next(int(h) for h in hints[:n] if not decode_tile(h).halo)
     run_program(prog)
     ref = yv.t.float().clone()
     scale = max(1.0, ref.abs().max().item())

@@ -25,7 +25,8 @@ import posenet_ref
 from conv_bound import derived_bound
 from flowtrack.pytorch_amd import _lib, synth
 from flowtrack.pytorch_amd._lib import ConvDesc, ConvGeometry
-from flowtrack.pytorch_amd.hip_ops import ActView, FusedConv, FusedLateralDeconv, act_stride, current_stream_handle, round_up
+from flowtrack.pytorch_amd.hip_ops import (WIDE8, ActView, FusedConv, FusedLateralDeconv, act_stride, current_stream_handle, decode_tile, round_up,
+                                           tile_str)
 from util import make_program, run_program, view_to_nchw
 
 pytestmark = pytest.mark.gpu
@@ -81,7 +82,7 @@ def _hints(lib, d):
 
 
 def _hint_str(h):
-    return f"hint {h:#x} (bp {h & 0xfff} bc {(h >> 12) & 0x1ff} splitK code {(h >> 21) & 7} ks {(h >> 24) & 0xf} wide {(h >> 28) & 3} halo {(h >> 30) & 1})"
+    return f"hint {h:#x} ({tile_str(h)})"
 
 
 def _table(v, cout_pad):
@@ -130,7 +131,8 @@ class Step:
     def hints(self):
         hs = _hints(self.lib, self.d)
         for h in hs:      # what the header states: with a second input no split-K, halo or 8-phase form is offered
-            assert (h >> 21) & 7 == 0 and (h >> 24) & 0xf == 1 and not (h >> 30) & 1 and (h >> 28) & 3 != 3, _hint_str(h)
+            t = decode_tile(h)
+            assert t.sk == 1 and t.ks == 1 and not t.halo and t.wide != WIDE8, _hint_str(h)
         assert self.lib.ft_conv_workspace_bytes(ctypes.byref(self.d)) == 0
         return hs
 

@@ -184,10 +184,16 @@ def _hints(hip_lib, d):
     buf = (ctypes.c_int * 64)()
     n = hip_lib.ft_conv_tile_candidates(ctypes.byref(d), buf, 64)
     assert n >= 0
-    return [int(v) for v in buf[:n]]
+    hints = [int(v) for v in buf[:n]]
+    for h in hints:      # the library's codec agrees with the ABI as _decode states it, and round-trips
+        t = _lib.ConvTile()
+        assert hip_lib.ft_conv_tile_decode(h, ctypes.byref(t)) == 0
+        assert {f: getattr(t, f) for f, _ in t._fields_} == _decode(h), hex(h)
+        assert hip_lib.ft_conv_tile_encode(ctypes.byref(t)) == h, hex(h)
+    return hints
 
 
-def _decode(h):
+def _decode(h):      # hand-written on purpose: the independent statement of the tile_hint layout (include/flowtrack_hip.h)
     return dict(bp=h & 0xfff, bc=(h >> 12) & 0x1ff, sk=(1, 2, 4, 8, 3, 5, 6, 7)[(h >> 21) & 7], ks=(h >> 24) & 0xf, wide=(h >> 28) & 3, halo=(h >> 30) & 1)
 
 
@@ -244,6 +250,11 @@ def test_tile_candidates_and_fusion_descriptors(hip_lib):
     assert _geom(hip_lib, tl)[0] == 1
     tl.tail_cout = 17; tl.dtype = _lib.FT_F32
     assert _geom(hip_lib, tl)[0] == 2                    # the fused tail is an fp16-mode feature
+    # the codec refuses a field that does not fit its bits; sk is the slice count 1..8
+    enc = lambda **kw: hip_lib.ft_conv_tile_encode(ctypes.byref(_lib.ConvTile(**dict(dict(bp=128, bc=128, ks=1, sk=1, wide=0, halo=0), **kw))))
+    assert _decode(enc()) == dict(bp=128, bc=128, ks=1, sk=1, wide=0, halo=0) and _decode(enc(sk=5, wide=3))["sk"] == 5
+    assert enc(sk=9) < 0 and enc(sk=0) < 0 and enc(bp=4096) < 0 and enc(bc=512) < 0 and enc(wide=4) < 0 and enc(halo=2) < 0
+    assert hip_lib.ft_conv_tile_encode(None) < 0 and hip_lib.ft_conv_tile_decode(0, None) == 1
 
 
 def test_bottleneck_desc_matches_header_and_argument_checks(hip_lib):

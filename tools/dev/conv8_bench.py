@@ -11,7 +11,7 @@ import torch
 
 from flowtrack.pytorch_amd import _lib
 from flowtrack.pytorch_amd._lib import check
-from flowtrack.pytorch_amd.hip_ops import FusedConv, Program, new_act
+from flowtrack.pytorch_amd.hip_ops import WIDE8, FusedConv, Program, decode_tile, new_act
 
 # name, N, Cin, H, W, Cout, k, stride, pad, transposed, tail
 POSE = [
@@ -45,12 +45,8 @@ FLOW = [
 def fmt(h):
     if h == 0:
         return "heuristic"
-    s = f"bp{h & 0xfff} bc{(h >> 12) & 0x1ff} ks{(h >> 24) & 0xf} w{(h >> 28) & 3}"
-    if (h >> 30) & 1:
-        s += " halo"
-    if (h >> 21) & 7:
-        s += f" sk{(1, 2, 4, 8, 3, 5, 6, 7)[(h >> 21) & 7]}"
-    return s
+    t = decode_tile(h)
+    return f"bp{t.bp} bc{t.bc} ks{t.ks} w{t.wide}" + (" halo" if t.halo else "") + (f" sk{t.sk}" if t.sk > 1 else "")
 
 
 def main():
@@ -104,8 +100,8 @@ def main():
             rows.append((best, h))
         fl = prog.flops
         base = rows[0][0]
-        best_old = min(r for r in rows if (r[1] >> 28) & 3 != 3)
-        best_new = min([r for r in rows if (r[1] >> 28) & 3 == 3], default=None)
+        best_old = min(r for r in rows if decode_tile(r[1]).wide != WIDE8)
+        best_new = min([r for r in rows if decode_tile(r[1]).wide == WIDE8], default=None)
         print(f"{name:30s} {fl / 1e9:7.2f} GFLOP  heuristic {base * 1e3:7.1f} us {fl / base / 1e9:7.1f} TF/s | best other {best_old[0] * 1e3:7.1f} us "
               f"{fl / best_old[0] / 1e9:7.1f} TF/s ({fmt(best_old[1])})" +
               (f" | 8-phase {best_new[0] * 1e3:7.1f} us {fl / best_new[0] / 1e9:7.1f} TF/s ({fmt(best_new[1])})" if best_new else " | 8-phase n/a"), flush=True)

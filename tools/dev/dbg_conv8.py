@@ -4,7 +4,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch
 from flowtrack.pytorch_amd import _lib, synth
-from flowtrack.pytorch_amd.hip_ops import FusedConv, Program, new_act
+from flowtrack.pytorch_amd.hip_ops import WIDE8, FusedConv, Program, decode_tile, new_act
 
 def main():
     N, Cin, H, W, Cout, k, s, p, tr = [int(v) for v in (sys.argv[1:10] if len(sys.argv) > 9 else "64 256 16 12 256 4 2 1 1".split())]
@@ -18,14 +18,14 @@ def main():
     prog = Program(torch.cuda.Stream()); layer.record(prog, x, y); prog.resolve_choices(); prog._ensure_workspace()
     d = prog.conv_records[-1][3]
     hints = (ctypes.c_int * 32)(); n = lib.ft_conv_tile_candidates(ctypes.byref(d), hints, 32)
-    mine = [int(h) for h in hints[:n] if (int(h) >> 28) & 3 == 3]
+    mine = [int(h) for h in hints[:n] if decode_tile(h).wide == WIDE8]
     d.tile_hint = 0; torch.cuda.synchronize(); prog.run_eager(); prog.stream.synchronize(); ref = y.t.float().clone()
     for h in mine:
         d.tile_hint = h
         outs = []
         for _ in range(6):
             y.t.fill_(7.0); torch.cuda.synchronize(); prog.run_eager(); prog.stream.synchronize(); outs.append(y.t.float().clone())
-        print(f"hint {h:#x} sk {(1, 2, 4, 8, 3, 5, 6, 7)[(h >> 21) & 7]}: max |out - default tile| = {(outs[0] - ref).abs().max().item():.4f}")
+        print(f"hint {h:#x} sk {decode_tile(h).sk}: max |out - default tile| = {(outs[0] - ref).abs().max().item():.4f}")
         for r, o in enumerate(outs[1:], 1):
             diff = (o != outs[0])
             if diff.any():

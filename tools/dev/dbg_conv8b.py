@@ -4,7 +4,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 import torch
 from flowtrack.pytorch_amd import _lib, synth
-from flowtrack.pytorch_amd.hip_ops import FusedConv, Program, new_act
+from flowtrack.pytorch_amd.hip_ops import WIDE8, FusedConv, Program, encode_tile, new_act
 N, Cin, H, W, Cout = 64, 256, 16, 12, 256
 dev, dtype = torch.device("cuda:0"), torch.float16
 lib = _lib.load()
@@ -14,7 +14,7 @@ x = new_act(N, H, W, Cin, dtype, dev); x.t[..., :Cin] = synth.normal(35, "x", (N
 y = new_act(N, 2 * H, 2 * W, Cout, dtype, dev)
 prog = Program(torch.cuda.Stream()); layer.record(prog, x, y); prog.resolve_choices(); prog._ensure_workspace()
 d = prog.conv_records[-1][3]
-d.tile_hint = 256 | (256 << 12) | (1 << 24) | (3 << 28)
+d.tile_hint = encode_tile(bp=256, bc=256, ks=1, wide=WIDE8)
 # expected constant per channel: wave * 16 + i * 4 + rg with wave = wc * 4 + wp: depends on the pixel's row in its tile
 for r in range(4):
     y.t.fill_(7.0); torch.cuda.synchronize(); prog.run_eager(); prog.stream.synchronize()

@@ -6,10 +6,11 @@
 A refactor that must not change device code is checked here instead of on a GPU: every kernel (symbol with an .amdhsa_kernel block)
 of the new tree has to exist in the parent under the same mangled name - or under the parent instantiation given for it on the
 command line, where template parameters were dropped - with identical instruction text (comments stripped, the kernel's own name
-and the function index of local labels .LBB<n>_ replaced) and equal VGPR / SGPR / AGPR-offset / LDS / scratch figures.  A kernel
-that differs is reported as "class B" if it has the same number of instruction lines with the same mnemonic (first token) on every line
-and equal descriptor figures, i.e. only operands changed.  Parent kernels that the new tree no longer has are listed.  Exit status 1 if
-any surviving kernel differs (class B included) or has no parent."""
+and the function index of local labels .LBB<n>_ replaced) and equal VGPR / SGPR / AGPR-offset / LDS / scratch figures.  The kernels
+of ALL units of a tree are pooled, so a kernel may move to another translation unit; one that the new tree emits from more than one
+unit is a defect.  A kernel that differs is reported as "class B" if it has the same number of instruction lines with the same
+mnemonic (first token) on every line and equal descriptor figures, i.e. only operands changed.  Parent kernels that the new tree no
+longer has are listed.  Exit status 1 if any surviving kernel differs (class B included), is duplicated or has no parent."""
 import os, re, subprocess, sys
 
 DESC = (".amdhsa_next_free_vgpr", ".amdhsa_next_free_sgpr", ".amdhsa_accum_offset", ".amdhsa_group_segment_fixed_size",
@@ -49,38 +50,53 @@ def kernels(path):
     return out
 
 
+def pool(sdir):
+    """{mangled name: [(unit, body, descriptor figures), ...]} over every .s file of one tree."""
+    out = {}
+    for unit in sorted(f for f in os.listdir(sdir) if f.endswith(".s")):
+        for name, (body, desc) in kernels(os.path.join(sdir, unit)).items():
+            out.setdefault(name, []).append((unit, body, desc))
+    return out
+
+
 def compare(pdir, ndir, renames):
+    par, new = pool(pdir), pool(ndir)
     bad = 0
-    tot = [0, 0, 0]
-    for unit in sorted(f for f in os.listdir(ndir) if f.endswith(".s")):
-        par, new = kernels(os.path.join(pdir, unit)), kernels(os.path.join(ndir, unit))
-        used, same = set(), 0
-        for name, (body, desc) in new.items():
-            pname = name if name in par else next((p for sub, p in renames if sub in name), None)
-            if pname not in par:
-                print(f"{unit}: NO PARENT for {name}")
-                bad += 1
-                continue
-            used.add(pname)
-            if pname != name:
-                print(f"{unit}: {name}\n    compared with parent {pname}")
-            if (body, desc) == par[pname]:
-                same += 1
-            else:
-                what = "descriptor " + " ".join(f"{a}->{b}" for a, b in zip(par[pname][1], desc)) if desc != par[pname][1] else "instructions"
-                # class B: the same instructions in the same places, only operands differ (register numbers, operand order)
-                mnem = [[line.split()[0] for line in b.split("\n")] for b in (par[pname][0], body)]
-                cls = "class B" if desc == par[pname][1] and mnem[0] == mnem[1] else "not class B"
-                print(f"{unit}: DIFFERS ({what}; {cls}): {name}")
-                bad += 1
-        gone = [p for p in par if p not in used]
-        for p in gone:
-            print(f"{unit}: removed {p}")
-        lines = [sum(1 for _ in open(os.path.join(d, unit))) for d in (pdir, ndir)]
-        print(f"{unit}: {len(new)} kernels compared, {same} identical, {len(gone)} removed; assembly lines {lines[0]} -> {lines[1]}")
-        for i, v in enumerate((len(new), same, len(gone))):
-            tot[i] += v
-    print(f"total: {tot[0]} compared, {tot[1]} identical, {tot[2]} removed, {bad} defects")
+    used, same, moved = set(), 0, 0
+    per_unit = {}                                # new unit -> [kernels, identical]
+    for name, found in sorted(new.items(), key=lambda kv: (kv[1][0][0], kv[0])):
+        unit, body, desc = found[0]
+        cnt = per_unit.setdefault(unit, [0, 0])
+        cnt[0] += 1
+        if len(found) > 1:                       # one kernel, one unit: a second copy is dead weight in the library
+            print(f"DUPLICATED in {', '.join(u for u, _, _ in found)}: {name}")
+            bad += 1
+        pname = name if name in par else next((p for sub, p in renames if sub in name), None)
+        if pname not in par:
+            print(f"{unit}: NO PARENT for {name}")
+            bad += 1
+            continue
+        used.add(pname)
+        punit, pbody, pdesc = par[pname][0]
+        if pname != name:
+            print(f"{unit}: {name}\n    compared with parent {pname}")
+        if (body, desc) == (pbody, pdesc):
+            same += 1
+            cnt[1] += 1
+            moved += punit != unit
+        else:
+            what = "descriptor " + " ".join(f"{a}->{b}" for a, b in zip(pdesc, desc)) if desc != pdesc else "instructions"
+            # class B: the same instructions in the same places, only operands differ (register numbers, operand order)
+            mnem = [[line.split()[0] for line in b.split("\n")] for b in (pbody, body)]
+            cls = "class B" if desc == pdesc and mnem[0] == mnem[1] else "not class B"
+            print(f"{unit}: DIFFERS ({what}; {cls}): {name}" + (f" (parent: {punit})" if punit != unit else ""))
+            bad += 1
+    gone = [p for p in par if p not in used]
+    for p in gone:
+        print(f"{par[p][0][0]}: removed {p}")
+    for unit, (n, s) in sorted(per_unit.items()):
+        print(f"{unit}: {n} kernels compared, {s} identical")
+    print(f"total: {len(new)} compared, {same} identical ({moved} of them in another unit), {len(gone)} removed, {bad} defects")
     return 1 if bad else 0
 
 
