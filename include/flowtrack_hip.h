@@ -564,6 +564,11 @@ int ft_hourglass_up_fwd(const void* skip, const void* low, int dtype, int N, int
                         int skip_cstride, int skip_coff, int low_cstride, int low_coff, void* sum, int sum_cstride, int sum_coff,
                         void* a_sum, int asum_cstride, int asum_coff, const float* scale, const float* shift, ft_stream_t stream);
 
+/* ---- F4-F6 parity: the entry points below (forward, the NHWC forms, the fused warp stage and the backward calls)
+ * are held to numbers the REFERENCE'S OWN kernels computed: tests/golden/flowops_golden.npz, written by its .cu
+ * files compiled for the CPU (oracle/cuda_on_cpu/, tests/test_flowops_pinned_gpu.py).  Not pinned that way: nvcc's
+ * FMA contraction, the order of Resample2d's backward atomics, coordinates with |x + dx| >= 2^31 (CUDA's
+ * saturating float-to-int conversion, restated). */
 /* ---- F4: Correlation forward ---------------------------------------------
  * Replaces Correlation_forward_cuda (correlation_package/src/correlation_cuda.c:11-93,
  * kernels correlation_cuda_kernel.cu:10-106).  Same parameters and output

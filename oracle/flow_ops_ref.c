@@ -12,10 +12,13 @@
  *   channelnorm_fwd   <- ChannelNorm_kernel.cu:19-51
  *   upsample4x_fwd    <- nn.Upsample(scale_factor=4, mode='bilinear') as used at FlowNetS.py:58
  *                        (align_corners=False semantics; checked against torch in tests)
- * Parity status: the reference ships no golden vectors for these ops and its kernels cannot run
- * here (CUDA only) => PARITY UNPINNED by the reference; pinned instead by (i) this line-by-line
- * restatement, (ii) an independent numpy formulation in oracle/flow_ref.py, (iii) algebraic
- * properties in tests/ (shift/identity cases with closed-form answers).
+ * Parity status: PINNED for the three operators' forwards.  The reference's own .cu kernels, compiled for the CPU by
+ * oracle/cuda_on_cpu/build_ref.py (one thread at a time, warp lockstep order, no FMA contraction), wrote
+ * tests/golden/flowops_golden.npz; correlation_fwd, resample2d_fwd and channelnorm_fwd below reproduce it BIT FOR BIT
+ * (tests/test_flowops_pinned_cpu.py, which also compares against the live library on a wider sweep where it is built).
+ * Not pinned: nvcc's default FMA contraction (bounded by a test), coordinates with |x + dx| >= 2^31 (the clamp before the
+ * int conversion in resample2d_fwd restates CUDA's saturating conversion, which a host compile cannot run).  Further checks:
+ * an independent numpy formulation in oracle/ops_ref.py and closed-form cases in tests/ (shifts, identities).
  */
 #include <math.h>
 #include <stdlib.h>

@@ -14,7 +14,7 @@ FlowNet2S and FlowNet2SD are pinned against the imported reference by tests/gold
 FlowNet2C/CS/CSS/FlowNet2: the GRAPHS are pinned the same way (round 4) — the imported reference
 classes run with the three CUDA-only operators injected at their `_ext` FFI boundary
 (make_golden.inject_restated_cuda_ops), and these functions reproduce them with max abs 0.0; the
-three operators themselves stay "restated, parity unpinned" (CUDA-only in the reference).
+three operators themselves are pinned separately, by tests/golden/flowops_golden.npz (oracle/cuda_on_cpu/).
 """
 from __future__ import annotations
 

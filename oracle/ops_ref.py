@@ -23,6 +23,10 @@ def build(force: bool = False) -> str:
     src = os.path.join(HERE, "flow_ops_ref.c")
     if force or not os.path.exists(LIB) or os.path.getmtime(LIB) < os.path.getmtime(src):
         subprocess.check_call(["make", "-C", HERE, "-B" if force else "-s"], stdout=subprocess.DEVNULL)
+    # the reference's own kernels, compiled for the CPU into oracle/_ref/ (oracle/ref_ops.py); nothing happens where the
+    # reference checkout is absent
+    from oracle.cuda_on_cpu import build_ref
+    build_ref.build(force)
     return LIB
 
 

@@ -96,7 +96,10 @@ def _cdiv(a: int, b: int) -> int:
 
 
 def correlation_bwd_loops(in1, in2, g, pad, k, md, s1, s2):
-    """Correlation_backward_input1 / _input2 (correlation_cuda_kernel.cu:108-290) over padded NHWC copies; numpy float64."""
+    """Correlation_backward_input1 / _input2 (correlation_cuda_kernel.cu:108-290) over padded NHWC copies; numpy float64.
+    For stride1 > 1 only the blocks whose pixel (yi * stride1, xi * stride1) lies inside the map are restated: the reference's
+    other blocks write through the flat index into the next row / channel or past the tensor (flowops_pinned.corr_stray_targets,
+    shown on the reference's own numbers by test_flowops_pinned_cpu.py)."""
     in1, in2, g = (np.asarray(t, dtype=np.float64) for t in (in1, in2, g))
     B, C, H, W = in1.shape
     _, OC, oh, ow = g.shape

@@ -64,8 +64,8 @@ def inject_restated_cuda_ops():
     `ChannelNorm_cuda_forward` channelnorm.py:14).  Everything above that line — the autograd Functions,
     the Modules, FlowNetC.forward (FlowNetC.py:71-128) and the stacked models (models.py:108-178,
     180-246, 346-498) — then runs as the REFERENCE's own Python, so the committed flows pin the graphs
-    (concat orders, div_flow handling, which frame is warped, bilinear vs nearest x4) even though the
-    three operators themselves stay 'reference CUDA-only, restated'."""
+    (concat orders, div_flow handling, which frame is warped, bilinear vs nearest x4); the three
+    operators themselves are pinned separately (make_flowops_golden.py: the reference's kernels on the CPU)."""
     from oracle import ops_ref
 
     def corr_fwd(in1, in2, rbot1, rbot2, output, pad, k, md, s1, s2, mult):
