@@ -186,10 +186,17 @@ _PROTOTYPES = {
     "ft_rcnn_mean_pool_fwd": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ft_rcnn_detections_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_float), POINTER(c_float), c_float, c_float,
                                        c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ft_maxpool2x2s2_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "ft_fc_supported": (c_int, [c_int] * 6),
+    "ft_fc_workspace_bytes": (ctypes.c_longlong, [c_int, c_int, c_int]),
+    "ft_fc_pack": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "ft_fc_fwd": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                          ctypes.c_size_t, c_void_p]),
 }
 
 # declared only under FT_EXPERIMENTAL in the header: measured alternatives the default plans do not record (tests / tools/dev reach them)
-EXPERIMENTAL_SYMBOLS = ("ft_bottleneck_rstat_supported", "ft_bottleneck_rstat_weight_bytes", "ft_bottleneck_rstat_fwd", "ft_bottleneck_cluster_supported", "ft_bottleneck_cluster_workspace_bytes", "ft_bottleneck_cluster_status_offset", "ft_bottleneck_cluster_fwd")
+EXPERIMENTAL_SYMBOLS = ("ft_bottleneck_rstat_supported", "ft_bottleneck_rstat_weight_bytes", "ft_bottleneck_rstat_fwd", "ft_bottleneck_cluster_supported", "ft_bottleneck_cluster_workspace_bytes", "ft_bottleneck_cluster_status_offset", "ft_bottleneck_cluster_fwd",
+                        "ft_fc_supported", "ft_fc_workspace_bytes", "ft_fc_pack", "ft_fc_fwd")
 EXPORTED_SYMBOLS = tuple(n for n in _PROTOTYPES if n not in EXPERIMENTAL_SYMBOLS)
 
 _lib = None

@@ -1581,6 +1581,53 @@ def record_maxpool(prog: Program, x: ActView, y: ActView) -> None:
              keep=(x.t, y.t))
 
 
+def record_maxpool2x2(prog: Program, x: ActView, y: ActView) -> None:
+    """nn.MaxPool2d(2, 2) (floor mode) between two dense NHWC buffers: ft_maxpool2x2s2_fwd."""
+    if x.coff or y.coff or x.cstride != x.C or y.cstride != y.C or x.rowpacked or y.rowpacked:
+        raise FlowtrackHipError("maxpool works on dense NHWC buffers")
+    if (y.N, y.H, y.W, y.C) != (x.N, x.H // 2, x.W // 2, x.C) or x.t.dtype != y.t.dtype:
+        raise FlowtrackHipError(f"maxpool2x2: output view mismatch {tuple(y.t.shape)} for input {tuple(x.t.shape)}")
+    prog.add("ft_maxpool2x2s2_fwd", x.t.data_ptr(), y.t.data_ptr(), x.N, x.H, x.W, x.C, _lib.dtype_code(x.t.dtype),
+             keep=(x.t, y.t))
+
+
+class FusedFC:
+    """One nn.Linear (+ ReLU) on a few hundred rows as the weight-streaming split-K GEMM ft_fc_fwd (fp16): the weight [N, K] is
+    packed once (ft_fc_pack), the bias stays fp32.  record() reads an ActView [rows, 1, 1, K] and writes one [rows, 1, 1, N]; the
+    split-K slabs live in the plan's shared workspace."""
+
+    def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor], *, device: torch.device, act: Optional[str] = None,
+                 label: str = ""):
+        require_gpu(device)
+        self.lib = _lib.load()
+        self.n, self.k = (int(v) for v in weight.shape)
+        self.act, self.label, self.device = ACT_CODES[act], label, device
+        if self.lib.ft_fc_supported(_lib.FT_F16, 1, self.k, self.n, self.k, self.n) != 0:
+            raise FlowtrackHipError(f"{label}: ft_fc_fwd does not take a [{self.n}, {self.k}] weight")
+        w16 = weight.detach().to(device=device, dtype=torch.float16).contiguous()
+        self.wpack = torch.empty_like(w16)
+        with torch.cuda.device(device):
+            check(self.lib.ft_fc_pack(w16.data_ptr(), self.n, self.k, self.wpack.data_ptr(), current_stream_handle(device)), "ft_fc_pack")
+            torch.cuda.current_stream(device).synchronize()         # w16 is dropped on return
+        self.bias = None if bias is None else bias.detach().to(device=device, dtype=torch.float32).contiguous()
+
+    @staticmethod
+    def supported(rows: int, k: int, n: int, dtype, x: ActView, y: ActView) -> bool:
+        return dtype == torch.float16 and not (x.coff or y.coff) and \
+            _lib.load().ft_fc_supported(_lib.FT_F16, rows, k, n, x.cstride, y.cstride) == 0
+
+    def record(self, prog: Program, x: ActView, y: ActView) -> None:
+        rows = x.N
+        if (x.H, x.W, x.C) != (1, 1, self.k) or (y.N, y.H, y.W, y.C) != (rows, 1, 1, self.n) or x.t.dtype != torch.float16 \
+                or y.t.dtype != torch.float16 or not self.supported(rows, self.k, self.n, torch.float16, x, y):
+            raise FlowtrackHipError(f"{self.label}: ft_fc_fwd needs fp16 [rows,1,1,{self.k}] -> [rows,1,1,{self.n}] views")
+        prog.need_workspace(self.lib.ft_fc_workspace_bytes(rows, self.k, self.n))
+        prog.flops += 2.0 * rows * self.k * self.n
+        prog.add("ft_fc_fwd", _lib.FT_F16, x.t.data_ptr(), x.cstride, self.wpack.data_ptr(), self.bias.data_ptr() if self.bias is not None else None,
+                 y.t.data_ptr(), y.cstride, rows, self.k, self.n, self.act, prog._ws_ptr, prog._ws_size,
+                 keep=(x.t, y.t, self.wpack, self.bias))
+
+
 def record_upsample4x(prog: Program, x: torch.Tensor, y: torch.Tensor, mul: float) -> None:
     N, C, h, w = x.shape
     prog.add("ft_upsample_bilinear4x", x.data_ptr(), y.data_ptr(), N, C, h, w, ctypes.c_float(mul), keep=(x, y))

@@ -204,6 +204,43 @@ def fill_detector_state_dict(sd: Dict[str, torch.Tensor], seed: int) -> Dict[str
     return out
 
 
+#: gains (std = sqrt(gain / fan_in)) of fill_vgg_detector_state_dict's trunk: the first conv reads mean-subtracted pixels of
+#: magnitude ~100 and scales them down by 20; the twelve convs behind it keep He's 2.0 (no BatchNorm: nothing else holds the
+#: magnitude), which leaves |net_conv| near 20 and the RPN's deltas spread enough for its NMS to keep tens of boxes; the two
+#: classifier layers shrink it again so that the class softmax does not saturate (tests/golden/make_detect_vgg_golden.py checks
+#: the conditions on the reference's run)
+VGG_FIRST_CONV_GAIN = 2.0 / 400.0
+VGG_CONV_GAIN = 2.0
+VGG_FC_GAIN = 0.4
+
+
+def fill_vgg_detector_state_dict(sd: Dict[str, torch.Tensor], seed: int) -> Dict[str, torch.Tensor]:
+    """Weights for a detection.nets.vgg16 state_dict.  `vgg.features.*` convs N(0, gain / fan_in) with the gains above and N(0, 0.05)
+    biases (there is no BatchNorm in this trunk); the two `vgg.classifier.*` weights from ONE uniform stream each, U(-a, a) with
+    a = sqrt(3 gain / fan_in), the variance of the wanted normal (synth.normal draws two streams and takes 12 s and three times
+    the memory on the 4096 x 25088 matrix); the five head layers as fill_detector_state_dict fills them."""
+    out = {}
+    for k, v in sd.items():
+        shape = tuple(v.shape)
+        head = k.split(".")[0]
+        if head in DET_HEAD_GAINS:
+            if k.endswith(".weight"):
+                out[k] = normal(seed, k, shape, std=float(np.sqrt(DET_HEAD_GAINS[head] / int(np.prod(shape[1:])))))
+            else:
+                out[k] = normal(seed, k, shape, std=0.05)
+        elif k.startswith("vgg.features.") and v.dim() == 4:
+            gain = VGG_FIRST_CONV_GAIN if k == "vgg.features.0.weight" else VGG_CONV_GAIN
+            out[k] = normal(seed, k, shape, std=float(np.sqrt(gain / _fan_in(k, shape, False))))
+        elif k.startswith("vgg.classifier.") and v.dim() == 2:
+            a = float(np.sqrt(3.0 * VGG_FC_GAIN / shape[1]))
+            out[k] = uniform(seed, k, shape, -a, a)
+        elif k.endswith(".bias"):
+            out[k] = normal(seed, k, shape, std=0.05)
+        else:
+            raise KeyError(k)
+    return out
+
+
 def detector_frame(seed: int, H: int, W: int) -> np.ndarray:
     """uint8 [H,W,3] BGR: a smooth random texture (8 x 8 blocks, 70 %) under fine noise (30 %), as frame_pairs builds its frames."""
     lo = uniform01(seed, "det_frame_lo", (H // 8 + 2, W // 8 + 2, 3))

@@ -837,9 +837,18 @@ int ft_rcnn_detections_fwd(const float* cls_score, const float* bbox_pred, const
                            const float* means, float im_scale, float im_h, float im_w, float* cls_prob, float* deltas,
                            float* pred_boxes, ft_stream_t stream);
 
+/* ---- the VGG16 detector trunk (reference lib/detection/nets/vgg16.py; csrc/vgg_ops.hip) -------------------------
+ * A refused call launches nothing.  (The unit's FC entry points, ft_fc_*, are declared under FT_EXPERIMENTAL below.) */
+
+/* ft_maxpool2x2s2_fwd — nn.MaxPool2d(2, 2) (floor mode) on a dense NHWC map [N,Hi,Wi,C] -> [N,Hi/2,Wi/2,C], FT_F16 or FT_F32,
+ * C % 8 == 0, both buffers 16-byte aligned; the last row / column of an odd map is never read.  The max is over the four values
+ * themselves (an all-negative window gives its negative max; a NaN stays): the output is one of the inputs, bit for bit.
+ * Hi < 2, Wi < 2 and bad arguments: FT_ERR_INVALID_ARG; N*Hi*Wi*C >= 2^31: FT_ERR_UNSUPPORTED. */
+int ft_maxpool2x2s2_fwd(const void* x, void* y, int N, int Hi, int Wi, int C, int dtype, ft_stream_t stream);
+
 /* ---- experimental entry points (NOT part of the drop-in boundary) -------------------------------------------
- * Measured alternatives of the fused-block kernels that the default plans do not record (profiles/README.md has their
- * numbers).  They are exported by the library so that the tests and tools/dev can reach them, but they are declared only
+ * Measured alternatives (of the fused-block kernels, and of the VGG16 detector's FC layers) that the default plans do not
+ * record or record second (profiles/README.md has their numbers).  They are exported by the library so that the tests and tools/dev can reach them, but they are declared only
  * when the includer defines FT_EXPERIMENTAL; signatures may change between rounds. */
 #ifdef FT_EXPERIMENTAL
 /* Register-stationary strip form of the same identity block (csrc/bottleneck_rstat.hip; fp16, C = 256, P = 64, stride 1,
@@ -867,6 +876,27 @@ long long ft_bottleneck_cluster_workspace_bytes(const ft_bottleneck_desc* d);
 long long ft_bottleneck_cluster_status_offset(const ft_bottleneck_desc* d);
 int ft_bottleneck_cluster_fwd(const ft_bottleneck_desc* d, const void* x, const void* wstream, const float* tables, void* y,
                               void* workspace, ft_stream_t stream);
+
+/* ft_fc_fwd (csrc/vgg_ops.hip) — nn.Linear (+ ReLU) on a few hundred rows as a weight-streaming split-K GEMM (vgg.classifier.0 / .3
+ * of the VGG16 detector's region head).  Measured at 300 rows it does not beat ft_conv2d_fwd on the [rows,1,1,K] view (138 vs 115 us
+ * at K = 25088, 38 vs 33 us at K = 4096; profiles/README.md), so detection.nets.vgg16 records it second, as the "fc" option.
+ * y[R,N] = act(x[R,K] . W[N,K]^T + bias[N]); fp16 x, W and y, fp32 accumulation on MFMA, bias float[N] (NULL: none), act
+ * FT_ACT_NONE or FT_ACT_RELU.  x and y are row-strided (x_stride >= K, y_stride >= N, in elements, multiples of
+ * 8), so an NHWC [R,7,7,512] buffer is the [R,25088] input as it stands.
+ *   constraints   K % 64 == 0, N % 64 == 0, any R >= 0; N*K, R*x_stride, R*y_stride and 64*R*N below 2^31; x, wpack, y, bias and
+ *                 workspace 16-byte aligned.  FT_F32 and every other shape: FT_ERR_UNSUPPORTED (ft_fc_supported returns the code
+ *                 ft_fc_fwd would, without pointers); negative sizes, short or odd strides, NULL / misaligned pointers, another
+ *                 act, a workspace below ft_fc_workspace_bytes(R, K, N): FT_ERR_INVALID_ARG.
+ *   ft_fc_pack    W fp16 [N,K] row-major -> wpack, N*K fp16, once per weight set: per 32 outputs g and 64-wide K-step t one 4 KB
+ *                 block, lane l of a wave holding W[32 g + (l & 31)][64 t + 32 (l >> 5) + 0..31].
+ *   two launches  K is split over workgroups (the grid fills 256 CUs at R <= 320, N = 4096); every slice writes an fp32 slab
+ *                 [slice][R][N] into `workspace`, the second launch sums the slabs in slice order, adds the bias, applies act and
+ *                 rounds once.  No atomics, no workgroup waits on another: the same call gives the same bits every time. */
+int ft_fc_supported(int dtype, int R, int K, int N, int x_stride, int y_stride);
+long long ft_fc_workspace_bytes(int R, int K, int N);
+int ft_fc_pack(const void* w, int N, int K, void* wpack, ft_stream_t stream);
+int ft_fc_fwd(int dtype, const void* x, int x_stride, const void* wpack, const float* bias, void* y, int y_stride, int R, int K,
+              int N, int act, void* workspace, size_t workspace_bytes, ft_stream_t stream);
 #endif /* FT_EXPERIMENTAL */
 
 #ifdef __cplusplus

@@ -1,6 +1,7 @@
-"""Person detection demo on the HIP path: the Faster R-CNN detector (flowtrack.pytorch_amd.detection.nets.resnetv1) on one image.
+"""Person detection demo on the HIP path: the Faster R-CNN detector (flowtrack.pytorch_amd.detection.nets: resnetv1 or vgg16) on
+one image.
 
-    python tools/detection/demo.py --net res101 --model CKPT.pth --num_classes 81 --person_id 1 --image frame.jpg [--fp16]
+    python tools/detection/demo.py --net res101|vgg16 --model CKPT.pth --num_classes 81 --person_id 1 --image frame.jpg [--fp16]
 
 The image is read with PIL and converted to BGR (the reference reads its frames with cv2.imread); `--model` is a checkpoint of the
 reference's detector (a state_dict, or a dict with one under 'state_dict' / 'model'); without it the net runs on the synthetic weights
@@ -23,12 +24,12 @@ if ROOT not in sys.path:
 from flowtrack.pytorch_amd import synth   # noqa: E402
 from flowtrack.pytorch_amd.detection import nets, test as det_test   # noqa: E402
 
-NETS = {"res50": 50, "res101": 101, "res152": 152}
+NETS = {"res50": 50, "res101": 101, "res152": 152, "vgg16": None}        # tools/tracking/demo.py:53-62 of the reference: --detect_net
 
 
 def build_parser():
     parser = argparse.ArgumentParser()
-    parser.add_argument("--net", default="res101", choices=sorted(NETS), help="trunk depth")
+    parser.add_argument("--net", default="res101", choices=sorted(NETS), help="trunk")
     parser.add_argument("--model", default="", type=str, metavar="PATH", help="detector checkpoint (default: synthetic weights)")
     parser.add_argument("--num_classes", type=int, default=81, help="classes of the checkpoint, background included")
     parser.add_argument("--person_id", type=int, default=1, help="class id of 'person'")
@@ -47,8 +48,9 @@ def load_image_bgr(path):
 
 
 def build_net(args):
-    net = nets.resnetv1(NETS[args.net])
+    net = nets.vgg16() if args.net == "vgg16" else nets.resnetv1(NETS[args.net])
     net.create_architecture(args.num_classes, tag="default")
+    fill = synth.fill_vgg_detector_state_dict if args.net == "vgg16" else synth.fill_detector_state_dict
     if args.model:
         ckpt = torch.load(args.model, map_location="cpu")
         for key in ("state_dict", "model"):
@@ -56,7 +58,7 @@ def build_net(args):
                 ckpt = ckpt[key]
         net.load_state_dict(ckpt)
     else:
-        net.load_state_dict(synth.fill_detector_state_dict(net.state_dict(), args.seed))
+        net.load_state_dict(fill(net.state_dict(), args.seed))
     net = net.cuda().eval()
     net.compute_dtype = torch.float16 if args.fp16 else torch.float32
     return net

@@ -9,14 +9,15 @@ from flowtrack.pytorch_amd import synth
 
 
 def frcnn(name, H, W, dt):
-    """python tools/dev/net_bench.py frcnn_resnet101 600 1000 [fp16]: the detector on one H x W blob (a uint8 frame of that size at
+    """python tools/dev/net_bench.py frcnn_resnet101|frcnn_vgg16 600 1000 [fp16]: the detector on one H x W blob (a uint8 frame of that size at
     scale 1): the per-launch tables of the trunk + RPN plan and of the region-head plan, then the per-image time of the three steps."""
     import time
     import numpy as np
     from flowtrack.pytorch_amd.detection import nets, test as det_test
-    net = nets.resnetv1(int(name[len("frcnn_resnet"):]))
+    vgg = name == "frcnn_vgg16"
+    net = nets.vgg16() if vgg else nets.resnetv1(int(name[len("frcnn_resnet"):]))
     net.create_architecture(81, tag="default")
-    net.load_state_dict(synth.fill_detector_state_dict(net.state_dict(), 1))
+    net.load_state_dict((synth.fill_vgg_detector_state_dict if vgg else synth.fill_detector_state_dict)(net.state_dict(), 1))
     net = net.cuda().eval()
     net.compute_dtype = torch.float16 if dt == "fp16" else torch.float32
     frame = torch.from_numpy(synth.detector_frame(1, H, W)).cuda()
@@ -28,7 +29,7 @@ def frcnn(name, H, W, dt):
     head = next(iter(plan.heads.values()))
     print(f"{name} {dt}: blob {tuple(plan.x_static.shape[2:])}, net_conv {plan.net_conv.H}x{plan.net_conv.W}, {int(net._predictions['rois'].shape[0])} RoIs, "
           f"{len(dets)} person boxes; blocks on plain launches: trunk {plan.fallbacks or 'none'}, head {head.fallbacks or 'none'}")
-    glue = {"ft_rpn_softmax_fwd", "ft_rcnn_mean_pool_fwd"}
+    glue = {"ft_rpn_softmax_fwd", "ft_rcnn_mean_pool_fwd", "ft_maxpool2x2s2_fwd", "ft_fc_fwd"}
     for what, prog in (("trunk + RPN", plan.prog), ("region head", head.prog)):
         labels = {idx: lab for lab, idx, _, _ in prog.conv_records}
         labels.update({r[1]: r[0] for r in prog.fused_records})
