@@ -187,6 +187,11 @@ _PROTOTYPES = {
     "ft_rcnn_detections_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, POINTER(c_float), POINTER(c_float), c_float, c_float,
                                        c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ft_maxpool2x2s2_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "ft_topk_desc_f32_workspace_bytes": (ctypes.c_longlong, [c_int, c_int]),
+    "ft_topk_desc_f32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ft_proposal_rois_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "ft_detect_select_fwd": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_float, c_float, c_int,
+                                     c_int, c_void_p, c_void_p, c_void_p]),
     "ft_fc_supported": (c_int, [c_int] * 6),
     "ft_fc_workspace_bytes": (ctypes.c_longlong, [c_int, c_int, c_int]),
     "ft_fc_pack": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),

@@ -26,6 +26,8 @@ Two plans (hip_ops.Program launch lists, replayed as HIP graphs) per blob shape 
 Between them: detection.proposal.proposal_layer (its one device -> host read: the kept count); rows past that count carry zero
 RoIs and are dropped.  Behind them: ft_rcnn_detections_fwd (class softmax, un-normalised deltas, and for im_detect the boxes).
 Everything that does not depend on the trunk lives in _FasterRCNN.
+detect_enqueue is the same frame step with nothing read from the device (proposal.proposal_layer_device between the plans,
+ft_detect_select_fwd behind them): what detection.test.detect_persons_clip enqueues for every frame of a clip.
 
 The blob has any height and width, so every map size follows (n + 2p - k) // s + 1 (the VGG pools: n // 2) and odd maps occur at
 every stage.  The ResNet block recorder (resnet.record_block, shared with the pose trunks) takes a fused form only where the
@@ -277,6 +279,58 @@ class _FasterRCNN(HipModule):
             out["pool5"] = hp.pool5.t[:n].permute(0, 3, 1, 2).float().contiguous()
             out["fc7"] = hp.fc7.t[:n, 0, 0, :].float().contiguous()
         return out
+
+    @torch.no_grad()
+    def detect_enqueue(self, plan: Plan, im_info, frame_shape, out_slot, person_id: int = 1, thresh: float = 0.3, min_score: float = 0.0,
+                       extra=None, extra_count=None, max_keep: int = 0) -> None:
+        """detect_staged + the person NMS of detection.test.detect_persons for the staged frame, enqueued on the current stream with
+        nothing read from the device: the trunk plan, proposal.proposal_layer_device into the head plan's rois at rows =
+        post_nms_topN (the row count region_head uses whenever n <= post_nms_topN: both paths replay the identical head plan), the
+        head plan, ft_rcnn_detections_fwd over all rows (rows past the kept count come from zero RoIs; ft_detect_select_fwd masks
+        them), ft_detect_select_fwd into out_slot = (dets fp32 [cap,5], count int32 [1]), both CUDA tensors (views of a clip's
+        buffers).  extra: fp32 CUDA [M,5] boxes that join the NMS (extra_count: int32 [1] on the device, all M rows without it).
+        self._predictions is not touched.  A plan's first run builds and captures it (HipModule.run): that one call waits."""
+        self._check_eval()
+        K, A = self._num_classes, self._num_anchors
+        device = plan.device
+        im_info = [float(v) for v in np.asarray(im_info, dtype=np.float64).reshape(-1)[:3]]
+        dets, count = out_slot
+        for t, dt, what in ((dets, torch.float32, "dets [cap,5]"), (count, torch.int32, "count [1]")):
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != device or not t.is_contiguous():
+                raise FlowtrackHipError(f"detect_enqueue out_slot: {what} is a contiguous {dt} tensor on {device}")
+        if dets.dim() != 2 or dets.shape[1] != 5 or dets.shape[0] < 1 or count.numel() != 1:
+            raise FlowtrackHipError(f"detect_enqueue out_slot: expected (dets [cap,5], count [1]), got {tuple(dets.shape)}, {tuple(count.shape)}")
+        M = 0
+        if extra is not None:
+            if not isinstance(extra, torch.Tensor) or extra.dtype != torch.float32 or extra.device != device or extra.dim() != 2 or \
+                    extra.shape[1] != 5 or not extra.is_contiguous():
+                raise FlowtrackHipError("detect_enqueue extra: expected a contiguous fp32 [M,5] tensor on the net's device")
+            M = int(extra.shape[0])
+            if M == 0:
+                extra = None
+        rows = max(RPN_POST_DEFAULT if self.rpn_post_nms_topN is None else int(self.rpn_post_nms_topN), 1)
+        self.run(plan)
+        hp = self.head_plan(plan, rows)
+        _, n_rois = proposal.proposal_layer_device(plan.rpn_cls_prob, plan.rpn_bbox_pred, im_info, "TEST", self._feat_stride[0], plan.anchors, A,
+                                                   hp.rois, pre_nms_topN=self.rpn_pre_nms_topN, post_nms_topN=self.rpn_post_nms_topN,
+                                                   nms_thresh=self.rpn_nms_thresh)
+        self.run(hp)
+        fc = hp.fc_out.view(rows, 5 * K)
+        cls_score, raw = fc[:, :K].contiguous(), fc[:, K:].contiguous()
+        cls_prob = torch.empty((rows, K), dtype=torch.float32, device=device)
+        boxes = torch.empty((rows, 4 * K), dtype=torch.float32, device=device)
+        lib = _lib.load()
+        with torch.cuda.device(device):
+            stream = current_stream_handle(device)
+            check(lib.ft_rcnn_detections_fwd(cls_score.data_ptr(), raw.data_ptr(), hp.rois.data_ptr(), rows, K,
+                                             (ctypes.c_float * 4)(*BBOX_NORMALIZE_STDS), (ctypes.c_float * 4)(*BBOX_NORMALIZE_MEANS),
+                                             im_info[2], float(frame_shape[0]), float(frame_shape[1]), cls_prob.data_ptr(), None,
+                                             boxes.data_ptr(), stream), "ft_rcnn_detections_fwd")
+            check(lib.ft_detect_select_fwd(cls_prob.data_ptr(), boxes.data_ptr(), rows, n_rois.data_ptr(), K, int(person_id),
+                                           extra.data_ptr() if extra is not None else None, M,
+                                           extra_count.data_ptr() if extra_count is not None else None, float(min_score), float(thresh),
+                                           int(max_keep), int(dets.shape[0]), dets.data_ptr(), count.data_ptr(), stream),
+                  "ft_detect_select_fwd")
 
     def forward(self, image, im_info, gt_boxes=None, mode="TRAIN", keep_intermediates: bool = False):
         if mode != "TEST" or gt_boxes is not None:

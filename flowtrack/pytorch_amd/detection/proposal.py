@@ -4,6 +4,8 @@
     proposal_layer         layer_utils/proposal_layer.py:19-56: decode + clip (ft_rpn_decode_boxes), top-N by a stable
                            descending sort, ft_box_nms (IoU > thresh, capped at post_nms_topN) and the [n,5] blob, with exactly
                            one device -> host read: the kept count
+    proposal_layer_device  the same blob without that read: ft_topk_desc_f32 for the sort, ft_box_nms, ft_proposal_rois_fwd into a
+                           caller-given [rows,5] buffer; returns device tensors only (the frame step of detect_persons_clip)
     crop_pool_layer        nets/network.py:93-121 on CropAndResizeFunction + F.max_pool2d, NCHW (the training drop-in)
     roi_crop_nhwc          the same values from dense NHWC fp16 / fp32 features in one launch (ft_roi_crop_nhwc_fwd): the
                            [R,pooled,pooled,C] tensor is the input of the layer4 convs (ft_conv2d_fwd, N = R)
@@ -18,7 +20,7 @@ from .. import _lib
 from .._lib import FlowtrackHipError, check
 from .ops import CropAndResizeFunction, _fp32_cuda, _ptr, _stream, box_nms_sorted
 
-__all__ = ["generate_anchors", "generate_anchors_pre", "decode_boxes", "proposal_layer", "crop_pool_layer", "roi_crop_nhwc", "RPN_DEFAULTS"]
+__all__ = ["generate_anchors", "generate_anchors_pre", "decode_boxes", "proposal_layer", "proposal_layer_device", "topk_desc", "crop_pool_layer", "roi_crop_nhwc", "RPN_DEFAULTS"]
 
 #: model/config.py: (RPN_PRE_NMS_TOP_N, RPN_POST_NMS_TOP_N, RPN_NMS_THRESH) per mode
 RPN_DEFAULTS = {"TEST": (6000, 300, 0.7), "TRAIN": (12000, 2000, 0.7)}
@@ -107,6 +109,60 @@ def proposal_layer(rpn_cls_prob, rpn_bbox_pred, im_info, cfg_key, feat_stride, a
     proposals, scores = proposals[keep], scores[keep]
     blob = torch.cat((proposals.new_zeros((n, 1)), proposals), 1)
     return blob, scores
+
+
+def topk_desc(scores: torch.Tensor, k: int):
+    """ft_topk_desc_f32: the first k entries of scores.sort(descending=True, stable=True) of an fp32 CUDA vector as (sorted
+    float32 [k], order int32 [k]), one launch, nothing read back.  1 <= k <= min(n, 16384), n <= 65536."""
+    scores = _fp32_cuda(scores, "topk_desc scores", (None,))
+    n, k = scores.shape[0], int(k)
+    order = torch.empty(k, dtype=torch.int32, device=scores.device)
+    out = torch.empty(k, dtype=torch.float32, device=scores.device)
+    lib = _lib.load()
+    nbytes = lib.ft_topk_desc_f32_workspace_bytes(n, k)
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=scores.device) if nbytes > 0 else None
+    with torch.cuda.device(scores.device):
+        check(lib.ft_topk_desc_f32(_ptr(scores), n, k, _ptr(order), _ptr(out), _ptr(workspace), _stream(scores.device)), "ft_topk_desc_f32")
+    return out, order
+
+
+def proposal_layer_device(rpn_cls_prob, rpn_bbox_pred, im_info, cfg_key, feat_stride, anchors, num_anchors, rois, *, pre_nms_topN=None,
+                          post_nms_topN=None, nms_thresh=None):
+    """proposal_layer with every step enqueued and nothing read from the device: the blob goes into the caller's `rois` [rows,5]
+    fp32 CUDA buffer (the first n = min(kept, rows) rows; the rest are zeroed) and n stays on the device.  Returns (rois, n_rois
+    int32 [1]).  `anchors` is a CUDA tensor; im_info is the host's copy.  The NMS is capped at min(post_nms_topN, rows)."""
+    if isinstance(cfg_key, bytes):
+        cfg_key = cfg_key.decode("utf-8")
+    if cfg_key not in RPN_DEFAULTS:
+        raise FlowtrackHipError(f"proposal_layer_device: cfg_key {cfg_key!r} is neither 'TEST' nor 'TRAIN'")
+    pre, post, thresh = RPN_DEFAULTS[cfg_key]
+    pre = pre if pre_nms_topN is None else int(pre_nms_topN)
+    post = post if post_nms_topN is None else int(post_nms_topN)
+    thresh = thresh if nms_thresh is None else float(nms_thresh)
+    rpn_cls_prob = _fp32_cuda(rpn_cls_prob, "proposal_layer_device rpn_cls_prob", (1, None, None, 2 * num_anchors))
+    rpn_bbox_pred = _fp32_cuda(rpn_bbox_pred, "proposal_layer_device rpn_bbox_pred", rpn_cls_prob.shape[:3] + (4 * num_anchors,))
+    if not isinstance(rois, torch.Tensor) or not rois.is_cuda or rois.dtype != torch.float32 or rois.dim() != 2 or rois.shape[1] != 5 or \
+            rois.shape[0] < 1 or not rois.is_contiguous() or rois.device != rpn_cls_prob.device:
+        raise FlowtrackHipError("proposal_layer_device rois: expected a contiguous fp32 CUDA buffer [rows,5], rows >= 1, on the maps' device")
+    rows = int(rois.shape[0])
+    device = rpn_cls_prob.device
+    im_h, im_w = float(im_info[0]), float(im_info[1])          # the host's copy: no device read
+    scores = rpn_cls_prob[:, :, :, num_anchors:].contiguous().view(-1)
+    anchors = _fp32_cuda(anchors, "proposal_layer_device anchors", (scores.shape[0], 4))
+    proposals = decode_boxes(anchors, rpn_bbox_pred.detach().view(-1, 4), im_h, im_w)
+    n_all = scores.shape[0]
+    n_rois = torch.zeros(1, dtype=torch.int32, device=device)
+    if n_all == 0:
+        rois.zero_()
+        return rois, n_rois
+    k = min(pre, n_all) if pre > 0 else n_all
+    top_scores, order = topk_desc(scores.detach(), k)
+    top = proposals.index_select(0, order)
+    keep, count = box_nms_sorted(torch.cat((top, top_scores.view(-1, 1)), 1), thresh, inclusive=False, max_keep=min(post, rows) if post > 0 else rows)
+    with torch.cuda.device(device):
+        check(_lib.load().ft_proposal_rois_fwd(_ptr(top), _ptr(keep), _ptr(count), k, rows, _ptr(rois), _ptr(n_rois), _stream(device)),
+              "ft_proposal_rois_fwd")
+    return rois, n_rois
 
 
 def crop_pool_layer(bottom, rois, max_pool=True, feat_stride=16.0, pooled=POOLING_SIZE):

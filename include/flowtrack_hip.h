@@ -846,6 +846,45 @@ int ft_rcnn_detections_fwd(const float* cls_score, const float* bbox_pred, const
  * Hi < 2, Wi < 2 and bad arguments: FT_ERR_INVALID_ARG; N*Hi*Wi*C >= 2^31: FT_ERR_UNSUPPORTED. */
 int ft_maxpool2x2s2_fwd(const void* x, void* y, int N, int Hi, int Wi, int C, int dtype, ft_stream_t stream);
 
+/* ---- the detector's frame step without a host wait (csrc/detect_pass_ops.hip) ----------------------------------
+ * What detection.proposal.proposal_layer and detection.test.detect_persons do in torch around a device -> host read, with
+ * every count in a device int32 word, so that the frames of a clip are enqueued back to back (detection/test.py:
+ * detect_persons_clip).  The conventions of the region stage above hold: asynchronous on `stream`, a refused call launches
+ * nothing, fp32 with every operation rounded separately, indices and counts read from device data are clamped or
+ * range-checked before they address anything. */
+
+/* ft_topk_desc_f32 — the first k entries of torch.sort(scores, descending=True, stable=True) of scores float[n]: sorted
+ * float[k] (the scores themselves, bit for bit scores[order[i]]) and order int32[k] (indices into scores).  The order is
+ * that of the unique key (order key of the score, index): larger scores first, equal scores by ascending index, -0.0 ties
+ * with +0.0, every NaN sorts in front of +inf (NaNs among themselves by index).  One launch of one 1024-thread workgroup:
+ * the scores read once into registers, radix select of the k-th key in 8-bit digits, the k winners compacted into LDS,
+ * merge sort there; no assumption on the spread of the scores.  Entries past k of order / sorted are not
+ * written.  n = 0 or k = 0: FT_OK, no launch.  FT_ERR_UNSUPPORTED outside 1 <= k <= min(n, 16384), n <= 65536.
+ * workspace: ft_topk_desc_f32_workspace_bytes(n, k) bytes; this form needs none (the query returns 0 and NULL is accepted):
+ * the argument is there so that a form for larger n keeps the signature. */
+long long ft_topk_desc_f32_workspace_bytes(int n, int k);
+int ft_topk_desc_f32(const float* scores, int n, int k, int32_t* order, float* sorted, void* workspace, ft_stream_t stream);
+
+/* ft_proposal_rois_fwd — the blob of layer_utils/proposal_layer.py:52-55 from ft_box_nms's output: boxes float[m,4] (the
+ * boxes that went into the NMS, in its order), keep int32[m], *count.  With c = min(*count, rows, m) clamped at 0:
+ * rois[j] = (0, boxes[keep[j]]) for j < c (a keep entry outside [0, m) gives a zero row), every row from c to rows is zeroed
+ * (the buffer is reused from frame to frame), *n_rois = c.  rows = 0: FT_OK, nothing is written. */
+int ft_proposal_rois_fwd(const float* boxes, const int32_t* keep, const int32_t* count, int m, int rows, float* rois,
+                         int32_t* n_rois, ft_stream_t stream);
+
+/* ft_detect_select_fwd — lib/tracking/net_utils.py:14-34 (`detect`) behind im_detect, one workgroup.  Candidates: the rows
+ * r < *n_rois (clamped to [0, R]) of cls_prob float[R,K] / pred_boxes float[R,4K] as (pred_boxes[r, 4p:4p+4], cls_prob[r, p])
+ * with p = person_id, followed by the first *extra_count rows (all M when extra_count is NULL) of extra float[M,5]
+ * (extra = NULL: none).  Candidates with score < min_score are dropped (0 keeps every probability: the reference).  Stable
+ * descending sort by score in the order of ft_topk_desc_f32 (detector rows before extras on ties), greedy NMS with the float
+ * expressions of ft_box_nms at inclusive = 0 (IoU > thresh suppresses), stopping after max_keep survivors (<= 0: cap).
+ * dets float[cap,5]: the survivors (x1, y1, x2, y2, score) in kept order, zeros past *count.
+ * FT_ERR_INVALID_ARG: person_id outside [0, K), cap < 1, NaN thresh / min_score, a missing pointer;
+ * FT_ERR_UNSUPPORTED: R + M > 1024. */
+int ft_detect_select_fwd(const float* cls_prob, const float* pred_boxes, int R, const int32_t* n_rois, int K, int person_id,
+                         const float* extra, int M, const int32_t* extra_count, float min_score, float thresh, int max_keep,
+                         int cap, float* dets, int32_t* count, ft_stream_t stream);
+
 /* ---- experimental entry points (NOT part of the drop-in boundary) -------------------------------------------
  * Measured alternatives (of the fused-block kernels, and of the VGG16 detector's FC layers) that the default plans do not
  * record or record second (profiles/README.md has their numbers).  They are exported by the library so that the tests and tools/dev can reach them, but they are declared only

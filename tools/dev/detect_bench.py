@@ -1,11 +1,21 @@
 """Times the detector's region-stage entry points (csrc/detect_ops.hip) at the detector's own shapes.
 
     python tools/dev/detect_bench.py [--iters 30] [--warmup 5] [--out detect_bench.json]
+    python tools/dev/detect_bench.py --clip [--frames 32] [--rounds 5] [--nets res101,vgg16] [--out detect_clip_bench.json]
 
 Shapes: a 600 x 1000 image at stride 16 -> features [1,1024,38,63], 9 anchors per cell = 21 546 boxes to decode, NMS over the top
 6000 of them, 300 RoIs.  Each call is timed alone with device events after a warm-up; printed per entry: the median and minimum
 in microseconds, the bytes it has to move (every input and output element once, the NMS mask written and read once) and the
 ratio of that floor at the achievable HBM rate to the measured median.
+
+--clip: the detector over a clip, two forms alternated in one process (windows a, b, a, b, ... as tools/dev/flip_bench.py), fp16, 81
+classes, synthetic weights, T frames of 600 x 1000 (blob scale 1) resident on the device:
+  (a) per frame   a loop of detection.test.detect_persons: per frame two torch.sort calls, two count reads, one download;
+  (b) clip        detection.test.detect_persons_clip: every frame step enqueued without a host wait, one download.
+A window is one pass over the T frames, host-timed between device synchronisations (form (a) is bound by the host, which device
+events around it would also see, but only as a whole).  Both forms are warmed first and their results compared bit for bit.  Also
+event-times ft_topk_desc_f32 at n = 21 546, k = 6000 against the torch.sort + slice it replaces, on spread scores and on scores
+within two ulps of 0.5 (what synthetic RPN heads give).
 """
 from __future__ import annotations
 
@@ -47,12 +57,93 @@ def _time(fn, iters, warmup):
     return ts[len(ts) // 2], ts[0]
 
 
+def clip_main(args):
+    import statistics
+    import time
+
+    from flowtrack.pytorch_amd import synth
+    from flowtrack.pytorch_amd.detection import nets, test as det_test
+    dev = torch.device("cuda:0")
+    T, K, person = args.frames, 81, 1
+    frames = torch.from_numpy(np.stack([synth.detector_frame(t, 600, 1000) for t in range(T)])).to(dev)
+    report = {"frames": T, "rounds": args.rounds, "nets": {}}
+    for name in args.nets.split(","):
+        net = nets.vgg16() if name == "vgg16" else nets.resnetv1(int(name[3:]))
+        net.create_architecture(K, tag="default")
+        fill = synth.fill_vgg_detector_state_dict if name == "vgg16" else synth.fill_detector_state_dict
+        net.load_state_dict(fill(net.state_dict(), 1))
+        net = net.to(dev).eval()
+        net.compute_dtype = torch.float16
+
+        def per_frame():
+            return [det_test.detect_persons(net, frames[t], person, 0.3) for t in range(T)]
+
+        def clip():
+            return det_test.detect_persons_clip(net, frames, person, 0.3)
+
+        forms = (("per_frame", per_frame), ("clip", clip))
+        for _ in range(2):                                  # plans, tile picks, graphs, torch's own kernels
+            outs = [fn() for _, fn in forms]
+        same = all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(*outs))
+        print(f"{name}: {T} frames, {sum(len(d) for d in outs[0])} person boxes, clip == per frame bit for bit: {same}")
+        ms = {k: [] for k, _ in forms}
+        for r in range(args.rounds):
+            for k, fn in forms:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ms[k].append((time.perf_counter() - t0) * 1e3 / T)
+                print(f"{name} round {r} {k:10s} {ms[k][-1]:8.4f} ms/frame")
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        for k, v in ms.items():
+            print(f"{name} {k:10s} median {med[k]:.4f} ms/frame (min {min(v):.4f}, max {max(v):.4f}; {1e3 / med[k]:.0f} frames/s)")
+        print(f"{name} per frame / clip = {med['per_frame'] / med['clip']:.3f}")
+        report["nets"][name] = {"ms_per_frame": ms, "median_ms": med, "ratio": med["per_frame"] / med["clip"], "bit_equal": bool(same)}
+        del net
+    # the sort alone
+    lib = _lib.load()
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    n, k = 21546, N_NMS
+    rng = np.random.RandomState(0)
+    inputs = {"spread": rng.permutation(n).astype(np.float32) / n,
+              "near_half": (np.uint32(0x3F000000) + rng.randint(-2, 3, n)).astype(np.uint32).view(np.float32)}
+    order, out = torch.empty(k, dtype=torch.int32, device=dev), torch.empty(k, dtype=torch.float32, device=dev)
+    report["topk"] = {}
+    for label, host in inputs.items():
+        sc = torch.from_numpy(host).to(dev)
+
+        def torch_sort():
+            v, i = sc.sort(descending=True, stable=True)
+            return v[:k], i[:k]
+
+        check(lib.ft_topk_desc_f32(p(sc), n, k, p(order), p(out), None, stream), "ft_topk_desc_f32")
+        tv, ti = torch_sort()
+        ok = bool(torch.equal(ti, order.long()) and torch.equal(tv.view(torch.int32), out.view(torch.int32)))
+        a = _time(lambda: lib.ft_topk_desc_f32(p(sc), n, k, p(order), p(out), None, stream), args.iters, args.warmup)
+        b = _time(torch_sort, args.iters, args.warmup)
+        print(f"top {k} of {n} ({label}): ft_topk_desc_f32 median {a[0]:.2f} us (min {a[1]:.2f}), torch.sort + slice median {b[0]:.2f} us "
+              f"(min {b[1]:.2f}), equal: {ok}")
+        report["topk"][label] = {"ft_topk_desc_f32_us": [round(a[0], 2), round(a[1], 2)], "torch_sort_us": [round(b[0], 2), round(b[1], 2)], "equal": ok}
+    print(json.dumps(report))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(report, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--clip", action="store_true", help="the detector over a clip: per-frame loop against detect_persons_clip")
+    ap.add_argument("--frames", type=int, default=32, help="--clip: frames per window")
+    ap.add_argument("--rounds", type=int, default=5, help="--clip: alternations a, b")
+    ap.add_argument("--nets", default="res101,vgg16", help="--clip: trunks, comma separated")
     args = ap.parse_args()
+    if args.clip:
+        return clip_main(args)
     lib = _lib.load()
     dev = torch.device("cuda:0")
     rng = np.random.RandomState(0)

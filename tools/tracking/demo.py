@@ -12,9 +12,15 @@ Multi-GPU decomposition (one process per GPU): the two embarrassingly parallel p
   phase 2: pose of the DETECTOR boxes of every frame, frames sharded by index, keypoints all-gathered;
   phase 3 (rank 0, sequential in t as the method requires): propagation, union + NMS, pose of the propagated-only
            boxes that survive NMS, tracking ids.
-The person detector itself is out of scope: boxes come from the synthetic clip generator
-(ground truth + jitter) or from --dets FILE.npz.  Checkpoints: --pose_model / --flow_model in the reference formats;
-without them deterministic synthetic weights are used (outputs are then only structurally meaningful).
+Detector boxes: by default the synthetic clip generator's (ground truth + jitter).  With --detector {res50,res101,res152,vgg16}
+a phase 0 runs the Faster R-CNN person detector over the clip's frames (detection.test.detect_persons_clip: every frame step
+enqueued without a host wait, one download; frames sharded by index under torchrun like phase 2) and its boxes replace the
+generator's dets[t]; everything downstream is unchanged.  The reference's frame step does ONE NMS over the detector's person rows
+and the propagated boxes (lib/tracking/net_utils.py:14-34 with prop_dets).  Here the propagated boxes exist only inside the
+sequential pass, so phase 0 NMSes the detector's rows alone (--det_nms) and the tracking pass NMSes the union of its survivors
+with the propagated boxes again: two NMS steps where the reference has one.
+Checkpoints: --pose_model / --flow_model / --det_model in the reference formats; without them deterministic synthetic weights are
+used (outputs are then only structurally meaningful).
 """
 from __future__ import absolute_import, division, print_function
 
@@ -82,6 +88,41 @@ def build_nets(args, device):
     if args.fp16:
         pose.compute_dtype = flow.compute_dtype = torch.float16
     return pose, flow
+
+
+DETECTORS = {"res50": 50, "res101": 101, "res152": 152, "vgg16": None}
+
+
+def build_detector(args, device):
+    """The person detector of --detector: --det_model (a state_dict, or a dict with one under 'state_dict' / 'model'), synthetic
+    weights without it, as tools/detection/demo.py."""
+    from flowtrack.pytorch_amd.detection import nets
+    net = nets.vgg16() if args.detector == "vgg16" else nets.resnetv1(DETECTORS[args.detector])
+    net.create_architecture(args.det_classes, tag="default")
+    if args.det_model:
+        ckpt = torch.load(args.det_model, map_location="cpu")
+        for key in ("state_dict", "model"):
+            if isinstance(ckpt, dict) and key in ckpt and isinstance(ckpt[key], dict):
+                ckpt = ckpt[key]
+        net.load_state_dict(ckpt)
+    else:
+        fill = synth.fill_vgg_detector_state_dict if args.detector == "vgg16" else synth.fill_detector_state_dict
+        net.load_state_dict(fill(net.state_dict(), 11))
+    net = net.to(device).eval()
+    net.compute_dtype = torch.float16 if args.fp16 else torch.float32
+    return net
+
+
+def detect_clip(det_net, frames, person_id, thresh=0.3, min_score=0.0, rank=0, world=1, target_size=600, max_size=1000):
+    """Phase 0: the detector's person boxes of every frame, [n_t,5] float32 each, on every rank.  Frames are sharded by index; a
+    rank enqueues its frames' detector steps without a host wait (detection.test.clip_enqueue), the packed results are gathered
+    by rows and downloaded once."""
+    from flowtrack.pytorch_amd.detection import test as det_test
+    T = len(frames)
+    lo, hi = parallel.shard_range(T, rank, world)
+    handle = det_test.clip_enqueue(det_net, frames[lo:hi], person_id, thresh, min_score, target_size=target_size, max_size=max_size)
+    packed = parallel.all_gather_rows(det_test.clip_pack(handle), T)
+    return det_test.clip_unpack(packed.cpu().numpy())
 
 
 def _sync(dev):
@@ -405,10 +446,12 @@ def run_clips(clips, pose_net, flow_net, thresh=0.3, flow_batch=16, pose_frames=
     return results, tm
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description="Pose estimation + flow-based tracking in video (HIP path)")
     ap.add_argument("--frames", type=int, default=60)
     ap.add_argument("--people", type=int, default=5)
+    ap.add_argument("--height", type=int, default=384, help="frame height of the synthetic clip")
+    ap.add_argument("--width", type=int, default=512, help="frame width of the synthetic clip")
     ap.add_argument("--pose_backbone", default=50, type=int, help="50, 101, 152")
     ap.add_argument("--pose_head", default="deconv", choices=("deconv", "fpn", "pose"),
                     help="pose model factory (the reference's opt.model): ResNet + 3-deconv head, ResNet + FPN head, or ResNet + "
@@ -431,7 +474,21 @@ def main(argv=None):
     ap.add_argument("--max_boxes", type=str, default="auto",
                     help="boxes kept per frame after NMS: 'none' (the reference: every survivor), an integer, '2x' = twice the "
                          "detector boxes; 'auto' = 'none' with --pose_model, '2x' with the synthetic (untrained) weights")
-    args = ap.parse_args(argv)
+    ap.add_argument("--detector", type=str, default="", choices=("",) + tuple(sorted(DETECTORS)),
+                    help="run the Faster R-CNN person detector over the clip (phase 0) instead of taking the generator's boxes")
+    ap.add_argument("--det_model", type=str, default="", help="detector checkpoint (default: synthetic weights)")
+    ap.add_argument("--det_classes", type=int, default=81, help="classes of the detector checkpoint, background included")
+    ap.add_argument("--det_person_id", type=int, default=1, help="class id of 'person'")
+    ap.add_argument("--det_min_score", type=float, default=0.0, help="person rows below this score are dropped ahead of the NMS (0: the reference)")
+    ap.add_argument("--det_nms", type=float, default=0.3, help="NMS threshold of the detector's person boxes")
+    ap.add_argument("--det_target_size", type=int, default=600, help="the detector's TEST.SCALES[0]")
+    ap.add_argument("--det_max_size", type=int, default=1000, help="the detector's TEST.MAX_SIZE")
+    return ap
+
+
+def run(args):
+    """What main() runs for the parsed `args`: (per-frame dict list on rank 0 | None, the detector boxes per frame (the
+    generator's without --detector) | None in the --clips mode, timing dict)."""
     max_boxes = {"auto": None if args.pose_model else "2x", "none": None, "2x": "2x"}.get(args.max_boxes)
     if args.max_boxes not in ("auto", "none", "2x"):
         max_boxes = int(args.max_boxes)
@@ -447,9 +504,11 @@ def main(argv=None):
     if args.clips > 1:
         if args.device_pass:
             raise SystemExit("--device_pass runs one clip (the interleaved clips share their host pass)")
+        if args.detector:
+            raise SystemExit("--detector runs one clip")
         if world != 1:
             raise SystemExit("--clips is the per-GPU throughput mode: run one process per GPU, each with its own clips")
-        clips = [synthetic_clip(args.frames, n_people=args.people, seed=c) for c in range(args.clips)]
+        clips = [synthetic_clip(args.frames, args.height, args.width, n_people=args.people, seed=c) for c in range(args.clips)]
         run_clips(clips, pose_net, flow_net, max_boxes=max_boxes, groups=args.groups, waves=args.waves)  # warm-up: plans / graphs of every replica
         for mode in (False, True):
             torch.cuda.synchronize(device)
@@ -458,23 +517,48 @@ def main(argv=None):
             dt = time.perf_counter() - t0
             print("clips: {} x {} frames, {}: {:.3f} s = {:.1f} frames/s total".format(
                 args.clips, args.frames, "interleaved" if mode else "one after the other", dt, args.clips * args.frames / dt))
-        return 0
-    frames, dets = synthetic_clip(args.frames, n_people=args.people)
-    run_clip(frames, dets, pose_net, flow_net, rank, world, max_boxes=max_boxes, device_pass=args.device_pass)   # warm-up: every plan / graph the timed run replays
+        return outs, None, tm
+    frames, gen_dets = synthetic_clip(args.frames, args.height, args.width, n_people=args.people)
+    det_net = None
+    if args.detector:
+        if not 0 <= args.det_person_id < args.det_classes:
+            raise SystemExit(f"--det_person_id {args.det_person_id} is not a class of a {args.det_classes}-class net")
+        det_net = build_detector(args, device)
+
+    def once():
+        dets, detect_s = gen_dets, None
+        if det_net is not None:                             # phase 0
+            t0 = time.perf_counter()
+            dets = detect_clip(det_net, frames, args.det_person_id, args.det_nms, args.det_min_score, rank, world, args.det_target_size,
+                               args.det_max_size)
+            _sync(device)
+            detect_s = time.perf_counter() - t0
+        out, tm = run_clip(frames, dets, pose_net, flow_net, rank, world, max_boxes=max_boxes, device_pass=args.device_pass)
+        if detect_s is not None:
+            tm["detect_s"] = detect_s
+        return out, dets, tm
+
+    once()                                                  # warm-up: every plan / graph the timed run replays
     parallel.barrier()
     t0 = time.perf_counter()
-    out, tm = run_clip(frames, dets, pose_net, flow_net, rank, world, max_boxes=max_boxes, device_pass=args.device_pass)
+    out, dets, tm = once()
     parallel.barrier()
     dt = time.perf_counter() - t0
     if rank == 0:
         n_ids = len({i for f in out for i in f["ids"]})
-        print("clip: {} frames {}x{} on {} GPU(s): {:.2f} s = {:.1f} frames/s (flow {:.2f} s, detector-box pose {:.2f} s, "
+        print("clip: {} frames {}x{} on {} GPU(s): {:.2f} s = {:.1f} frames/s ({}flow {:.2f} s, detector-box pose {:.2f} s, "
               "{}tracking pass {:.2f} s); {} track ids for {} people".format(
-                  args.frames, frames.shape[2], frames.shape[1], world, dt, args.frames / dt, tm["flow_s"], tm["pose_s"],
+                  args.frames, frames.shape[2], frames.shape[1], world, dt, args.frames / dt,
+                  "detector {} {:.2f} s, ".format(args.detector, tm["detect_s"]) if det_net is not None else "", tm["flow_s"], tm["pose_s"],
                   "device " if args.device_pass else "", tm["track_s"], n_ids, args.people))
         if args.save:
             np.savez_compressed(args.save, boxes=np.array([f["boxes"] for f in out], dtype=object),
                                 ids=np.array([f["ids"] for f in out], dtype=object), allow_pickle=True)
+    return out, dets, tm
+
+
+def main(argv=None):
+    run(build_parser().parse_args(argv))
     return 0
 
 
