@@ -146,6 +146,7 @@ _PROTOTYPES = {
     "ft_upsample_bilinear_ac_fwd": (c_int, [c_void_p, c_void_p] + [c_int] * 11 + [c_void_p, c_void_p]),
     "ft_scale_shift_act_nhwc_fwd": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong] + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_float,
                                             c_void_p]),
+    "ft_preact_conv1x1_fwd": (c_int, [c_void_p] * 7 + [c_int] * 12 + [c_void_p]),
     "ft_hourglass_down_fwd": (c_int, [c_void_p] + [c_int] * 7 + [c_void_p, c_int, c_int] + [c_void_p, c_int, c_int, c_void_p, c_void_p] * 2 + [c_void_p]),
     "ft_hourglass_up_fwd": (c_int, [c_void_p, c_void_p] + [c_int] * 11 + [c_void_p, c_int, c_int] + [c_void_p, c_int, c_int, c_void_p, c_void_p] + [c_void_p]),
     "ft_correlation_out_shape": (c_int, [c_int] * 8 + [POINTER(c_int)] * 3),

@@ -19,7 +19,7 @@ INCLUDE = os.path.join(ROOT, "include")
 LIB_PATH = os.path.join(HERE, "libflowtrack_hip.so")
 STAMP_PATH = os.path.join(HERE, ".libflowtrack_hip.stamp")
 
-SOURCES = ["conv_igemm.hip", "conv_igemm8.hip", "conv_fewout.hip", "conv_dispatch.hip", "bottleneck.hip", "bottleneck_rstat.hip", "bottleneck_stream.hip", "bottleneck_cluster.hip", "conv_direct.hip", "conv_wstat.hip", "aux_ops.hip", "fpn_ops.hip", "posenet_ops.hip", "hourglass_ops.hip", "flow_ops.hip", "crop_ops.hip", "track_ops.hip", "detect_ops.hip", "detect_net_ops.hip", "detect_pass_ops.hip", "vgg_ops.hip", "runtime.hip"]
+SOURCES = ["conv_igemm.hip", "conv_igemm8.hip", "conv_fewout.hip", "conv_dispatch.hip", "bottleneck.hip", "bottleneck_rstat.hip", "bottleneck_stream.hip", "bottleneck_cluster.hip", "conv_direct.hip", "conv_wstat.hip", "aux_ops.hip", "fpn_ops.hip", "posenet_ops.hip", "hourglass_ops.hip", "densenet_ops.hip", "flow_ops.hip", "crop_ops.hip", "track_ops.hip", "detect_ops.hip", "detect_net_ops.hip", "detect_pass_ops.hip", "vgg_ops.hip", "runtime.hip"]
 HEADERS = [os.path.join(CSRC, "ft_common.h"), os.path.join(CSRC, "conv_common.h"), os.path.join(CSRC, "conv_dispatch.h"), os.path.join(CSRC, "conv_wstat.h"), os.path.join(CSRC, "bilerp_ac.h"), os.path.join(INCLUDE, "flowtrack_hip.h")]
 EXPORTS = os.path.join(CSRC, "exports.map")   # version script: only ft_* leaves the library
 ARCH = "gfx950"

@@ -1118,6 +1118,64 @@ def record_scale_shift_act(prog: Program, x: ActView, y: ActView, scale: torch.T
              keep=(x.t, y.t, scale, shift))
 
 
+def pack_preact_weights(weight: torch.Tensor, dtype: torch.dtype, device) -> torch.Tensor:
+    """The weight operand of ft_preact_conv1x1_fwd (include/flowtrack_hip.h) from a 1x1 conv's [Cout, Cin(, 1, 1)] weights.
+    fp32: [Cout, Cin] as it is.  fp16: [Cout/32][ceil(Cin/64)][4][64][8], element (g, c, s, lane, e) = W[32 g + (lane & 31)]
+    [64 c + 32 (lane >> 5) + 8 s + e], zeros past Cin: the order in which a lane of mfma_f32_32x32x16_f16 takes its operand."""
+    w = weight.detach().to(torch.float32).cpu().reshape(weight.shape[0], -1)
+    cout, cin = w.shape
+    if cout % 32:
+        raise FlowtrackHipError(f"preact conv1x1: {cout} outputs, the kernel takes multiples of 32")
+    if dtype == torch.float32:
+        return w.contiguous().to(device)
+    if dtype != torch.float16:
+        raise FlowtrackHipError(f"preact conv1x1: unsupported dtype {dtype}")
+    chunks = (cin + 63) // 64
+    wp = torch.zeros((cout, chunks * 64), dtype=torch.float32)
+    wp[:, :cin] = w
+    wp = wp.view(cout // 32, 32, chunks, 2, 4, 8).permute(0, 2, 4, 3, 1, 5)         # [g, c, s, h, r, e]: lane = 32 h + r
+    return wp.contiguous().to(torch.float16).to(device)
+
+
+class PreactConv1x1:
+    """conv1x1(relu(bn_pre(x))) with an optional BatchNorm (+ ReLU) behind it and, pool=True at record time, the 2x2 average pool of
+    a DenseNet transition in front of the GEMM: one ft_preact_conv1x1_fwd launch.  record_unfused() records the same layer as
+    ft_scale_shift_act_nhwc_fwd + ft_conv2d_fwd (the activated copy of the input goes through memory)."""
+
+    def __init__(self, weight: torch.Tensor, pre_bn: dict, *, dtype: torch.dtype, device: torch.device, post_bn: Optional[dict] = None,
+                 act: Optional[str] = None, label: str = ""):
+        require_gpu(device)
+        if act not in (None, "relu"):
+            raise FlowtrackHipError(f"{label}: the pre-activation conv takes no activation or ReLU behind it")
+        self.cout, self.cin = weight.shape[0], weight.shape[1]
+        if tuple(weight.shape[2:]) not in ((), (1, 1)):
+            raise FlowtrackHipError(f"{label}: a 1x1 conv is expected")
+        self.dtype, self.device, self.label, self.act = dtype, device, label, ACT_CODES[act]
+        self.w = pack_preact_weights(weight, dtype, device)
+        self.pre = fold_scale_shift(self.cin, self.cin, None, pre_bn, device)
+        self.post = fold_scale_shift(self.cout, self.cout, None, post_bn, device) if post_bn is not None else (None, None)
+        self.unfused = FusedConv(weight.reshape(self.cout, self.cin, 1, 1), dtype=dtype, device=device, bn=post_bn, act=act, label=label)
+
+    def record(self, prog: Program, x: ActView, y: ActView, pool: bool = False) -> None:
+        yH, yW = (x.H // 2, x.W // 2) if pool else (x.H, x.W)
+        if x.C != self.cin or y.C != self.cout or (y.N, y.H, y.W) != (x.N, yH, yW) or x.rowpacked or y.rowpacked:
+            raise FlowtrackHipError(f"{self.label}: views do not line up ({tuple(x.t.shape)} C={x.C} -> {tuple(y.t.shape)} C={y.C}, pool={pool})")
+        if x.t.dtype != self.dtype or y.t.dtype != self.dtype or not x.t.is_contiguous() or not y.t.is_contiguous():
+            raise FlowtrackHipError(f"{self.label}: buffers must be contiguous {self.dtype}")
+        flops = 2.0 * y.N * yH * yW * self.cin * self.cout
+        prog.flops += flops
+        prog.fused_records.append((self.label, len(prog.calls), flops))
+        prog.add("ft_preact_conv1x1_fwd", x.t.data_ptr(), self.w.data_ptr(), self.pre[0].data_ptr(), self.pre[1].data_ptr(),
+                 self.post[0].data_ptr() if self.post[0] is not None else None, self.post[1].data_ptr() if self.post[1] is not None else None,
+                 y.t.data_ptr(), _lib.dtype_code(self.dtype), x.N, x.H, x.W, self.cin, x.cstride, x.coff, self.cout, y.cstride, y.coff,
+                 int(bool(pool)), self.act, keep=(x.t, y.t, self.w) + tuple(self.pre) + tuple(t for t in self.post if t is not None))
+
+    def record_unfused(self, prog: Program, x: ActView, y: ActView, scratch: ActView) -> None:
+        """The two-launch form: scratch = relu(bn_pre(x)) (a view of x's size with Cin channels), then the conv on today's path."""
+        record_scale_shift_act(prog, x, scratch, self.pre[0], self.pre[1], "relu")
+        self.unfused.record(prog, scratch, y)
+
+
 def bottleneck_fusable(c1: "FusedConv", c2: "FusedConv", c3: "FusedConv", x: ActView, y: ActView) -> bool:
     """True when ft_bottleneck_fwd covers this identity-shortcut block (fp16, 256 -> 64 -> 64 -> 256, stride 1)."""
     if x.t.dtype != torch.float16 or x.rowpacked or (x.N, x.H, x.W, x.C) != (y.N, y.H, y.W, y.C):

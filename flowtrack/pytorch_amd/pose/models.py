@@ -22,13 +22,14 @@ from __future__ import annotations
 import functools
 import math
 import os
+import re
 from typing import List
 
 import torch
 import torch.nn as nn
 
 from ..engine import HipModule, Plan
-from ..hip_ops import (ActView, FlowtrackHipError, FusedConv, FusedLateralDeconv, Program, record_scale_shift_act, bottleneck_exit_fusable, new_act, new_rowpacked_act,
+from ..hip_ops import (ActView, FlowtrackHipError, FusedConv, FusedLateralDeconv, PreactConv1x1, Program, record_scale_shift_act, bottleneck_exit_fusable, new_act, new_rowpacked_act,
                        record_bottleneck_exit, record_maxpool, record_pack_input, fold_scale_shift, record_upsample_ac, record_hourglass_down, record_hourglass_up)
 from ..params import ActMarker, BatchNormParams, ConvParams, ConvTransposeParams
 from ..resnet import BLOCKS, Bottleneck, record_block
@@ -821,7 +822,7 @@ class FpnResnet(PoseResnet):
         B, mk = cur.N, dict(dtype=dtype, device=device)
         feats = self.latlayer1.cout
         p = new_act(B, cur.H, cur.W, feats, dtype, device)
-        self.fused("latlayer1", self.latlayer1.weight, act=None, **mk).record(prog, cur, p)
+        self._record_p5(prog, cur, p, dtype, device)
         stages["p5"] = p
         for j, stage in ((1, "layer3"), (2, "layer2"), (3, "layer1")):
             lat, top, c = getattr(self, f"latlayer{j + 1}"), getattr(self, f"toplayer{j}"), stages[stage]
@@ -843,6 +844,204 @@ class FpnResnet(PoseResnet):
         heatmaps = torch.empty((B, self.num_classes, p.H, p.W), dtype=torch.float32, device=device)
         self.fused("heatmap.2", self.heatmap[2].weight, bias=self.heatmap[2].bias, act=None, **mk).record(prog, p, heatmaps)
         return heatmaps
+
+
+    def _record_p5(self, prog, cur: ActView, p: ActView, dtype, device) -> None:
+        """p5 = latlayer1(c5) from the trunk's last map `cur` (here c5 itself)."""
+        self.fused("latlayer1", self.latlayer1.weight, act=None, dtype=dtype, device=device).record(prog, cur, p)
+
+
+#: depth -> (num_init_features, growth_rate, block_config) (densenet.py:150-153)
+densenet_dict = {121: (64, 32, [6, 12, 24, 16]), 169: (64, 32, [6, 12, 32, 32]), 201: (64, 32, [6, 12, 48, 32]), 161: (96, 48, [6, 12, 36, 24])}
+
+
+class DenseLayer(nn.Module):
+    """Parameter layout of _DenseLayer (densenet.py:19-30): norm1 -> relu1 -> conv1 (1x1 to bn_size * growth) -> norm2 -> relu2 -> conv2
+    (3x3 to growth); its output is concatenated behind its input."""
+
+    def __init__(self, cin: int, growth: int, bn_size: int):
+        super().__init__()
+        self.norm1, self.relu1 = BatchNormParams(cin), ActMarker("relu")
+        self.conv1 = ConvParams(cin, bn_size * growth, 1, bias=False)
+        self.norm2, self.relu2 = BatchNormParams(bn_size * growth), ActMarker("relu")
+        self.conv2 = ConvParams(bn_size * growth, growth, 3, padding=1, bias=False)
+
+
+class DenseBlock(nn.Module):
+    """_DenseBlock (densenet.py:39-44): denselayer1 .. denselayerN, layer i on cin + (i - 1) growth channels."""
+
+    def __init__(self, num_layers: int, cin: int, growth: int, bn_size: int):
+        super().__init__()
+        for i in range(num_layers):
+            self.add_module(f"denselayer{i + 1}", DenseLayer(cin + i * growth, growth, bn_size))
+
+    def layers(self):
+        return list(self.children())
+
+
+class Transition(nn.Module):
+    """_Transition (densenet.py:47-54): norm -> relu -> conv (1x1, halves the channels) -> AvgPool2d(2, 2)."""
+
+    def __init__(self, cin: int, cout: int):
+        super().__init__()
+        self.norm, self.relu = BatchNormParams(cin), ActMarker("relu")
+        self.conv = ConvParams(cin, cout, 1, bias=False)
+        self.pool = ActMarker("avgpool2x2s2")
+
+
+class FpnDensenet(FpnResnet):
+    """DenseNet-BC trunk + the FPN head of FpnResnet (pose_fpn.py:106-151, densenet.py:57-108).  Of PoseResnet it keeps everything
+    behind the network itself (the plan cache, forward / replay, the flip plan, the key points inside the plan), of FpnResnet the
+    head; the parameters and the trunk's launch list (_record_net) are its own, and none of the ResNet trunk's switches applies.
+
+    A dense block is ONE NHWC buffer [B, H, W, inplanes + L * growth]: every layer reads the channel window [0, cin) and writes its
+    `growth` new channels into the window behind it, so the reference's torch.cat never runs.  A dense layer is two launches:
+        t = relu(norm2(conv1(relu(norm1(block[:cin])))))      ft_preact_conv1x1_fwd: norm1 + ReLU on the GEMM's input operand (norm1
+                                                               belongs to the layer that reads the concat: no producer can fold it)
+        block[cin : cin + growth] = conv2(t)                   the 3x3 conv of today's path
+    The first is recorded in two forms, the first-call benchmark keeps one per shape (`dense_layer_form` pins one):
+      "preact"        the one launch above;
+      "affine+igemm"  ft_scale_shift_act_nhwc_fwd writes relu(norm1(block[:cin])), ft_conv2d_fwd reads it.
+    A transition is one ft_preact_conv1x1_fwd launch with pool = 1 (the 2x2 average commutes with the 1x1 conv, so it runs on the
+    GEMM's input and the GEMM has a quarter of the pixels) into channels [0, inplanes / 2) of the next block's buffer; p5 =
+    latlayer1(relu(norm5(block4))) is one more, so c5 is never written.  latlayer2..4 read the raw block buffers c4, c3, c2."""
+    #: None: both forms of a dense layer's first launch are recorded and the first-call benchmark keeps one per shape; "preact" /
+    #: "affine+igemm" records that form only (dev, tests; FT_DENSE_LAYER in the environment)
+    dense_layer_form = os.environ.get("FT_DENSE_LAYER") or None
+    LAYER_FORMS = ("preact", "affine+igemm")
+    bn_size = 4
+
+    def __init__(self, num_init_features: int, growth_rate: int, block_config, num_classes: int):
+        HipModule.__init__(self)        # (not PoseResnet's: that one builds the ResNet trunk)
+        self.num_classes, self.growth_rate, self.block_config = num_classes, growth_rate, list(block_config)
+        self.conv0 = ConvParams(3, num_init_features, 7, stride=2, padding=3, bias=False)
+        self.norm0 = BatchNormParams(num_init_features)
+        self.relu0 = ActMarker("relu")
+        self.pool0 = ActMarker("maxpool3x3s2")
+        self.inplanes, self.planes = num_init_features, []
+        for i, n in enumerate(self.block_config):
+            setattr(self, f"denseblock{i + 1}", DenseBlock(n, self.inplanes, growth_rate, self.bn_size))
+            self.inplanes += n * growth_rate
+            self.planes.append(self.inplanes)
+            if i != len(self.block_config) - 1:
+                setattr(self, f"transition{i + 1}", Transition(self.inplanes, self.inplanes // 2))
+                self.inplanes //= 2
+        self.norm5 = BatchNormParams(self.inplanes)
+        feats = 256
+        for i in range(4):                                              # lateral layers (pose_fpn.py:113-116): latlayer1 reads c5
+            setattr(self, f"latlayer{i + 1}", ConvParams(self.planes[3 - i], feats, 1, bias=False))
+        for j in (1, 2, 3):
+            setattr(self, f"toplayer{j}", _bn_relu_conv(feats, feats, 3, padding=1, bias=False))
+        self.heatmap = _bn_relu_conv(feats, num_classes, 1)
+
+    # -- initialisation / loading (densenet.py:122-148) -------------------------------------------
+    _OLD_KEY = re.compile(r"^(.*denselayer\d+\.(?:norm|relu|conv))\.((?:[12])\.(?:weight|bias|running_mean|running_var))$")
+
+    @classmethod
+    def rewrite_checkpoint_keys(cls, state_dict: dict) -> dict:
+        """torchvision's DenseNet checkpoints under this model's names: `features.` stripped, `norm.1` -> `norm1` and likewise
+        (densenet.py:126-139)."""
+        out = {}
+        for key, v in state_dict.items():
+            new_key = re.sub(r"^features\.", "", key)
+            m = cls._OLD_KEY.match(new_key)
+            if m:
+                new_key = m.group(1) + m.group(2)
+            out[new_key] = v
+        return out
+
+    def init_weights(self, pretrained: str = "") -> None:
+        if os.path.isfile(pretrained):
+            print("=> loading pretrained model {}".format(pretrained))
+            self.load_state_dict(self.rewrite_checkpoint_keys(torch.load(pretrained, map_location="cpu")), strict=False)
+            return
+        for m in self.modules():
+            if isinstance(m, ConvParams):
+                nn.init.kaiming_normal_(m.weight)
+            elif isinstance(m, BatchNormParams):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+        self._invalidate()
+
+    def _check_input_size(self, H: int, W: int) -> None:
+        if H % 32 or W % 32 or H < 64 or W < 64:
+            raise FlowtrackHipError(f"input {H}x{W}: height and width must be multiples of 32 and at least 64")
+
+    # -- the launch list ----------------------------------------------------------------------------
+    def _preact(self, label: str, weight, pre_bn, post_bn, act, dtype, device) -> PreactConv1x1:
+        key = (label, dtype, str(device))
+        layer = self._layers.get(key)
+        if layer is None:
+            layer = self._layers[key] = PreactConv1x1(weight, pre_bn.as_dict(), post_bn=post_bn.as_dict() if post_bn is not None else None,
+                                                      act=act, dtype=dtype, device=device, label=label)
+        return layer
+
+    def _record_p5(self, prog, cur: ActView, p: ActView, dtype, device) -> None:
+        """p5 = latlayer1(relu(norm5(block4))): norm5 + ReLU on the input operand, the activated map c5 is never written."""
+        self._preact("norm5+latlayer1", self.latlayer1.weight, self.norm5, None, None, dtype, device).record(prog, cur, p)
+
+    def _record_net(self, prog, x_static, dtype, device):
+        form = self.dense_layer_form
+        if form is not None and form not in self.LAYER_FORMS:
+            raise FlowtrackHipError(f"dense_layer_form {form!r}: None or one of {self.LAYER_FORMS}")
+        B, _, H, W = x_static.shape
+        mk = dict(dtype=dtype, device=device)
+        growth, c0 = self.growth_rate, self.conv0.cout
+        h, w = H // 4, W // 4
+        buf = new_act(B, h, w, self.planes[0], dtype, device)
+        stem_out = ActView(buf.t, c0, 0)
+        # conv0 + norm0 + relu0 + pool0 into channels [0, c0) of block 1's buffer; fp16: one launch, as PoseResnet's stem
+        pool_in_stem = self.fuse_stem_pool and dtype == torch.float16
+        planar_in = pool_in_stem and self.fuse_stem_pack
+        a_in = new_rowpacked_act(B, H, W, 3, 5 if pool_in_stem else 3, dtype, "meta" if planar_in else device)
+        if not planar_in:
+            record_pack_input(prog, x_static, a_in)
+        stem = self.fused("conv0" + ("+pool0" if pool_in_stem else ""), self.conv0.weight, stride=2, pad=3, bn=self.norm0.as_dict(), act="relu", **mk)
+        if pool_in_stem:
+            stem.record(prog, a_in, stem_out, pool=True, x_nchw=x_static if planar_in else None)
+        else:
+            a1 = new_act(B, H // 2, W // 2, c0, dtype, device)
+            stem.record(prog, a_in, a1)
+            pooled = new_act(B, h, w, c0, dtype, device)
+            record_maxpool(prog, a1, pooled)
+            # (the max-pool kernel writes dense buffers: its map goes into the block's window as x * 1 + 0, exactly)
+            key = ("pool0.copy", dtype, str(device))
+            ident = self._layers.get(key)
+            if ident is None:
+                ident = self._layers[key] = (torch.ones(c0, dtype=torch.float32, device=device), torch.zeros(c0, dtype=torch.float32, device=device))
+            record_scale_shift_act(prog, pooled, stem_out, ident[0], ident[1], None)
+        stages = _Stages({"stem": stem_out})
+        cin = c0
+        for bi, nlayers in enumerate(self.block_config, start=1):
+            block = getattr(self, f"denseblock{bi}")
+            t = new_act(B, h, w, self.bn_size * growth, dtype, device)             # conv1's output: read by the next launch only
+            scratch = new_act(B, h, w, self.planes[bi - 1], dtype, device) if form != "preact" else None
+            for li, layer in enumerate(block.layers(), start=1):
+                name = f"denseblock{bi}.denselayer{li}"
+                pc = self._preact(name + ".norm1+conv1+norm2", layer.conv1.weight, layer.norm1, layer.norm2, "relu", dtype, device)
+                c2 = self.fused(name + ".conv2", layer.conv2.weight, pad=1, act=None, **mk)
+                xin = ActView(buf.t, cin, 0)
+                forms = {"preact": lambda pc=pc, xin=xin: pc.record(prog, xin, t),
+                         "affine+igemm": lambda pc=pc, xin=xin: pc.record_unfused(prog, xin, t, ActView(scratch.t, xin.C, 0))}
+                if form is not None:
+                    forms[form]()
+                else:
+                    prog.begin_choice(f"dense_layer|{B},{h},{w},{cin},{t.C},{buf.cstride},{dtype}")
+                    for fname in self.LAYER_FORMS:
+                        prog.option(fname)
+                        forms[fname]()
+                    prog.end_choice()
+                c2.record(prog, t, ActView(buf.t, growth, cin))
+                cin += growth
+            stages[f"layer{bi}"] = buf
+            if bi != len(self.block_config):
+                tr = getattr(self, f"transition{bi}")
+                h, w = h // 2, w // 2
+                nxt = new_act(B, h, w, self.planes[bi], dtype, device)
+                self._preact(f"transition{bi}", tr.conv.weight, tr.norm, None, None, dtype, device).record(prog, buf, ActView(nxt.t, cin // 2, 0), pool=True)
+                buf, cin = nxt, cin // 2
+        heatmaps = self._record_head(prog, stages, buf, dtype, device)
+        return stages, heatmaps
 
 
 def _bn_relu_deconv(cin: int, cout: int) -> nn.Sequential:
@@ -1200,11 +1399,33 @@ def deconv(backbone: str, num_classes: int, pretrained: bool) -> DeconvResnet:
 
 def fpn(backbone: str, num_classes: int, pretrained: bool) -> FpnResnet:
     """Factory with the reference's signature (pose_fpn.py:171-184) for backbone 'resnet50' | 'resnet101' | 'resnet152';
-    pretrained=True loads data/pretrained/<backbone>.pth if present.  The reference's DenseNet trunks are not on the HIP path."""
+    pretrained=True loads data/pretrained/<backbone>.pth if present.  The reference's DenseNet trunks: fpn_densenet."""
     depth = backbone[len("resnet"):] if backbone.startswith("resnet") else ""
     if not depth.isdigit() or int(depth) not in resnet_dict:
-        raise FlowtrackHipError(f"backbone '{backbone}': the FPN head is on the HIP path for resnet50 / resnet101 / resnet152 only")
+        raise FlowtrackHipError(f"backbone '{backbone}': the FPN head is on the HIP path for resnet50 / resnet101 / resnet152 only" +
+                                ("; DenseNet trunks: models.fpn_densenet" if backbone.startswith("densenet") else ""))
     model = FpnResnet(resnet_dict[int(depth)], num_classes=num_classes)
+    path = os.path.join("data", "pretrained", "{}.pth".format(backbone)) if pretrained else ""
+    model.init_net(path)
+    return model
+
+
+#: DenseNet trunks of fpn_densenet.  densenet161 (growth 48) is not among them: its channel windows (144, 240, ...) are no multiples
+#: of 32, the K-step of the channel-aligned 3x3 conv kernel that every other trunk's windows run on, and that path has not been
+#: validated on such windows
+FPN_DENSENETS = ("densenet121", "densenet169", "densenet201")
+
+
+def fpn_densenet(backbone: str, num_classes: int, pretrained: bool) -> FpnDensenet:
+    """The reference's models.fpn on its DenseNet trunks (pose_fpn.py:106-184) for backbone 'densenet121' | 'densenet169' |
+    'densenet201'; pretrained=True loads data/pretrained/<backbone>.pth if present (a torchvision checkpoint: its keys are rewritten
+    as densenet.py:126-139 rewrites them)."""
+    if backbone == "densenet161":
+        raise FlowtrackHipError("backbone 'densenet161': growth rate 48 gives channel windows (144, 240, ...) that are no multiples of 32; the 3x3 "
+                                f"conv kernel of the HIP path has not been validated on them.  Accepted: {' / '.join(FPN_DENSENETS)}")
+    if backbone not in FPN_DENSENETS:
+        raise FlowtrackHipError(f"backbone '{backbone}': fpn_densenet takes {' / '.join(FPN_DENSENETS)}")
+    model = FpnDensenet(*densenet_dict[int(backbone[len("densenet"):])], num_classes=num_classes)
     path = os.path.join("data", "pretrained", "{}.pth".format(backbone)) if pretrained else ""
     model.init_net(path)
     return model

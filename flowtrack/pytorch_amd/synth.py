@@ -131,6 +131,37 @@ def fill_pose_state_dict(sd: Dict[str, torch.Tensor], seed: int) -> Dict[str, to
     return out
 
 
+#: conv gains of fill_densenet_state_dict (He's 2.0 in fill_pose_state_dict): every conv but the last, and the heat-map conv
+DENSENET_GAIN, DENSENET_HEATMAP_GAIN = 1.0, 9.0
+
+
+def fill_densenet_state_dict(sd: Dict[str, torch.Tensor], seed: int) -> Dict[str, torch.Tensor]:
+    """Weights for an `fpn_densenet('densenetNNN', K)` state_dict: fill_pose_state_dict's recipe with every conv at gain
+    DENSENET_GAIN and the heat-map conv at DENSENET_HEATMAP_GAIN.  A dense block has no BatchNorm behind a layer's last conv and concatenates instead of adding, so with He gains
+    the FPN head's four lateral convs sum over up to 1024 un-normalised channels and the heat maps span about -53 .. 37: too wide
+    for an absolute 1e-3 bound in fp32.  Gain 1 everywhere gives maps within +-3 whose top-1 / top-2 margins are too small for an
+    exact arg-max test; the heat-map conv's gain stretches them to about +-10 (tests/golden/make_fpn_densenet_golden.py states the conditions this fill meets)."""
+    out = {}
+    for k, v in sd.items():
+        shape = tuple(v.shape)
+        if k.endswith("num_batches_tracked"):
+            out[k] = torch.tensor(0, dtype=torch.long)
+        elif k.endswith("running_mean"):
+            out[k] = normal(seed, k, shape, std=0.1)
+        elif k.endswith("running_var"):
+            out[k] = uniform(seed, k, shape, 0.5, 1.5)
+        elif v.dim() == 4:
+            gain = DENSENET_HEATMAP_GAIN if k.startswith("heatmap") else DENSENET_GAIN
+            out[k] = normal(seed, k, shape, std=float(np.sqrt(gain / _fan_in(k, shape, False))))
+        elif k.endswith(".weight"):  # BN gamma
+            out[k] = uniform(seed, k, shape, 0.5, 1.5)
+        elif k.endswith(".bias"):
+            out[k] = normal(seed, k, shape, std=0.1)
+        else:
+            raise KeyError(k)
+    return out
+
+
 #: gain of the hourglass convs that write into the residual stream (fill_hg_state_dict)
 HG_STREAM_GAIN = 0.03
 

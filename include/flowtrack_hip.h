@@ -529,6 +529,32 @@ int ft_scale_shift_act_nhwc_fwd(const void* x, void* y, int dtype, long long npi
                                 int y_cstride, int y_coff, const float* scale, const float* shift, int act, float slope,
                                 ft_stream_t stream);
 
+/* ---- DenseNet trunks of the FPN pose model: the pre-activation 1x1 conv ----
+ * Replaces `norm1 -> relu1 -> conv1 (-> norm2 -> relu2)` of a dense layer and `norm -> relu -> conv -> AvgPool2d(2, 2)` of a
+ * transition (lib/pose/models/densenet.py:19-36, 47-54).  norm1 belongs to the layer that READS the concatenated input, so it folds
+ * into no producer's epilogue; here it is applied to the GEMM's input operand on its way from memory.
+ *   x [N, H, W, x_cstride] NHWC, FT_F16 or FT_F32; channels [x_coff, x_coff + Cin) of a pixel are read, NO other channel is (a
+ *     channel at or above Cin may hold anything, a NaN included: it reaches no operand)
+ *   pool = 0:  a[p][c] = dtype(relu(fma(pre_scale[c], float(x[p][c]), pre_shift[c])))      ft_scale_shift_act_nhwc_fwd's bits
+ *   pool = 1:  a[p][c] = dtype(0.25f * ((r00 + r01) + (r10 + r11)))   r_ij = the four fp32 values relu(fma(...)) of the 2x2 window
+ *              of output pixel p, unrounded; fp32 adds in this order, one rounding to dtype.  The output map is [N, H/2, W/2]
+ *              (floor: an odd last row or column takes no part), which equals avg_pool(conv(.)) because the conv is linear
+ *   acc[p][n] = sum_c a[p][c] * w[n][c]      fp32 accumulation (fp16: MFMA, exact products; fp32: one fma per product, ascending c)
+ *   y[p][y_coff + n] = dtype(act(fma(post_scale[n], acc, post_shift[n])))      post_scale = post_shift = NULL: act(acc)
+ * act is FT_ACT_NONE or FT_ACT_RELU.  Channels outside [y_coff, y_coff + Cout) of an output pixel stay untouched.  x and y must not
+ * share bytes a launch both reads and writes (disjoint channel windows of one buffer are fine).
+ * w: the packed [Cout, Cin] weights.  FT_F32: fp32 [Cout][Cin] row-major.  FT_F16: fp16 [Cout/32][ceil(Cin/64)][4][64][8] —
+ * element (g, c, s, lane, e) = W[32 g + (lane & 31)][64 c + 32 (lane >> 5) + 8 s + e], zero where that channel is >= Cin (the
+ * order in which mfma_f32_32x32x16_f16 takes its operand).  pre_scale, pre_shift: fp32 [Cin]; post_scale, post_shift: fp32 [Cout].
+ * FT_ERR_UNSUPPORTED: Cout % 32 != 0; Cin, an offset or a stride that is no multiple of the 16-byte channel group (8 fp16 / 4 fp32
+ * channels); pool = 1 with H < 2 or W < 2 (an empty output); 2^31 or more pixels.  FT_ERR_INVALID_ARG: a NULL pointer (only the
+ * post_* pair may be NULL, together), a size <= 0, a negative offset, a stride smaller than offset + C, an unknown dtype, act or
+ * pool, a pointer that is not 16-byte aligned.  A refused call launches nothing. */
+int ft_preact_conv1x1_fwd(const void* x, const void* w, const float* pre_scale, const float* pre_shift,
+                          const float* post_scale, const float* post_shift, void* y, int dtype, int N, int H, int W, int Cin,
+                          int x_cstride, int x_coff, int Cout, int y_cstride, int y_coff, int pool, int act,
+                          ft_stream_t stream);
+
 /* ---- Stacked hourglass (lib/pose/models/hourglass.py:110-121): the two seams of a level that are not convs ----
  * Every block of the hourglass is pre-activation: it reads its raw input (the shortcut) and relu(bn(input)).  At the two
  * memory-bound seams of a level the activated copies are written while the map is in registers.  Both kernels: NHWC, FT_F16 or

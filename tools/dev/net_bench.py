@@ -1,6 +1,6 @@
 """Per-launch timing of a whole plan (dev tool): python tools/dev/net_bench.py FlowNet2C 16 384 512 fp16
 (pose nets: resnet50 = ResNet-50 + deconv head, fpn_resnet50 = ResNet-50 + FPN head, pose_resnet50 = ResNet-50 + lateral-deconv head,
-hg8 = 8 stacked hourglasses; NB_FUSE_SEAMS=0 records the hourglass's level seams unfused)"""
+fpn_densenet121 = DenseNet-121 + FPN head, hg8 = 8 stacked hourglasses; NB_FUSE_SEAMS=0 records the hourglass's level seams unfused)"""
 import sys, os, types
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -68,6 +68,12 @@ if name.startswith("hg"):        # hg8 = models.hg(17, num_stacks=8)
     m = models.hg(17, int(name[2:]))
     m.fuse_seams = os.environ.get("NB_FUSE_SEAMS", "1") != "0"
     m.load_state_dict(synth.fill_hg_state_dict(m.state_dict(), 1))
+    x = synth.pose_crops(1, B, H, W)
+elif name.startswith("fpn_densenet"):          # fpn_densenet121: the FPN head on a DenseNet trunk; NB_DENSE_LAYER pins a dense-layer form
+    from flowtrack.pytorch_amd.pose import models
+    m = models.fpn_densenet(name[4:], 17, False)
+    m.dense_layer_form = os.environ.get("NB_DENSE_LAYER") or m.dense_layer_form
+    m.load_state_dict(synth.fill_densenet_state_dict(m.state_dict(), 1))
     x = synth.pose_crops(1, B, H, W)
 elif name.startswith(("resnet", "fpn_resnet", "pose_resnet")):      # resnet50 = the deconv head, fpn_resnet50 = the FPN head, pose_resnet50 = the lateral-deconv head
     from flowtrack.pytorch_amd.pose import models

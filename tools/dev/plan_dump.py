@@ -4,7 +4,7 @@ record the same plan exactly when their dumps are byte-equal: a device address (
 its first appearance in the dump, so the text does not depend on the allocator and still pins which launch reads which buffer.
 
     python tools/dev/plan_dump.py SPEC [SPEC ...]         SPEC = name:B:H:W:dtype[:variant]
-    resnet50:64:256:192:fp16          models.deconv (fpn_resnet50 / pose_resnet50: the FPN / lateral-deconv head; hg2: 2 hourglasses)
+    resnet50:64:256:192:fp16          models.deconv (fpn_resnet50 / pose_resnet50: the FPN / lateral-deconv head; fpn_densenet121; hg2: 2 hourglasses)
     resnet50:64:256:192:fp16:flip     the flip plan of the shape
     frcnn_resnet50:1:600:901:fp16     the detector's trunk + RPN plan of one H x W blob and its region-head plan at 300 rows
     frcnn_resnet50:1:600:901:fp16:force    ... with fuse_bottleneck = "force"
@@ -70,6 +70,11 @@ def dump(spec):
         from flowtrack.pytorch_amd.pose import models
         m = models.hg(17, int(name[2:]))
         m.load_state_dict(synth.fill_hg_state_dict(m.state_dict(), 1))
+    elif name.startswith("fpn_densenet"):          # fpn_densenet121: the FPN head on a DenseNet trunk; NB_DENSE_LAYER pins a dense-layer form
+        from flowtrack.pytorch_amd.pose import models
+        m = models.fpn_densenet(name[4:], 17, False)
+        m.dense_layer_form = os.environ.get("NB_DENSE_LAYER") or m.dense_layer_form
+        m.load_state_dict(synth.fill_densenet_state_dict(m.state_dict(), 1))
     elif name.startswith(("resnet", "fpn_resnet", "pose_resnet")):
         from flowtrack.pytorch_amd.pose import models
         m = models.fpn(name[4:], 17, False) if name.startswith("fpn_") else models.pose(name[5:], 17, False) if name.startswith("pose_") else models.deconv(name, 17, False)

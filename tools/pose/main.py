@@ -150,13 +150,15 @@ def main(**kwargs):
     num_classes = num_joints[opt.dataset] + (1 if opt.with_bg else 0)
     print("==> creating model '{}', backbone = {}".format(opt.model, opt.backbone))
     if opt.model not in ('deconv', 'fpn', 'hg'):
-        raise ValueError("only model='deconv' (ResNet + 3-deconv head), model='fpn' (ResNet + FPN head) and model='hg' (8 stacked "
+        raise ValueError("only model='deconv' (ResNet + 3-deconv head), model='fpn' (ResNet / DenseNet + FPN head) and model='hg' (8 stacked "
                          "hourglasses) are on the HIP path; got '{}'".format(opt.model))
     if opt.model == 'hg':       # the reference's main.py:69-72: no backbone, 8 stacks
         model = models.hg(num_classes=num_classes, num_stacks=8)
         opt.model_name = 'hg'
     else:
-        model = getattr(models, opt.model)(opt.backbone, num_classes=num_classes, pretrained=opt.pretrained)
+        # (the reference's models.fpn builds FPN_Densenet for a densenet* backbone, its own default: here that model is fpn_densenet)
+        factory = models.fpn_densenet if opt.model == 'fpn' and str(opt.backbone).startswith('densenet') else getattr(models, opt.model)
+        model = factory(opt.backbone, num_classes=num_classes, pretrained=opt.pretrained)
         opt.model_name = '{}_{}'.format(opt.model, opt.backbone)
     if not opt.use_gpu:
         raise ValueError('the HIP path needs use_gpu=True (CPU reference results: oracle/)')

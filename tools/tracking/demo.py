@@ -73,11 +73,16 @@ def synthetic_clip(n_frames, H=384, W=512, n_people=5, seed=0):
 
 
 def build_nets(args, device):
-    pose = getattr(pose_models, getattr(args, "pose_head", "deconv"))("resnet%d" % args.pose_backbone, num_classes=getattr(args, "pose_classes", 17), pretrained=False)
+    head, backbone = getattr(args, "pose_head", "deconv"), str(args.pose_backbone)
+    dense = backbone.startswith("densenet")         # --pose_backbone densenet121: the FPN head's DenseNet trunk (models.fpn_densenet)
+    if dense and head != "fpn":
+        raise SystemExit("--pose_backbone %s needs --pose_head fpn (the only head the reference runs on DenseNet trunks)" % backbone)
+    factory = pose_models.fpn_densenet if dense else getattr(pose_models, head)
+    pose = factory(backbone if dense else "resnet%d" % int(backbone), num_classes=getattr(args, "pose_classes", 17), pretrained=False)
     if args.pose_model:
         pose.load_state_dict(torch.load(args.pose_model, map_location="cpu")["state_dict"])
     else:
-        pose.load_state_dict(synth.fill_pose_state_dict(pose.state_dict(), 11))
+        pose.load_state_dict((synth.fill_densenet_state_dict if dense else synth.fill_pose_state_dict)(pose.state_dict(), 11))
     fargs = types.SimpleNamespace(rgb_max=255.0, fp16=args.fp16)
     flow = getattr(flow_models, args.flow_net)(fargs)
     if args.flow_model:
@@ -452,7 +457,7 @@ def build_parser():
     ap.add_argument("--people", type=int, default=5)
     ap.add_argument("--height", type=int, default=384, help="frame height of the synthetic clip")
     ap.add_argument("--width", type=int, default=512, help="frame width of the synthetic clip")
-    ap.add_argument("--pose_backbone", default=50, type=int, help="50, 101, 152")
+    ap.add_argument("--pose_backbone", default="50", help="50, 101, 152 (ResNet depth), or with --pose_head fpn: densenet121, densenet169, densenet201")
     ap.add_argument("--pose_head", default="deconv", choices=("deconv", "fpn", "pose"),
                     help="pose model factory (the reference's opt.model): ResNet + 3-deconv head, ResNet + FPN head, or ResNet + "
                          "lateral-deconv head")
