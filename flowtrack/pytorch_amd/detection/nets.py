@@ -488,28 +488,12 @@ class vgg16(_FasterRCNN):
     def _record_fc(self, prog, label: str, weight: torch.Tensor, bias: torch.Tensor, x: ActView, y: ActView, device, dtype) -> None:
         """One classifier layer + ReLU, [rows,1,1,K] -> [rows,1,1,N], in the forms fc_form allows."""
         rows, (n, k) = x.N, weight.shape
-        forms = ("igemm",) if dtype != torch.float16 else (self.fc_form,) if self.fc_form else \
-            (self.FC_FIRST, "igemm" if self.FC_FIRST == "fc" else "fc")
-        if "fc" in forms and not FusedFC.supported(rows, k, n, dtype, x, y):
+        only = "igemm" if dtype != torch.float16 else self.fc_form or None
+        if only != "igemm" and not FusedFC.supported(rows, k, n, dtype, x, y):
             raise FlowtrackHipError(f"{label}: ft_fc_fwd does not take {rows} rows of [{n}, {k}]")
-
-        def record(form):
-            if form == "fc":
-                key = (label + "|fc", dtype, str(device))
-                layer = self._layers.get(key)
-                if layer is None:
-                    layer = self._layers[key] = FusedFC(weight, bias, device=device, act="relu", label=label)
-                layer.record(prog, x, y)
-            else:
-                self.fused(label, weight[:, :, None, None], bias=bias, act="relu", dtype=dtype, device=device).record(prog, x, y)
-
-        if len(forms) == 1:
-            return record(forms[0])
-        prog.begin_choice(f"fc|{rows}x{k}x{n}")
-        for form in forms:
-            prog.option(form)
-            record(form)
-        prog.end_choice()
+        forms = {"fc": lambda: self._cached(label + "|fc", dtype, device, lambda: FusedFC(weight, bias, device=device, act="relu", label=label)).record(prog, x, y),
+                 "igemm": lambda: self.fused(label, weight[:, :, None, None], bias=bias, act="relu", dtype=dtype, device=device).record(prog, x, y)}
+        prog.choice(f"fc|{rows}x{k}x{n}", {form: forms[form] for form in sorted(forms, key=lambda f: f != self.FC_FIRST)}, only=only)
 
     def _record_tail(self, prog, plan: Plan, feat: ActView, rows: int, device, dtype) -> ActView:
         """nets/vgg16.py:46-50: pool5.view(R, -1) -> classifier (Linear, ReLU, Dropout, Linear, ReLU, Dropout), in eval."""

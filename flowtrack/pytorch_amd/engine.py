@@ -50,26 +50,25 @@ class HipModule(nn.Module):
         Needed only after edits the version check of _check_fingerprint() cannot see (writes through `p.data`)."""
         self._invalidate()
 
-    def fused(self, label: str, weight, *, dtype, device, **kw):
-        """FusedConv for `label`, built once per (dtype, device) and shared by every plan (input shape) of this
-        module — weight packing / BN folding is per layer, not per plan."""
-        from .hip_ops import FusedConv
+    def _cached(self, label: str, dtype, device, make):
+        """What make() returns — a packed layer, a folded BatchNorm table — built once per (label, dtype, device) and shared by every
+        plan (input shape) of this module: weight packing / BN folding is per layer, not per plan."""
         key = (label, dtype, str(device))
         layer = self._layers.get(key)
         if layer is None:
-            layer = self._layers[key] = FusedConv(weight, dtype=dtype, device=device, label=label, **kw)
+            layer = self._layers[key] = make()
         return layer
+
+    def fused(self, label: str, weight, *, dtype, device, **kw):
+        """FusedConv for `label`, cached as _cached() caches."""
+        return self._cached(label, dtype, device, lambda: hip_ops.FusedConv(weight, dtype=dtype, device=device, label=label, **kw))
 
     def fused_shortcut(self, label: str, blk, stride_d: int, *, dtype, device, key_suffix: str = ""):
         """FusedShortcutConv of `blk` (a resnet.Bottleneck with a projection shortcut read at stride `stride_d`), cached as fused()
         caches; `key_suffix` tells apart two layers of one label (the stage-exit form reads its shortcut operand at stride 1)."""
-        from .hip_ops import FusedShortcutConv
-        key = (label + key_suffix, dtype, str(device))
-        layer = self._layers.get(key)
-        if layer is None:
-            layer = self._layers[key] = FusedShortcutConv(blk.conv3.weight, blk.bn3.as_dict(), blk.downsample[0].weight,
-                                                          blk.downsample[1].as_dict(), stride_d, dtype=dtype, device=device, act="relu", label=label)
-        return layer
+        return self._cached(label + key_suffix, dtype, device, lambda: hip_ops.FusedShortcutConv(
+            blk.conv3.weight, blk.bn3.as_dict(), blk.downsample[0].weight, blk.downsample[1].as_dict(), stride_d, dtype=dtype, device=device,
+            act="relu", label=label))
 
     def _apply(self, fn, *a, **k):
         out = super()._apply(fn, *a, **k)

@@ -182,6 +182,18 @@ class Program:
         self.calls.append(("__endchoice__", ()))
         self.lanes.append(0)
 
+    def choice(self, key: str, forms, only: Optional[str] = None) -> None:
+        """Record `forms` (form name -> thunk that records it, in the recorder's order of preference) as one choice under `key`;
+        `only` names the one form to record instead, with no markers (a pinned form, or one that alone applies)."""
+        if only is not None:
+            forms[only]()
+            return
+        self.begin_choice(key)
+        for name, form in forms.items():
+            self.option(name)
+            form()
+        self.end_choice()
+
     def _innermost_choices(self) -> list:
         """Unresolved choice groups that contain no other group: dicts {key, marks: [option starts..., end]}."""
         stack, out = [], []

@@ -345,6 +345,24 @@ def test_inapplicable_hints_fall_back(hip_lib, monkeypatch):
     assert outs[0][..., :1024].abs().max().item() > 0
 
 
+def test_program_choice_records_the_hand_written_markers(hip_lib):
+    """Program.choice(key, forms) = begin_choice(key), option(name) + the form for each form in order, end_choice(); with `only` it
+    records that form alone, with no markers.  Nothing is launched: the entries are recorded, never run."""
+    forms = {"one": lambda p: p.add("form_one", 1), "two": lambda p: (p.add("form_two", 2), p.add("form_two_b"))}
+    by_hand, by_choice, pinned = make_program(), make_program(), make_program()
+    by_hand.begin_choice("demo|1,2")
+    for name, form in forms.items():
+        by_hand.option(name)
+        form(by_hand)
+    by_hand.end_choice()
+    by_choice.choice("demo|1,2", {name: (lambda form=form: form(by_choice)) for name, form in forms.items()})
+    assert by_choice.calls == by_hand.calls and by_choice.lanes == by_hand.lanes
+    assert [c[0] for c in by_choice.calls] == ["__choice__", "__option__", "form_one", "__option__", "form_two", "form_two_b", "__endchoice__"]
+    assert [g["names"] for g in by_choice._innermost_choices()] == [["one", "two"]]
+    pinned.choice("demo|1,2", {name: (lambda form=form: form(pinned)) for name, form in forms.items()}, only="two")
+    assert pinned.calls == [("form_two", (2,)), ("form_two_b", ())]
+
+
 # ---- conv3 + projection shortcut as one K-concatenated GEMM (ft_conv_desc.x2_*, FusedShortcutConv) -----------
 SHORTCUT_CASES = [
     # (name, N, planes (conv3 input channels), Cin of the block input, H, W of the block input, stride of the shortcut)

@@ -6,6 +6,8 @@ its first appearance in the dump, so the text does not depend on the allocator a
     python tools/dev/plan_dump.py SPEC [SPEC ...]         SPEC = name:B:H:W:dtype[:variant]
     resnet50:64:256:192:fp16          models.deconv (fpn_resnet50 / pose_resnet50: the FPN / lateral-deconv head; fpn_densenet121; hg2: 2 hourglasses)
     resnet50:64:256:192:fp16:flip     the flip plan of the shape
+    resnet50:64:256:192:fp16:kp       a pose model's plan with keypoints_in_plan = True (its last launch writes the key-point rows)
+    resnet50:64:256:192:fp16:exact    ... and exact_in_plan = True (fp16: the exact-arg-max screen, gather and header copy behind it)
     frcnn_resnet50:1:600:901:fp16     the detector's trunk + RPN plan of one H x W blob and its region-head plan at 300 rows
     frcnn_resnet50:1:600:901:fp16:force    ... with fuse_bottleneck = "force"
     FlowNet2S:2:128:128:fp32          a flow model
@@ -85,9 +87,11 @@ def dump(spec):
         from flowtrack.pytorch_amd.flownet import models
         m = getattr(models, name)(types.SimpleNamespace(rgb_max=255.0, fp16=False))
         m.load_state_dict(synth.fill_flow_state_dict(m.state_dict(), 1))
+    if variant in ("kp", "exact"):                  # (pose models) the plan's tail as well: key points, and the exact-arg-max screen
+        m.keypoints_in_plan, m.exact_in_plan = True, variant == "exact"
     m = m.cuda().eval()
     m.compute_dtype = dtype
-    m.static_input(B, H, W)                         # builds the plan, runs nothing
+    m.static_input(B, H, W)                        # builds the plan, runs nothing
     (key, plan), = m._plans.items()
     out.prog(f"plan {[k for k in key if not isinstance(k, torch.device)]}", plan.prog)
 
