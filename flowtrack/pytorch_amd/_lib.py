@@ -49,7 +49,7 @@ class BottleneckDesc(ctypes.Structure):
 
     _fields_ = [("dtype", c_int), ("N", c_int), ("H", c_int), ("W", c_int), ("C", c_int), ("P", c_int),
                 ("x_cstride", c_int), ("x_coff", c_int), ("y_cstride", c_int), ("y_coff", c_int), ("head_only", c_int), ("projection", c_int),
-                ("stride", c_int), ("folded", c_int)]
+                ("stride", c_int), ("folded", c_int), ("wfrag", c_int)]
 
 
 class ConvGeometry(ctypes.Structure):
@@ -105,6 +105,8 @@ _PROTOTYPES = {
     "ft_bottleneck_supported": (c_int, [POINTER(BottleneckDesc)]),
     "ft_bottleneck_fwd": (c_int, [POINTER(BottleneckDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ft_bottleneck_flops": (c_double, [POINTER(BottleneckDesc)]),
+    "ft_bottleneck_frag_bytes": (ctypes.c_longlong, [POINTER(BottleneckDesc)]),
+    "ft_bottleneck_frag_pack": (c_int, [POINTER(BottleneckDesc), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ft_bottleneck_exit_supported": (c_int, [POINTER(BottleneckDesc), c_int, c_int, c_int, c_int]),
     "ft_bottleneck_exit_weight_bytes": (ctypes.c_longlong, [POINTER(BottleneckDesc), c_int]),
     "ft_bottleneck_exit_pack": (c_int, [POINTER(BottleneckDesc), c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),

@@ -21,10 +21,12 @@
 //            coalesced stores (one barrier per quarter, no wait on the stores).
 // 75 KiB of LDS -> two workgroups per CU.  The halo makes phase 1 do 1.4x the 1x1's MACs (0.9 GMAC of 13.7 per block at
 // batch 64): cheap next to 3 MB of HBM.
-// Measured (batch 64, 64x48): 134 us for the three launches -> 64 us.  Per patch 232 KB go L2 -> LDS (96 x, 136 weights)
-// and that delivery (~16 B/clk/CU, the same ceiling the conv kernels see) is what bounds it now, not HBM: tools/dev/
-// bnk_phases.py (phase timestamps) and the FT_BNK_DBG ablations in bnk_bench.py are how that was established; deeper
-// rings, 64- vs 128-byte rows, an L2 warm-up of the later chunks and staggering the co-resident workgroups changed nothing.
+// Measured (batch 64, 64x48): 134 us for the three launches -> 64 us.  The phases above describe the LDS-RING form (wfrag = 0): per
+// patch 232 KB go L2 -> LDS (96 x, 136 weights), every hand-over is a workgroup barrier (22 per patch).  Its weight traffic alone is
+// worth 6-11 us of a 55-73-us launch (FT_BNK_DBG=64: no weight loads; profiles/HISTORY.md, "fragment stream"); tools/dev/
+// bnk_phases.py (phase timestamps) and the FT_BNK_DBG ablations in bnk_bench.py are the instruments; deeper rings, 64- vs
+// 128-byte rows, an L2 warm-up of the later chunks and staggering the co-resident workgroups changed nothing.  The whole-block forms
+// now run the fragment-stream form (WFRAG below): the weights skip LDS, 12-13 barriers per patch.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -96,6 +98,14 @@ constexpr int kC = 256, kP = 64;                 // block width / planes this ke
 [[maybe_unused]] constexpr int kOffT1 = 0, kOffT2 = 49152, kOffOutA = 0, kOffOutB = 49152, kOffTab = 73728;
 constexpr int kLdsBytes = 76800;
 __device__ __forceinline__ constexpr int ring_slot(int i) { return i == 0 ? 65536 : 24576 + (i - 1) * 8192; }
+// The fragment stream of the WFRAG forms, in 1-KiB fragments (64 lanes x 16 bytes: lane -> weight row 32 * tile + lane % 32, eight
+// consecutive k from 16 * slice + 8 * (lane / 32)), in the order a wave reads them.  nch = 64-channel chunks of the block input:
+//   W1  [chunk nch][channel tile 2][K16 slice 4]
+//   W2  [tap 9][channel tile 2][K16 slice 4]
+//   W3  [quarter 4][channel tile 2][K16 slice 4]; projection form [quarter 4][channel tile 2][8]: slices 0-3 of W3', then 0-3 of Wd'
+__host__ __device__ constexpr int frag_w2(int nch) { return nch * 8; }
+__host__ __device__ constexpr int frag_w3(int nch) { return nch * 8 + 72; }
+__host__ __device__ constexpr int frag_count(int nch, bool proj) { return nch * 8 + 72 + (proj ? 64 : 32); }
 
 // NCH = 64-channel chunks of the block input (4: the 256-wide identity blocks, 1: the stage's entry block, 64 in).
 // FULL = false stops after phase 2 and writes t2 (the entry block's conv3 is K-concatenated with its projection shortcut
@@ -114,13 +124,31 @@ __device__ __forceinline__ constexpr int ring_slot(int i) { return i == 0 ? 6553
 // through buffer stores, which the compiler counts: no wait on a weight fragment also waits for stores.  t1 leaves from the
 // accumulator layout (a lane owns 16 consecutive channels, as in conv1x1_stream_kernel) and y is written whole, at its even pixels
 // only (compact [N, H/2, W/2, 256]: what the stride-2 shortcut reads) or not at all.  250 registers, 76 800 B of LDS, no scratch.
-template <int TW, int NCH, bool FULL, bool PROJ = false, bool EXIT = false>
+//
+// WFRAG = the weights come as ONE fragment-ordered stream (bnk_frag_pack_kernel, ft_bottleneck_desc.wfrag = 1; p.w1 is the stream,
+// p.w2 / p.w3 are not read) and go from L2 straight to registers, every wave load one contiguous 1 KiB in the A-operand layout of
+// mfma_f32_32x32x16_f16; both pixel groups of a channel tile load the same fragments (as bottleneck_stream_direct128_kernel):
+//   phase 1  the W1 K-slice of a chunk (4 fragments per wave) one chunk ahead in two register sets; the stages hold x only, so there
+//            are THREE of them (3 x 24 KiB): chunks 0..2 are in flight from the start and chunk 3 refills stage 0 — one refill
+//            barrier per patch instead of two, 72 KiB per workgroup in flight against HBM.
+//   phase 2  a tap's four fragments two taps ahead in three register sets; T1 is static in LDS, so the nine taps run with NO
+//            workgroup barrier between them and the T1 fragment reads of tap t + 1 are issued under tap t's MFMAs.
+//   phase 3  a W3 quarter's four fragments one quarter ahead (projection form: eight, W3' | Wd' — the shortcut weights stream with
+//            them instead of sitting in 64 registers from kernel start).  The barrier per quarter guards the staging tiles only.
+//            EXIT form: phases 3 / 4 have no registers left (acc4 + fw4), so its four W3 quarters go to LDS in one go behind
+//            phase 1 (8 LDS-DMA loads per wave into the space the old ring slots had: free during phase 2) and are read as before.
+//            The other forms write y with buffer stores the compiler can count: a wait on a W3 fragment leaves the stores in flight.
+// The ring, its slots and 10 of the 22 barriers per patch are gone (12 left: 4 chunk + 1 refill + 1 stage hand-over, T1, T2,
+// 4 quarters; + 1 in front of the quarters in the exit form).  The MFMA operand values and the accumulation order are those of the
+// ring form: every output is bit-identical (tests/test_bottleneck_frag_gpu.py).  The head-only form (FULL = false) has no stream form.
+template <int TW, int NCH, bool FULL, bool PROJ = false, bool EXIT = false, bool WFRAG = false>
 __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const std::conditional_t<EXIT, BnkExitParams, BnkParams> p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int TH = 128 / TW, PW = TW + 2, PH = TH + 2, NPIX = PW * PH;
   static_assert(NPIX <= 192, "halo patch");
   static_assert(!PROJ || (FULL && NCH == 1), "projection form: 64-channel input, whole block");
   static_assert(!EXIT || (FULL && NCH == 4 && !PROJ), "exit form: the 256-wide identity block");
+  static_assert(!WFRAG || FULL, "the fragment stream: whole blocks only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef __attribute__((address_space(3))) void* lds_ptr;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -144,6 +172,11 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const std::con
   const __amdgpu_buffer_rsrc_t rsrc_w3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.w3), 0, (FULL && !now) ? kC * kP * (PROJ ? 4 : 2) : 0, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_tab = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.tab), 0, FULL ? 3072 : 1024, 0x00020000);
   constexpr unsigned kOOB = 0x80000000u;
+  // WFRAG: the one stream behind p.w1; fragment f of it into a register quad (the fragment index is wave-uniform: the scalar offset)
+  [[maybe_unused]] const __amdgpu_buffer_rsrc_t rsrc_ws =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p.w1), 0, (WFRAG && !now) ? frag_count(NCH, PROJ) * 1024 : 0, 0x00020000);
+  [[maybe_unused]] const unsigned lane16 = (unsigned)(lane * 16);
+  [[maybe_unused]] auto ld_frag = [&](int f) { return __builtin_amdgcn_raw_buffer_load_b128(rsrc_ws, lane16, f * 1024, 0); };
 
   // ---- loader lanes --------------------------------------------------------------------------------------------
   // every LDS tile here has 128-byte rows (64 fp16): a 1-KiB wave load covers 8 rows, lane -> (row = lane / 8, 16-byte
@@ -199,7 +232,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const std::con
   // projection form: the shortcut weights of this wave's channel tile, all four quarters x four 16-channel K slices, straight
   // to registers (the oldest loads of the wave: every counted wait below covers them)
   uint4_t fad[PROJ ? 4 : 1][4];
-  if constexpr (PROJ) {
+  if constexpr (PROJ && !WFRAG) {
     const int wc2_ = wave >> 1;
 #pragma unroll
     for (int q = 0; q < 4; ++q)
@@ -209,8 +242,8 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const std::con
   }
   if (wave < (FULL ? 3 : 1))
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_tab, (lds_ptr)(smem + kOffTab + wave * 1024), 16, (unsigned)(lane * 16), wave * 1024, 0, 0);
-  load_item(0);
-  const float* tab = reinterpret_cast<const float*>(smem + kOffTab);
+  if constexpr (!WFRAG) load_item(0);
+  const float* tab =reinterpret_cast<const float*>(smem + kOffTab);
   unsigned long long ts[8];
 #define BNK_TS(i) do { if (p.dbg & 32) ts[i] = __builtin_amdgcn_s_memtime(); } while (0)
   BNK_TS(0);
@@ -246,20 +279,72 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const std::con
   half4_t res[FULL && !PROJ ? 4 : 1][2][4];
   uint4_t fbx[PROJ ? 2 : 1][2][2];      // projection form: the block input at the patch's own pixels as phase 3's pixel operand
 
-  // two 32-KiB stages: chunk c+1 streams while chunk c is multiplied; a stage is refilled (chunk c+2) once every wave is
-  // past its reads — a second barrier per chunk, four chunks
-  load_stage1(0, 0);
-  if constexpr (NCH > 1) load_stage1(1, 1);
+  // WFRAG: register sets of the weight stream.  W1's K-slice of chunk c sits in wa[c & 1], W2's tap t in w2r[t % 3], W3's quarter q
+  // in w3r[q & 1] (projection form: W3' in [0..3], Wd' in [4..7])
+  constexpr int NW3 = PROJ ? 8 : 4;
+  uint4_t wa[WFRAG ? 2 : 1][4], w2r[WFRAG ? 3 : 1][4], w3r[WFRAG && !EXIT ? 2 : 1][NW3];
+  [[maybe_unused]] auto load_w1 = [&](int c) __attribute__((always_inline)) {
+#pragma unroll
+    for (int k16 = 0; k16 < 4; ++k16) wa[c & 1][k16] = ld_frag((c * 2 + wc1) * 4 + k16);
+  };
+  [[maybe_unused]] auto load_w2 = [&](int tap) __attribute__((always_inline)) {
+#pragma unroll
+    for (int kq = 0; kq < 4; ++kq) w2r[tap % 3][kq] = ld_frag(frag_w2(NCH) + (tap * 2 + wc2) * 4 + kq);
+  };
+  [[maybe_unused]] auto load_w3 = [&](int q) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < NW3; ++i) w3r[q & 1][i] = ld_frag(frag_w3(NCH) + (q * 2 + wc2) * NW3 + i);
+  };
+  [[maybe_unused]] auto load_x = [&](int slot, int c) __attribute__((always_inline)) {   // WFRAG: a stage is the 24-KiB x chunk alone
+    char* st = smem + slot * kXChunk;
+#pragma unroll
+    for (int t = 0; t < 6; ++t)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (lds_ptr)(st + (t * 4 + wave) * 1024), 16, x_voff[t],
+                                               x_voff[t] == kOOB ? 0 : c * 128, 0, FT_BNK_XLOAD_AUX);
+  };
+
+  // ring form: two 32-KiB stages: chunk c+1 streams while chunk c is multiplied; a stage is refilled (chunk c+2) once every wave is
+  // past its reads — a second barrier per chunk, four chunks.
+  // WFRAG: three x stages, chunks 0..2 in flight from the start.  Vector-memory order of a wave: [table] W1.0 (4) x.0 (6) W1.1 (4)
+  // x.1 (6) x.2 (6) | chunk 0 | W1.2 (4) x.3 (6, behind the refill barrier) | chunk 1 | W1.3 (4) | chunk 2 | chunk 3, W2 taps 0, 1 —
+  // the counted waits below leave in flight what is younger than the chunk's x AND its W1 slice.
+  if constexpr (WFRAG) {
+    load_w1(0);
+    asm volatile("" ::: "memory");    // compiler fences: the counts below need this issue order
+    load_x(0, 0);
+    if constexpr (NCH > 1) {
+      asm volatile("" ::: "memory");
+      load_w1(1);
+      asm volatile("" ::: "memory");
+      load_x(1, 1);
+      load_x(2, 2);
+    }
+  } else {
+    load_stage1(0, 0);
+    if constexpr (NCH > 1) load_stage1(1, 1);
+  }
   unroll_for<NCH>([&](auto cc) {
     constexpr int c = decltype(cc)::value;
-    if constexpr (c < NCH - 1) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");   // chunk c landed; c+1 (8 loads) may fly
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    if constexpr (WFRAG) {
+      static_assert(NCH == 1 || NCH == 4, "counted waits");
+      if constexpr (c + 1 == NCH) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      else if constexpr (c < 2) asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory");   // c = 0: W1.1 x.1 x.2; c = 1: x.2 W1.2 x.3
+      else asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory");                        // c = 2: x.3 W1.3
+    } else {
+      if constexpr (c < NCH - 1) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");   // chunk c landed; c+1 (8 loads) may fly
+      else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    }
     BNK_BARRIER();
-    const char* st = smem + (c & 1) * kStage1;
+    if constexpr (WFRAG && c + 1 == NCH) {     // W2's first two taps fly under the last chunk's MFMAs and epilogue 1
+      load_w2(0);
+      load_w2(1);
+    }
+    const char* st = smem + (WFRAG ? (c % 3) * kXChunk : (c & 1) * kStage1);
     uint4_t fa[4], fb[4][3];
 #pragma unroll
     for (int k16 = 0; k16 < 4; ++k16) {
-      fa[k16] = *reinterpret_cast<const uint4_t*>(st + kXChunk + (a1_off ^ (k16 << 5)));
+      if constexpr (WFRAG) fa[k16] = wa[c & 1][k16];
+      else fa[k16] = *reinterpret_cast<const uint4_t*>(st + kXChunk + (a1_off ^ (k16 << 5)));
 #pragma unroll
       for (int j = 0; j < 3; ++j) fb[k16][j] = *reinterpret_cast<const uint4_t*>(st + (b1_off[j] ^ (k16 << 5)));
     }
@@ -288,19 +373,41 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const std::con
       for (int j = 0; j < 3; ++j)
         acc1[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, fa[k16]),
                                                          __builtin_bit_cast(half8_t, fb[k16][j]), acc1[j], 0, 0, 0);
-    if constexpr (c + 2 < NCH) {
+    if constexpr (WFRAG) {
+      if constexpr (c + 2 < NCH) load_w1(c + 2);      // into the set this chunk's MFMAs were the last readers of
+      if constexpr (c == 0 && NCH > 3) {              // the one refill: chunk 3 into stage 0
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        BNK_BARRIER();
+        load_x(0, 3);
+      }
+    } else if constexpr (c + 2 < NCH) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       BNK_BARRIER();
       load_stage1(c & 1, c + 2);
     }
   });
-  // the last chunk had vmcnt(0): nothing of this wave is in flight.  Every wave is past its last stage read once it
-  // reaches this barrier: the stage region becomes T1 + the W2 ring.
+  // the last chunk had vmcnt(0): no LDS-DMA load of this wave is in flight.  Every wave is past its last stage read once it
+  // reaches this barrier: the stage region becomes T1 + the W2 ring (WFRAG, exit form: + the four W3 quarters).
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   BNK_BARRIER();
   BNK_TS(1);
-  load_item(1);
-  load_item(2);
+  if constexpr (!WFRAG) {
+    load_item(1);
+    load_item(2);
+  } else if constexpr (EXIT) {
+    // W3 whole, from the fragment stream into the row-major swizzled image phase 3 reads (quarter q at ring_slot(q + 1)): LDS row
+    // wr, 16-byte position lpos holds chunk lc = lpos ^ key of that row = lane 32 * (lc & 1) + wr % 32 of fragment
+    // (q, wr / 32, lc / 2); eight rows of a wave load = eight 128-byte runs of the stream
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int wr = (t * 4 + wave) * 8 + lrow, lc = lpos ^ BNK_KEY(wr);
+        const unsigned vo = (unsigned)((((wr >> 5) * 4 + (lc >> 1)) * 64 + (lc & 1) * 32 + (wr & 31)) * 16);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_ws, (lds_ptr)(smem + ring_slot((q + 1) & 3) + (t * 4 + wave) * 1024), 16, vo,
+                                                 (frag_w3(NCH) + q * 8) * 1024, 0, 0);
+      }
+  }
   {
     char* t1 = smem + kOffT1;
     float4_t sc[4], sh[4];               // read once: the compiler cannot hoist LDS reads over the T1 writes itself
@@ -351,6 +458,45 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const std::con
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc2[j][r] = 0.f;
 
+  if constexpr (WFRAG) {
+    // T1 written by every wave; from here to T2 no barrier: the weights are this wave's own registers
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    BNK_BARRIER();
+    const char* t1 = smem + kOffT1;
+    uint4_t fbt[2][2][2][2];             // [tap & 1][sl][kk][j]: tap t + 1's pixel fragments are read under tap t's MFMAs
+    auto read_t1 = [&](int tap) __attribute__((always_inline)) {
+      const int ky = tap / 3, kx = tap % 3;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int r = r0[j] + ky * PW + kx;
+        const int lsw = lhi ^ bnk_t1_key<TW>(r, c0[j] + kx);
+        const char* rowp = t1 + r * 128;
+#pragma unroll
+        for (int sl = 0; sl < 2; ++sl)
+#pragma unroll
+          for (int kk = 0; kk < 2; ++kk)
+            fbt[tap & 1][sl][kk][j] = *reinterpret_cast<const uint4_t*>(rowp + ((lsw ^ (sl * 4 + kk * 2)) << 4));
+      }
+    };
+    read_t1(0);
+    unroll_for<9>([&](auto tc) {
+      constexpr int tap = decltype(tc)::value;
+      // (scheduling barriers: left alone, hipcc sinks every weight load to two MFMAs in front of its first use — the look-ahead is gone)
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (tap + 2 < 9) load_w2(tap + 2);                 // two taps ahead
+      else if constexpr (tap == 7 && !EXIT) load_w3(0);            // then W3's first quarter
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (tap + 1 < 9) read_t1(tap + 1);
+#pragma unroll
+      for (int sl = 0; sl < 2; ++sl)
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+          for (int j = 0; j < 2; ++j)
+            acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, w2r[tap % 3][sl * 2 + kk]),
+                                                             __builtin_bit_cast(half8_t, fbt[tap & 1][sl][kk][j]), acc2[j], 0, 0, 0);
+    });
+  } else
   unroll_for<9>([&](auto tc) {
     constexpr int tap = decltype(tc)::value;
     constexpr int ky = tap / 3, kx = tap % 3;
@@ -443,7 +589,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const std::con
     }
     return;
   }
-  load_item(12);
+  if constexpr (!WFRAG) load_item(12);
 
   // ================= phase 3: y = relu(bn3(W3 . t2) + x), four quarters of 64 output channels ====================
   // exit form: 64 more accumulator registers live through phase 3, so T2's fragments are read again in every quarter instead of
@@ -475,14 +621,18 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const std::con
       else if (p.y_mode == FT_BNK_Y_NONE) spix[i] = -1;
     }
   }
-  // every W3 quarter and the residuals have landed; every wave holds its T2 fragments (staging B reuses the T2 region)
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  BNK_BARRIER();
+  // every W3 quarter and the residuals have landed; every wave holds its T2 fragments (staging B reuses the T2 region).
+  // WFRAG, not the exit form: W3 is in this wave's registers and nothing waits here — staging A is the T1 region, dead since the
+  // barrier above, and staging B is first written behind quarter 0's barrier, which every wave reaches with its T2 fragments read.
+  if constexpr (!WFRAG || EXIT) {
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    BNK_BARRIER();
+  }
   BNK_TS(5);
 
   unroll_for<4>([&](auto qc) {
     constexpr int q = decltype(qc)::value;
-    const char* wq = smem + ring_slot((q + 1) & 3);
+    [[maybe_unused]] const char* wq = smem + ring_slot((q + 1) & 3);
     float16_t acc3[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
@@ -492,11 +642,18 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const std::con
       if constexpr (q < 3) load_tail(q + 1);
       BNK_LOAD_FB3();
     }
+    if constexpr (WFRAG && !EXIT && q < 3) {                     // one quarter ahead
+      __builtin_amdgcn_sched_barrier(0);
+      load_w3(q + 1);
+      __builtin_amdgcn_sched_barrier(0);
+    }
 #pragma unroll
     for (int sl = 0; sl < 2; ++sl)
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
-        const uint4_t fa = *reinterpret_cast<const uint4_t*>(wq + (a2_off ^ ((sl * 2 + kk) << 5)));
+        uint4_t fa;
+        if constexpr (WFRAG && !EXIT) fa = w3r[q & 1][sl * 2 + kk];
+        else fa = *reinterpret_cast<const uint4_t*>(wq + (a2_off ^ ((sl * 2 + kk) << 5)));
 #pragma unroll
         for (int j = 0; j < 2; ++j)
           acc3[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, fa),
@@ -508,9 +665,13 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const std::con
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc3[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, fad[q][sl * 2 + kk]),
+          for (int j = 0; j < 2; ++j) {
+            uint4_t fd;
+            if constexpr (WFRAG) fd = w3r[q & 1][4 + sl * 2 + kk];
+            else fd = fad[q][sl * 2 + kk];
+            acc3[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(half8_t, fd),
                                                              __builtin_bit_cast(half8_t, fbx[sl][kk][j]), acc3[j], 0, 0, 0);
+          }
     }
     char* so = smem + ((q & 1) ? kOutB : kOffOutA);
     float4_t sc[4], sh[4];
@@ -542,7 +703,19 @@ __global__ __launch_bounds__(256, 2) void bottleneck_fused_kernel(const std::con
     // one barrier per quarter: the two staging buffers alternate, a buffer's previous readers are two barriers behind
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     BNK_BARRIER();
-    if constexpr (!EXIT) {
+    if constexpr (WFRAG && !EXIT) {
+      // buffer stores, which the compiler counts (store_out16 is opaque to it): its waits on the W3 fragments of the next quarter,
+      // loaded in front of these stores, then leave the stores in flight.  32-bit offsets: supported() bounds y for wfrag.
+      const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(
+          p.y, 0, (p.dbg & 4) ? 0 : (unsigned)((size_t)p.N * p.H * p.W * p.y_cstride * 2), 0x00020000);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int idx = tid + 256 * i, m = idx >> 3, ch = idx & 7;
+        const uint4_t v = *reinterpret_cast<const uint4_t*>(so + m * 128 + ((ch ^ BNK_KEY(m)) << 4));
+        const unsigned vo = spix[i] >= 0 ? (unsigned)((spix[i] * p.y_cstride + p.y_coff + q * 64 + ch * 8) * 2) : kOOB;
+        __builtin_amdgcn_raw_buffer_store_b128(v, rsrc_y, vo, 0, FT_YSTORE_BUF_AUX);
+      }
+    } else if constexpr (!EXIT) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int idx = tid + 256 * i, m = idx >> 3, ch = idx & 7;
@@ -633,6 +806,9 @@ static int supported(const ft_bottleneck_desc* d) {
   if (d->N <= 0 || d->H <= 0 || d->W <= 0) return FT_ERR_INVALID_ARG;
   if (d->dtype != FT_F16 || d->P != kP || d->stride > 1) return FT_ERR_UNSUPPORTED;
   if (d->head_only && d->projection) return FT_ERR_INVALID_ARG;
+  if (d->wfrag != 0 && d->wfrag != 1) return FT_ERR_INVALID_ARG;
+  if (d->wfrag && d->head_only) return FT_ERR_UNSUPPORTED;      // the head-only form has no fragment-stream kernel
+  if (d->wfrag && (long long)d->N * d->H * d->W * d->y_cstride * 2 >= (1LL << 31)) return FT_ERR_UNSUPPORTED;   // its y goes through buffer stores
   if (d->head_only || d->projection ? d->C != 64 : d->C != kC) return FT_ERR_UNSUPPORTED;   // (256-wide head-only: no caller, not instantiated)
   const int yc = d->head_only ? d->P : kC;
   if (d->x_coff < 0 || d->y_coff < 0 || d->x_coff % 8 || d->y_coff % 8 || d->x_cstride % 8 || d->y_cstride % 8) return FT_ERR_UNSUPPORTED;
@@ -652,6 +828,36 @@ __global__ __launch_bounds__(256) void bnk_tail_pack_kernel(const half_t* __rest
   out[idx] = *reinterpret_cast<const uint4_t*>(w + (size_t)co * kpad + k);
 }
 
+// the fragment stream of the WFRAG forms (layout: frag_w2 / frag_w3 above) from the three packed weight blocks: W1 [64][64 nch],
+// W2 [64][576], W3 [256][64] (projection form [256][W3' 64 | Wd' 64]).  One thread per 16 bytes; the fp16 values are copied as they are.
+__global__ __launch_bounds__(256) void bnk_frag_pack_kernel(const half_t* __restrict__ w1, const half_t* __restrict__ w2,
+                                                            const half_t* __restrict__ w3, uint4_t* __restrict__ out, int nch, int proj) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;      // frag_count * 64 = a multiple of 256
+  const int lane = idx & 63, f = idx >> 6;
+  const int l31 = lane & 31, k8 = 8 * (lane >> 5);
+  const half_t* src;
+  if (f < frag_w2(nch)) {
+    const int c = f >> 3, wc = (f >> 2) & 1, k16 = f & 3;
+    src = w1 + (size_t)(wc * 32 + l31) * (nch * 64) + c * 64 + k16 * 16 + k8;
+  } else if (f < frag_w3(nch)) {
+    const int g = f - frag_w2(nch), tap = g >> 3, wc = (g >> 2) & 1, kq = g & 3;
+    src = w2 + (size_t)(wc * 32 + l31) * (9 * kP) + tap * 64 + kq * 16 + k8;
+  } else if (!proj) {
+    const int g = f - frag_w3(nch), q = g >> 3, wc = (g >> 2) & 1, kq = g & 3;
+    src = w3 + (size_t)(q * 64 + wc * 32 + l31) * kP + kq * 16 + k8;
+  } else {
+    const int g = f - frag_w3(nch), q = g >> 4, wc = (g >> 3) & 1, i = g & 7;
+    src = w3 + (size_t)(q * 64 + wc * 32 + l31) * (2 * kP) + i * 16 + k8;
+  }
+  out[idx] = *reinterpret_cast<const uint4_t*>(src);
+}
+
+// 0 when the descriptor has no stream form (unsupported, or head-only)
+static long long frag_bytes(const ft_bottleneck_desc* d) {
+  if (supported(d) != FT_OK || d->head_only) return 0;
+  return (long long)frag_count(d->C / 64, d->projection != 0) * 1024;
+}
+
 static int exit_supported(const ft_bottleneck_desc* d, int tail_cout, int t1_cstride, int t1_coff, int y_mode) {
   const int st = supported(d);
   if (st != FT_OK) return st;
@@ -665,18 +871,18 @@ static int exit_supported(const ft_bottleneck_desc* d, int tail_cout, int t1_cst
   return FT_OK;
 }
 
-template <int TW>
+template <int TW, bool WFRAG = false>
 static int launch_exit(const BnkExitParams& p, hipStream_t s) {
-  auto k = bottleneck_fused_kernel<TW, 4, true, false, true>;
+  auto k = bottleneck_fused_kernel<TW, 4, true, false, true, WFRAG>;
   FT_RAISE_LDS(k, kLdsBytes);
   hipLaunchKernelGGL(k, dim3(p.total), dim3(256), kLdsBytes, s, p);
   FT_LAUNCH_CHECK("bottleneck_fused_kernel(exit)");
   return FT_OK;
 }
 
-template <int TW, int NCH, bool FULL, bool PROJ = false>
+template <int TW, int NCH, bool FULL, bool PROJ = false, bool WFRAG = false>
 static int launch(const BnkParams& p, hipStream_t s) {
-  auto k = bottleneck_fused_kernel<TW, NCH, FULL, PROJ>;
+  auto k = bottleneck_fused_kernel<TW, NCH, FULL, PROJ, false, WFRAG>;
   FT_RAISE_LDS(k, kLdsBytes);
   hipLaunchKernelGGL(k, dim3(p.total), dim3(256), kLdsBytes, s, p);
   FT_LAUNCH_CHECK("bottleneck_fused_kernel");
@@ -724,14 +930,35 @@ extern "C" int ft_bottleneck_fwd(const ft_bottleneck_desc* d, const void* x, con
   using namespace ft;
   const int st = supported(d);
   if (st != FT_OK) return st;
-  if (!x || !w1 || !w2 || (!w3 && !d->head_only) || !scale_shift || !y) return FT_ERR_INVALID_ARG;
+  if (!x || !w1 || !scale_shift || !y) return FT_ERR_INVALID_ARG;
+  if (d->wfrag ? (w2 || w3) : (!w2 || (!w3 && !d->head_only))) return FT_ERR_INVALID_ARG;   // wfrag: w1 is the whole stream
   BnkParams p{};
   fill_params(p, d, x, w1, w2, w3, scale_shift, y);
   hipStream_t s = as_stream(stream);
   const bool tall = d->W % 16 != 0 && d->W % 8 == 0;
   if (d->head_only) return tall ? launch<8, 1, false>(p, s) : launch<16, 1, false>(p, s);
+  if (d->wfrag) {
+    if (d->projection) return tall ? launch<8, 1, true, true, true>(p, s) : launch<16, 1, true, true, true>(p, s);
+    return tall ? launch<8, 4, true, false, true>(p, s) : launch<16, 4, true, false, true>(p, s);
+  }
   if (d->projection) return tall ? launch<8, 1, true, true>(p, s) : launch<16, 1, true, true>(p, s);
   return tall ? launch<8, 4, true>(p, s) : launch<16, 4, true>(p, s);
+}
+
+extern "C" long long ft_bottleneck_frag_bytes(const ft_bottleneck_desc* d) { return d ? ft::frag_bytes(d) : 0; }
+
+extern "C" int ft_bottleneck_frag_pack(const ft_bottleneck_desc* d, const void* w1, const void* w2, const void* w3, void* out,
+                                       ft_stream_t stream) {
+  using namespace ft;
+  const int st = supported(d);
+  if (st != FT_OK) return st;
+  if (d->head_only) return FT_ERR_UNSUPPORTED;
+  if (!w1 || !w2 || !w3 || !out) return FT_ERR_INVALID_ARG;
+  const int nch = d->C / 64, proj = d->projection != 0;
+  hipLaunchKernelGGL(bnk_frag_pack_kernel, dim3(frag_count(nch, proj) / 4), dim3(256), 0, as_stream(stream), static_cast<const half_t*>(w1),
+                     static_cast<const half_t*>(w2), static_cast<const half_t*>(w3), static_cast<uint4_t*>(out), nch, proj);
+  FT_LAUNCH_CHECK("bnk_frag_pack_kernel");
+  return FT_OK;
 }
 
 extern "C" int ft_bottleneck_exit_supported(const ft_bottleneck_desc* d, int tail_cout, int t1_cstride, int t1_coff, int y_mode) {
@@ -761,8 +988,9 @@ extern "C" int ft_bottleneck_exit_fwd(const ft_bottleneck_desc* d, const void* x
   using namespace ft;
   const int st = exit_supported(d, tail_cout, t1_cstride, t1_coff, y_mode);
   if (st != FT_OK) return st;
-  if (!x || !w1 || !w2 || !w3 || !scale_shift || (!y && y_mode != FT_BNK_Y_NONE) || !tail_wstream || !tail_scale || !tail_shift || !t1)
+  if (!x || !w1 || !scale_shift || (!y && y_mode != FT_BNK_Y_NONE) || !tail_wstream || !tail_scale || !tail_shift || !t1)
     return FT_ERR_INVALID_ARG;
+  if (d->wfrag ? (w2 || w3) : (!w2 || !w3)) return FT_ERR_INVALID_ARG;      // wfrag: w1 is the whole stream
   BnkExitParams p{};
   fill_params(p, d, x, w1, w2, w3, scale_shift, y);
   p.tw = static_cast<const char*>(tail_wstream);
@@ -775,5 +1003,6 @@ extern "C" int ft_bottleneck_exit_fwd(const ft_bottleneck_desc* d, const void* x
   p.y_bytes = (unsigned)(ypix * d->y_cstride * 2);
   p.t1_bytes = (unsigned)((size_t)d->N * d->H * d->W * t1_cstride * 2);
   const bool tall = d->W % 16 != 0 && d->W % 8 == 0;
+  if (d->wfrag) return tall ? launch_exit<8, true>(p, as_stream(stream)) : launch_exit<16, true>(p, as_stream(stream));
   return tall ? launch_exit<8>(p, as_stream(stream)) : launch_exit<16>(p, as_stream(stream));
 }

@@ -1255,8 +1255,41 @@ def _bottleneck_packed(conv: "FusedConv", x: ActView, want, label: str):
     return w, scale, shift
 
 
+def bottleneck_wfrag(exit_form: bool = False) -> bool:
+    """The 64-plane identity and projection blocks take their weights as one fragment-ordered stream (ft_bottleneck_desc.wfrag = 1).
+    The exit form has the stream kernel too but lost its A/B at batch 64 (profiles/HISTORY.md, "fragment stream") and stays on the
+    LDS ring.  FT_BNK_WFRAG (dev, read at record time): 0 = the three packed layouts and the ring kernel for every form, 1 = the
+    stream for every form, the exit form included."""
+    env = os.environ.get("FT_BNK_WFRAG")
+    return not exit_form if env is None else env != "0"
+
+
+def _bottleneck_set_wfrag(d: _lib.BottleneckDesc, exit_form: bool = False) -> bool:
+    """Sets d.wfrag = 1 where the switch is on and the library takes the stream form of this descriptor (it bounds y to 2 GiB)."""
+    d.wfrag = 1 if bottleneck_wfrag(exit_form) else 0
+    if d.wfrag and _lib.load().ft_bottleneck_supported(ctypes.byref(d)) != 0:
+        d.wfrag = 0
+    return bool(d.wfrag)
+
+
+def _bottleneck_frag_stream(c1: "FusedConv", d: _lib.BottleneckDesc, w1, w2, w3):
+    """The weight stream of ft_bottleneck_desc.wfrag = 1 for this conv triple: built once per packed weight set, cached where
+    c1's packed weights are."""
+    key = ("bnk_frag", w1.data_ptr(), w2.data_ptr(), w3.data_ptr(), int(d.projection))
+    cached = c1._packed.get(key)
+    if cached is None:
+        lib = _lib.load()
+        stream = torch.empty(int(lib.ft_bottleneck_frag_bytes(ctypes.byref(d))), dtype=torch.uint8, device=w1.device)
+        check(lib.ft_bottleneck_frag_pack(ctypes.byref(d), w1.data_ptr(), w2.data_ptr(), w3.data_ptr(), stream.data_ptr(),
+                                          current_stream_handle(w1.device)), "ft_bottleneck_frag_pack")
+        torch.cuda.current_stream(w1.device).synchronize()
+        cached = c1._packed[key] = (stream, w1, w2, w3)       # the sources stay alive: their addresses are the key
+    return cached[0]
+
+
 def record_bottleneck_head(prog: Program, c1: "FusedConv", c2: "FusedConv", x: ActView, t2: ActView, label: str) -> None:
-    """conv1 + bn1 + relu -> conv2 + bn2 + relu of a stage's entry block as one launch (ft_bottleneck_fwd, head_only)."""
+    """conv1 + bn1 + relu -> conv2 + bn2 + relu of a stage's entry block as one launch (ft_bottleneck_fwd, head_only).
+    (This form has no fragment-stream kernel: it stays on the LDS ring.)"""
     lib = _lib.load()
     planes = c2.cin
     w1, s1, b1 = _bottleneck_packed(c1, x, (planes, x.C, 1), label)
@@ -1364,6 +1397,11 @@ def record_bottleneck_entry(prog: Program, c1: "FusedConv", c2: "FusedConv", sc:
     prog.fused_records.append((label, len(prog.calls), flops))
     table = torch.cat([t.flatten()[:planes].float() for t in (s1, b1, s2, b2)] +
                       [torch.ones(4 * planes, dtype=torch.float32, device=x.t.device), shift3.flatten()[:4 * planes].float()]).contiguous()
+    if _bottleneck_set_wfrag(d):
+        ws = _bottleneck_frag_stream(c1, d, w1, w2, w3)
+        prog.add("ft_bottleneck_fwd", ctypes.byref(d), x.t.data_ptr(), ws.data_ptr(), None, None, table.data_ptr(),
+                 y.t.data_ptr(), keep=(d, x.t, y.t, ws, table))
+        return
     prog.add("ft_bottleneck_fwd", ctypes.byref(d), x.t.data_ptr(), w1.data_ptr(), w2.data_ptr(), w3.data_ptr(), table.data_ptr(),
              y.t.data_ptr(), keep=(d, x.t, y.t, w1, w2, w3, table))
 
@@ -1553,6 +1591,11 @@ def record_bottleneck(prog: Program, c1: "FusedConv", c2: "FusedConv", c3: "Fuse
         prog.add("ft_bottleneck_rstat_fwd", ctypes.byref(d), x.t.data_ptr(), wpack.data_ptr(), y.t.data_ptr(), keep=(d, x.t, y.t, wpack))
         return
     table = torch.cat([t.flatten()[:n] for t, n in ((s1, planes), (b1, planes), (s2, planes), (b2, planes), (s3, x.C), (b3, x.C))]).contiguous()
+    if _bottleneck_set_wfrag(d):
+        ws = _bottleneck_frag_stream(c1, d, w1, w2, w3)
+        prog.add("ft_bottleneck_fwd", ctypes.byref(d), x.t.data_ptr(), ws.data_ptr(), None, None, table.data_ptr(),
+                 y.t.data_ptr(), keep=(d, x.t, y.t, ws, table))
+        return
     prog.add("ft_bottleneck_fwd", ctypes.byref(d), x.t.data_ptr(), w1.data_ptr(), w2.data_ptr(), w3.data_ptr(), table.data_ptr(),
              y.t.data_ptr(), keep=(d, x.t, y.t, w1, w2, w3, table))
 
@@ -1630,6 +1673,12 @@ def record_bottleneck_exit(prog: Program, c1: "FusedConv", c2: "FusedConv", c3: 
     flops = float(lib.ft_bottleneck_flops(ctypes.byref(d))) + 2.0 * x.N * x.H * x.W * x.C * tail.cout
     prog.flops += flops
     prog.fused_records.append((label, len(prog.calls), flops))
+    if _bottleneck_set_wfrag(d, exit_form=True):
+        ws = _bottleneck_frag_stream(c1, d, w1, w2, w3)
+        prog.add("ft_bottleneck_exit_fwd", ctypes.byref(d), x.t.data_ptr(), ws.data_ptr(), None, None, table.data_ptr(),
+                 y.t.data_ptr() if y is not None else None, mode, tail.cout, wstream.data_ptr(), tscale.data_ptr(), tshift.data_ptr(),
+                 t1.t.data_ptr(), t1.cstride, t1.coff, keep=(d, x.t, y.t if y is not None else None, t1.t, ws, table, wstream, tscale, tshift))
+        return
     prog.add("ft_bottleneck_exit_fwd", ctypes.byref(d), x.t.data_ptr(), w1.data_ptr(), w2.data_ptr(), w3.data_ptr(), table.data_ptr(),
              y.t.data_ptr() if y is not None else None, mode, tail.cout, wstream.data_ptr(), tscale.data_ptr(), tshift.data_ptr(),
              t1.t.data_ptr(), t1.cstride, t1.coff, keep=(d, x.t, y.t if y is not None else None, t1.t, w1, w2, w3, table, wstream, tscale, tshift))

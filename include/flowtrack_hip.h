@@ -294,6 +294,11 @@ typedef struct ft_bottleneck_desc {
                              pairs, hi = fp16(shift) in bits 0-15, lo = fp16(shift - hi) in bits 16-31.  The kernels add the shift and
                              the identity residual as extra MFMA k-steps and their epilogues are fp16(relu(acc)).  0 = the scale /
                              shift tables of round 2. */
+  int wfrag;              /* ft_bottleneck_fwd / ft_bottleneck_exit_fwd only (appended: zero-initialised descriptors of older callers keep
+                             their meaning).  0: w1 / w2 / w3 are the three ft_conv_pack_geometry layouts.  1: w1 is the ONE
+                             fragment-ordered stream ft_bottleneck_frag_pack built from them and w2 = w3 = NULL; the launch then takes
+                             its weights from L2 straight to registers.  Same fp16 values, same accumulation order: bit-identical
+                             outputs.  Not with head_only (FT_ERR_UNSUPPORTED). */
 } ft_bottleneck_desc;
 int ft_bottleneck_supported(const ft_bottleneck_desc* d);   /* FT_OK or FT_ERR_UNSUPPORTED / FT_ERR_INVALID_ARG */
 int ft_bottleneck_fwd(const ft_bottleneck_desc* d, const void* x,
@@ -301,6 +306,18 @@ int ft_bottleneck_fwd(const ft_bottleneck_desc* d, const void* x,
                       const float* scale_shift, void* y, ft_stream_t stream);
 /* algorithmic FLOPs of the three convs (2*MACs, no halo recompute) */
 double ft_bottleneck_flops(const ft_bottleneck_desc* d);
+/* The weight stream of ft_bottleneck_desc.wfrag = 1, built once per weight set.  It is a sequence of 1-KiB fragments in the order a
+ * wave reads them; a fragment is the A operand of one mfma_f32_32x32x16_f16: 64 lanes x 16 bytes, lane l holds row 32 * tile + l % 32
+ * of a weight block, the eight k from 16 * slice + 8 * (l / 32).  With nch = C / 64:
+ *   W1  [chunk nch][tile 2][slice 4]    rows = output channels of conv1, k = 64 * chunk + ...
+ *   W2  [tap 9][tile 2][slice 4]        rows = output channels of conv2, k = 64 * tap + ...
+ *   W3  [quarter 4][tile 2][slice 4]    rows = 64 * quarter + 32 * tile + ... of conv3; projection = 1: [quarter 4][tile 2][8], the
+ *                                       four slices of W3' (k 0..63 of the K-concatenated rows), then the four of Wd' (k 64..127)
+ * ft_bottleneck_frag_bytes = 1024 * (8 nch + 72 + 32) = 139 264 for C = 256, 1024 * (8 + 72 + 64) = 147 456 with projection = 1;
+ * 0 when the descriptor has no stream form (unsupported, or head_only).  ft_bottleneck_frag_pack takes w1 / w2 / w3 exactly as
+ * ft_bottleneck_fwd with wfrag = 0 does and copies the fp16 values unchanged. */
+long long ft_bottleneck_frag_bytes(const ft_bottleneck_desc* d);
+int ft_bottleneck_frag_pack(const ft_bottleneck_desc* d, const void* w1, const void* w2, const void* w3, void* out, ft_stream_t stream);
 
 /* Exit form of ft_bottleneck_fwd for a stage's LAST identity block (fp16, C = 256, P = 64, even H and W): the same block plus the
  * 1x1 conv + bn + relu that opens the next stage (layer2.0.conv1 of the ResNets, 256 -> tail_cout = 128, resnet.py:37-43) in one

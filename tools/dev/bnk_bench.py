@@ -43,8 +43,8 @@ if len(sys.argv) > 4 and sys.argv[4].startswith("exit"):
     sys.exit(0)
 prog = Program(torch.cuda.Stream())
 for _ in range(4):           # ping-pong like the network does, 4 launches per pass
-    record_bottleneck(prog, c1, c2, c3, x, y, "a")
-    record_bottleneck(prog, c1, c2, c3, y, y2, "b")
+    record_bottleneck(prog, c1, c2, c3, x, y, "a", form="patch")      # the kernel the FT_BNK_DBG knobs belong to, as the network records it
+    record_bottleneck(prog, c1, c2, c3, y, y2, "b", form="patch")
 torch.cuda.synchronize()
 prog.run_eager(); prog.stream.synchronize()
 t = prog.time_calls(iters=10)

@@ -16,7 +16,7 @@ c3 = FusedConv(synth.normal(1, "w3", (256, 64, 1, 1), std=0.17), bn=bn(256), **m
 x = ActView(torch.randn((B, H, W, 256), device=dev).to(dt), 256, 0)
 y = ActView(torch.zeros((B, H, W, 256), dtype=dt, device=dev), 256, 0)
 prog = Program(torch.cuda.Stream())
-record_bottleneck(prog, c1, c2, c3, x, y, "a")
+record_bottleneck(prog, c1, c2, c3, x, y, "a", form="patch")     # (the default form at this shape is the strip kernel: no stamps)
 torch.cuda.synchronize()
 for _ in range(3):
     prog.run_eager(); prog.stream.synchronize()
